@@ -7,16 +7,27 @@ backward (+ gradient all-reduce for N > 1) + Adam -- HRNet-W48 + SMPL LBS + IUV 
          --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  `value` is the whole-job aggregate (all ranks), timed over
-exactly K steps between barrier + synchronize pairs, max over ranks.  `roofline` is for the
-kernel instance with the largest total time (measured live with HIP events on the launch
-stream during the timed steps); `cpu_baseline` times the CPU oracle (plain-torch fp32 HRNet
-step + C LBS + C raster) on the host cores on a bounded sample.
+exactly K steps between barrier + synchronize pairs, max over ranks.  A plain run sets up,
+warms up, times the K steps and prints the line; everything else it can measure runs only
+with `--full`: `roofline` for the kernel instance with the largest total time (one extra
+eager step with every conv launch bracketed by HIP events), `roofline_extra` (the geometry
+kernels, timed on their own), the `fp32` sub-record (BASELINE config C4, re-captured) and
+`cpu_baseline` (the CPU oracle -- plain-torch fp32 HRNet step + C LBS + C raster -- on the
+host cores on a bounded sample).
+
+`--dump-outputs DIR` writes what the last timed step returned -- its outputs and losses --
+and a sample of the parameters it updated as DIR/<name>.npy (float32, or float64 for
+float64 / integer tensors), at most DUMP_BUDGET_BYTES in all: an array above its share of
+the budget is a fixed sample of its flattened elements (seeded by its name and size).  The
+inputs and the initial weights are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 import torch
 import torch.distributed as dist
@@ -78,6 +89,54 @@ def _flush_c_stdio():
         pass
 
 
+DUMP_BUDGET_BYTES = 48 << 20          # --dump-outputs: the arrays' data in all (the .npy headers fit in what is left of 64 MB)
+
+
+def _tensor_leaves(obj, name, seen):
+    """(name, tensor) for every tensor in nested dicts / lists / tuples, in their order; a tensor met twice is kept once."""
+    if torch.is_tensor(obj):
+        if id(obj) not in seen:
+            seen.add(id(obj))
+            yield name, obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from _tensor_leaves(v, '%s.%s' % (name, k), seen)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            yield from _tensor_leaves(v, '%s.%d' % (name, i), seen)
+
+
+def dump_outputs(path, step_out, params):
+    """Write the step's returned tensors (`step_out` = (out, losses)) and the parameters (one flat array) as path/<name>.npy.
+    Every array gets an equal share of DUMP_BUDGET_BYTES; a larger one is reduced to a sample of its flattened elements at
+    positions drawn from a generator seeded by its name and element count, so that the same arguments give the same positions.
+    Returns {name: (shape of the full tensor, elements written)}."""
+    import numpy as np
+    out, losses = step_out
+    seen = set()
+    arrays = list(_tensor_leaves(losses, 'losses', seen)) + list(_tensor_leaves(out, 'out', seen))
+    arrays.append(('params', torch.cat([p.detach().reshape(-1).float() for p in params])))
+    cap = max(1, DUMP_BUDGET_BYTES // 8 // len(arrays))       # (elements per array: 8 bytes each, the float64 worst case)
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, t in arrays:
+        name = ''.join(c if c.isalnum() or c in '._-' else '_' for c in name)
+        t = t.detach()
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            rng = np.random.default_rng(zlib.crc32(('%s:%d' % (name, flat.numel())).encode()))
+            idx = np.sort(rng.choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.cpu()
+        else:
+            a = t.cpu()
+        wide = a.dtype == torch.float64 or not (a.is_floating_point() or a.dtype == torch.bool)
+        a = a.to(torch.float64 if wide else torch.float32).numpy()
+        np.save(os.path.join(path, name + '.npy'), a)
+        written[name] = (tuple(t.shape), int(a.size))
+    return written
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -85,8 +144,13 @@ def parse():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=32, help='images per GPU (BASELINE: 32)')
     ap.add_argument('--size', type=int, default=256, help='input resolution (BASELINE: 256)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-fp32', action='store_true', help='skip the fp32 (BASELINE config C4) sub-record')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the roofline (one profiled eager step), the geometry kernels, the fp32 (BASELINE config C4) '
+                         'sub-record and the CPU baseline; a plain run times the steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, sampled to fit 64 MB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-fp32', action='store_true', help='--full: skip the fp32 (BASELINE config C4) sub-record')
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
     ap.add_argument('--cpu-batch', type=int, default=8)
     ap.add_argument('--dtype', choices=('bf16', 'fp32'), default='bf16',
@@ -96,7 +160,10 @@ def parse():
     ap.add_argument('--dry', action='store_true',
                     help='launch-line check: build the trainer, capture, run ONE step and print the line (allreduce record included) without the '
                          'roofline / geometry / fp32 / CPU legs -- what a multi-GPU launch does first, cheap enough for a test')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def _cpu_model():
@@ -207,19 +274,27 @@ def geometry_rooflines(tr, B, size, dev):
             mk('iuv_raster forward (project+faces+resolve)', by_r, t_r)]
 
 
-def fp32_record(args, tr, batch, world, dev):
+def fp32_record(args, tr, batch, world, dev, headline=False):
     """BASELINE config C4 (the full train step in fp32, the reference's own arithmetic type): the same model and step with fp32
     NHWC activations on the fp32 MFMA kernels (csrc/conv_f32m.hip, norm_act_f32.hip), replayed from a hipGraph when the
-    capture succeeds.  Returns the timing record (every rank must call it: the step holds the gradient all-reduces)."""
+    capture succeeds.  Returns (the timing record, what the last timed step returned); every rank must call it: the step holds
+    the gradient all-reduces.  `headline` (--dtype fp32): --steps / --warmup steps; otherwise (the sub-record of a --full
+    bf16 run) 10 - 20 steps after 2."""
     from danet_densepose2smpl_amd import conv
     from danet_densepose2smpl_amd import nn as _dnn
-    steps, warm = (1 if args.dry else max(10, min(args.steps, 20))), 2
+    if args.dry:
+        steps, warm = 1, 2
+    elif headline:
+        steps, warm = args.steps, args.warmup
+    else:
+        steps, warm = max(10, min(args.steps, 20)), 2
     roof = None
     with conv.precision('fp32'):
         exec_mode = 'eager'
         if not args.dry:
-            # the fp32 step's own roofline: the conv launches of one eager step bracketed by HIP events, against the fp32 MFMA peak
             tr.train_step(batch)
+        if args.full and not args.dry:
+            # the fp32 step's own roofline: the conv launches of one eager step bracketed by HIP events, against the fp32 MFMA peak
             summ, dominant = profile_step(tr, batch, dev)
             if dominant is not None:
                 n, secs, flops = summ[dominant]
@@ -254,16 +329,19 @@ def fp32_record(args, tr, batch, world, dev):
         elapsed = float(t.item())
     losses = out[1] if isinstance(out, tuple) else out
     finite = bool(all(torch.isfinite(v).all() for v in losses.values())) if isinstance(losses, dict) else None
-    return {'dtype': 'f32', 'value': round(world * args.batch * steps / elapsed, 2), 'unit': 'images/sec', 'ms_per_step': round(elapsed / steps * 1e3, 2),
-            'steps': steps, 'warmup': warm, 'exec': exec_mode, 'finite_losses': finite, 'roofline': roof,
-            'whole_step_mfma': whole_step_mfma(args.batch, args.size, elapsed / steps * 1e3, PEAK_FP32_MFMA_TFLOPS),
-            'workload': 'BASELINE config C4 arithmetic: the same full train step with fp32 NHWC activations; convolutions on '
-                        'v_mfma_f32_16x16x4_f32 (conv_f32m.hip), BatchNorm / fuse sums / STN on the fp32 instantiation of the HIP kernels'}
+    rec = {'dtype': 'f32', 'value': round(world * args.batch * steps / elapsed, 2), 'unit': 'images/sec', 'ms_per_step': round(elapsed / steps * 1e3, 2),
+           'steps': steps, 'warmup': warm, 'exec': exec_mode, 'finite_losses': finite, 'roofline': roof,
+           'whole_step_mfma': whole_step_mfma(args.batch, args.size, elapsed / steps * 1e3, PEAK_FP32_MFMA_TFLOPS),
+           'workload': 'BASELINE config C4 arithmetic: the same full train step with fp32 NHWC activations; convolutions on '
+                       'v_mfma_f32_16x16x4_f32 (conv_f32m.hip), BatchNorm / fuse sums / STN on the fp32 instantiation of the HIP kernels'}
+    return rec, out
 
 
 def fp32_line(args, tr, batch, world, rank, dev):
-    rec = fp32_record(args, tr, batch, world, dev)
+    rec, out = fp32_record(args, tr, batch, world, dev, headline=True)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, tr.model.parameters())
         B = args.batch
         print(json.dumps({'metric': 'images/sec fwd+bwd HRNet-W48+SMPL+IUV 256x256 bs32/GPU', 'value': rec['value'],
                           'unit': 'images/sec', 'n_gpus': world, 'steps': rec['steps'], 'warmup': rec['warmup'],
@@ -353,9 +431,8 @@ def main():
 
     if args.dry:
         args.steps, args.warmup, args.no_fp32, args.no_cpu_baseline = 1, 0, True, True
-    # One eager step with every conv launch bracketed by HIP events (on the launch stream) finds the
-    # dominant kernel instance and gives its per-launch durations -- the same kernels, shapes and
-    # data as the timed steps (which replay them from a hipGraph, where events cannot be recorded).
+    measure_more = args.full and not args.dry       # the legs beside the headline figure: roofline, geometry, fp32, CPU
+
     def stage(tag):              # DANET_BENCH_STAGES=1: the grid-barrier error word after each stage (stderr)
         if os.environ.get('DANET_BENCH_STAGES'):
             torch.cuda.synchronize(dev)
@@ -366,7 +443,10 @@ def main():
     torch.cuda.synchronize(dev)
     stage('two eager steps')
     summ, dominant = {}, None
-    if not args.dry:
+    if measure_more:
+        # One eager step with every conv launch bracketed by HIP events (on the launch stream) finds the
+        # dominant kernel instance and gives its per-launch durations -- the same kernels, shapes and
+        # data as the timed steps (which replay them from a hipGraph, where events cannot be recorded).
         summ, dominant = profile_step(tr, batch, dev)
     stage('profile_step')
     use_graph = not args.no_graph
@@ -387,7 +467,7 @@ def main():
     _flush_c_stdio()      # RCCL's start-up banner sits in the C stdio buffer of every rank: emit it now, not after the JSON line
     t0 = time.time()
     for _ in range(args.steps):
-        step()
+        out = step()
     sync()
     elapsed = time.time() - t0
     elapsed_local = elapsed
@@ -395,9 +475,10 @@ def main():
     # what the timed steps computed must be numbers: the last step's losses and a sample of the parameters the optimizer has
     # updated W + K times by now (round 5 found replays of the round-4 graph turning NaN after a few steps: a memset node racing the
     # bias-gradient kernel -- the timing was unaffected, the training was not)
-    last = tr._static_out[1] if use_graph else tr.train_step(batch)[1]
-    finite = bool(all(torch.isfinite(v.float()).all() for v in last.values())) and \
+    finite = bool(all(torch.isfinite(v.float()).all() for v in out[1].values())) and \
         bool(all(torch.isfinite(p).all() for p in list(tr.model.parameters())[::7]))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, tr.model.parameters())
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -420,16 +501,16 @@ def main():
                     'rocprof_avg_us': rp_us, 'rocprof_frac': None if rp_us is None else round(flops / n / (rp_us * 1e-6) / 1e12 / PEAK_BF16_DENSE_TFLOPS, 4),
                     'rocprof_source': rp_src}
     extra = None
-    if rank == 0 and not args.dry:
+    if rank == 0 and measure_more:
         try:
             extra = geometry_rooflines(tr, B, args.size, dev)
         except Exception as e:                                       # secondary figures must not take the bench line down
             extra = [{'error': repr(e)}]
 
     fp32 = None
-    if not args.no_fp32 and world == 1:                             # (N > 1: one configuration per run; `--dtype fp32` measures C4 on N GPUs)
+    if measure_more and not args.no_fp32 and world == 1:            # (N > 1: one configuration per run; `--dtype fp32` measures C4 on N GPUs)
         try:                                                         # (after everything measured on the bf16 graph: this re-captures)
-            fp32 = fp32_record(args, tr, batch, world, dev)
+            fp32 = fp32_record(args, tr, batch, world, dev)[0]
         except Exception as e:
             fp32 = {'error': repr(e)}
     allreduce_info = None
@@ -468,7 +549,7 @@ def main():
                 'roofline_extra': extra}
         if fp32 is not None:
             line['fp32'] = fp32
-        if world == 1 and not args.no_cpu_baseline:
+        if measure_more and world == 1 and not args.no_cpu_baseline:
             try:
                 line['cpu_baseline'] = cpu_baseline(args.size, args.cpu_batch)
             except Exception as e:                                   # the bench line must still be printed

@@ -390,6 +390,33 @@ def test_bench_dry_launch_line_on_a_one_rank_group():
     assert ar['comm_channels_reserved'] >= 1 and ar['onepass_max_blocks'] == 2 * (256 - ar['comm_channels_reserved']), ar
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): exactly --steps timed replays, the headline fields, none of the --full legs, and
+    --dump-outputs writing the last step's losses, outputs and parameter sample as finite float .npy files within 64 MB."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, RANK='0', WORLD_SIZE='1', LOCAL_RANK='0')
+    dump = str(tmp_path / 'dump')
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4',
+                        '--dump-outputs', dump], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['exec'] == 'hipgraph' and line['dtype'] == 'bf16', line
+    assert line['unit'] == 'images/sec' and line['higher_is_better'] is True and line['value'] > 0 and line['ms_per_step'] > 0
+    assert abs(line['value'] - 4 * 1e3 / line['ms_per_step']) <= 0.01 * line['value']
+    assert line['finite_losses_and_parameters'] and not line['onepass_error']
+    assert line['roofline'] is None and line['roofline_extra'] is None and 'fp32' not in line and 'cpu_baseline' not in line
+    files = sorted(os.listdir(dump))
+    assert 'params.npy' in files and any(f.startswith('losses.') for f in files) and any(f.startswith('out.') for f in files), files
+    total = 0
+    for f in files:
+        a = np.load(os.path.join(dump, f))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+        total += os.path.getsize(os.path.join(dump, f))
+    assert total <= 64 << 20
+
+
 def _two_proc_worker(rank, world, port, tmp):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch.distributed as dist

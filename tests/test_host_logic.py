@@ -408,3 +408,36 @@ def test_bench_cpu_baseline_leg_runs_on_host_cores():
     assert out['kind'] == 'port' and out['unit'] == 'images/sec' and out['value'] > 0 and out['cores'] >= 1 and 'sample' in out
     assert 'StepNets' in out['sample'] and '99.9' in out['sample']
     assert bench.pmc_traffic('no_such_kernel')[0] is None
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """bench.py --dump-outputs: every tensor the step returned (a tensor reached twice written once) and the parameters as
+    float32 / float64 .npy files; an array above its share of the budget becomes a sorted sample of its elements, at the
+    same positions on every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.DUMP_BUDGET_BYTES = 6 * 8 * 1000                       # 6 arrays below: 1000 elements each
+    losses = {'loss_a': torch.tensor(1.5), 'loss/b': torch.tensor(2.5, dtype=torch.float64)}
+    out = {'losses': losses, 'verts': torch.arange(5000, dtype=torch.float32).reshape(50, 100),
+           'iuv': [torch.ones(4, 8, dtype=torch.bfloat16), torch.arange(6, dtype=torch.int64)], 'flag': True}
+    params = [torch.nn.Parameter(torch.full((30, 40), 0.25)), torch.nn.Parameter(torch.zeros(7))]
+    written = bench.dump_outputs(str(tmp_path / 'a'), (out, losses), params)
+    assert set(written) == {'losses.loss_a', 'losses.loss_b', 'out.verts', 'out.iuv.0', 'out.iuv.1', 'params'}
+    arrays = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in written}
+    assert set(os.listdir(str(tmp_path / 'a'))) == {n + '.npy' for n in written}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= bench.DUMP_BUDGET_BYTES
+    assert arrays['losses.loss_a'].dtype == np.float32 and float(arrays['losses.loss_a']) == 1.5
+    assert arrays['losses.loss_b'].dtype == np.float64 and float(arrays['losses.loss_b']) == 2.5
+    assert arrays['out.iuv.0'].dtype == np.float32 and arrays['out.iuv.0'].shape == (4, 8)
+    np.testing.assert_array_equal(arrays['out.iuv.1'], np.arange(6, dtype=np.float64))
+    v = arrays['out.verts']                                      # sampled: values == positions of arange
+    assert written['out.verts'] == ((50, 100), 1000) and v.shape == (1000,)
+    assert (np.diff(v) > 0).all() and v[0] >= 0 and v[-1] < 5000
+    assert written['params'] == ((1207,), 1000) and set(np.unique(arrays['params'])) <= {0.0, 0.25}
+    again = bench.dump_outputs(str(tmp_path / 'b'), (out, losses), params)
+    assert again == written
+    for n in written:
+        np.testing.assert_array_equal(np.load(str(tmp_path / 'b' / (n + '.npy'))), arrays[n])

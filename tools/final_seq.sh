@@ -7,10 +7,11 @@ set -u
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 R=r06
-echo "== bench (default flags, fresh box)"
-timeout 600 python bench.py > gpurun_out/${R}_final_bench.log 2>&1; grep "^{" gpurun_out/${R}_final_bench.log | tail -1 > gpurun_out/${R}_plain_line.json; cut -c1-300 gpurun_out/${R}_plain_line.json
+echo "== bench --full (fresh box)"
+OUT=${BENCH_OUT:-bench_out}; mkdir -p $OUT
+timeout 600 python bench.py --full > $OUT/${R}_final_bench.log 2>&1; grep "^{" $OUT/${R}_final_bench.log | tail -1 > $OUT/${R}_full_line.json; cut -c1-300 $OUT/${R}_full_line.json
 echo "== rocprofv3 of the same command"
-bash tools/prof_bench.sh ${R}_bench | tail -2 | cut -c1-200
+bash tools/prof_bench.sh ${R}_bench --full | tail -2 | cut -c1-200
 echo "== rocprofv3, bf16 steps only"
 bash tools/prof_bench.sh ${R}_bf16only --no-fp32 --no-cpu-baseline | tail -1 | cut -c1-100
 python tools/step_breakdown.py gpurun_out/${R}_bf16only_kernel_stats.csv > gpurun_out/${R}_step_breakdown.txt; cat gpurun_out/${R}_step_breakdown.txt
