@@ -59,6 +59,11 @@ _SIGNATURES = {
     'danet_conv_forward_multi_ok': (c_i, [c_f, c_i]),
     'danet_conv_forward_multi_kernel': (c_i, [c_f, c_i]),
     'danet_conv_forward_multi': (c_i, [c_f, c_i, c_f]),
+    'danet_conv_forward_multi_epi_ok': (c_i, [c_f, c_i]),
+    'danet_conv_forward_multi_epi_kernel': (c_i, [c_f, c_i]),
+    'danet_conv_forward_multi_epi': (c_i, [c_f, c_i, c_f]),
+    'danet_conv_stem_forward_epi': (c_i, [c_f, c_f, c_f, c_f] + [c_i] * 8 + [c_f]),
+    'danet_conv3x3a_forward_epi': (c_i, [c_f] * 5 + [c_i] * 4 + [c_f]),
     'danet_conv_bn_forward_multi_ok': (c_i, [c_f, c_i, c_f, c_f]),
     'danet_conv_bn_forward_multi': (c_i, [c_f, c_i, c_f, c_fl, c_fl, c_f, c_f, c_f]),
     'danet_conv_forward_kernel': (c_i, [c_i] * 15),
@@ -195,6 +200,11 @@ class ConvJob(ctypes.Structure):
     """One problem of danet_conv_forward_multi (include/danet_hip.h)."""
     _fields_ = [(k, ctypes.c_void_p) for k in ('x', 'wp', 'y', 'bn_sums', 'bn_x', 'bn_y', 'bn_saved', 'bn_red', 'addend')] + \
                [(k, c_i) for k in ('B', 'H', 'W', 'Cin', 'OH', 'OW', 'Cout', 'R', 'S', 'stride', 'pad', 'dil', 'groups', 'transposed', 'bn_gate')]
+
+
+class ConvJobEpi(ctypes.Structure):
+    """One problem of danet_conv_forward_multi_epi: a ConvJob plus the folded BatchNorm's bias and a ReLU flag (include/danet_hip.h)."""
+    _fields_ = [('j', ConvJob), ('bias', ctypes.c_void_p), ('relu', c_i)]
 
 
 def exported_symbols():

@@ -48,6 +48,7 @@ struct C3aP {
     int B, H, W, mirrored;
     int ntiles, strips;                                      // tiles per image = H / TH
     int bytes;                                               // of x (= of y: same shape)
+    const float* bias; int relu;                             // conv3x3a_bias_kernel only: y = [relu](acc + bias[c] [+ addend])
 };
 
 __device__ __forceinline__ void dma16(unsigned lds_addr, int voff, const i32x4& desc, int soff) {
@@ -73,8 +74,10 @@ __device__ inline float row_sum16(float v) {
     return v;
 }
 
-template <int TW>
-__global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p)
+// EPI = false: the training forward / data gradient; EPI = true: the folded-inference forward (bias, optional residual addend, optional
+// ReLU; no statistics).  Two kernels over one body, so conv3x3a_kernel itself compiles as before.
+template <int TW, bool EPI>
+__device__ __forceinline__ void conv3x3a_body(const C3aP& p)
 {
     using G_ = Geo<TW>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -256,6 +259,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p)
             for (int np = 0; np < CA_NT; np += 2) {
                 f32x4 va = acc[mt][np], vb = acc[mt][np + 1];
                 asm volatile("" : "+v"(va), "+v"(vb));
+                if constexpr (EPI) {
+                    va += *reinterpret_cast<const f32x4*>(p.bias + np * 16 + lg * 4);
+                    vb += *reinterpret_cast<const f32x4*>(p.bias + (np + 1) * 16 + lg * 4);
+                }
                 if (p.addend) {                             // before the exchange a lane holds channels nt * 16 + lg * 4 .. + 3 of pixel li
                     const i32x2 qa = __builtin_amdgcn_raw_buffer_load_b64(adr, (pix * 64 + np * 16 + lg * 4) * 2, 0, 0);
                     const i32x2 qb = __builtin_amdgcn_raw_buffer_load_b64(adr, (pix * 64 + (np + 1) * 16 + lg * 4) * 2, 0, 0);
@@ -264,8 +271,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p)
                     vb[0] += __uint_as_float((unsigned)qb.x << 16); vb[1] += __uint_as_float((unsigned)qb.x & 0xffff0000u);
                     vb[2] += __uint_as_float((unsigned)qb.y << 16); vb[3] += __uint_as_float((unsigned)qb.y & 0xffff0000u);
                 }
+                if constexpr (EPI) {
+                    if (p.relu) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { va[r] = fmaxf(va[r], 0.f); vb[r] = fmaxf(vb[r], 0.f); }
+                    }
+                }
                 const i32x2 pa = {(int)f2bf_pk(va[0], va[1]), (int)f2bf_pk(va[2], va[3])}, pb = {(int)f2bf_pk(vb[0], vb[1]), (int)f2bf_pk(vb[2], vb[3])};
-                if (p.stats) {
+                if (!EPI && p.stats) {
                     auto stat = [&](int nt, const i32x2& pk) {
                         f32x2_ lo = {__uint_as_float((unsigned)pk.x << 16), __uint_as_float((unsigned)pk.x & 0xffff0000u)};
                         f32x2_ hi = {__uint_as_float((unsigned)pk.y << 16), __uint_as_float((unsigned)pk.y & 0xffff0000u)};
@@ -282,7 +295,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p)
                 const int c8 = (np + (lg & 1)) * 16 + (lg >> 1) * 8;               // the lane's eight channels after the exchange (conv_pw.hip)
                 const int off = (pix * 64 + c8) * 2;
                 __builtin_amdgcn_raw_buffer_store_b128(q, yr, off, 0, 0);
-                if (p.bn_red) {
+                if (!EPI && p.bn_red) {
                     const i32x4 xq = __builtin_amdgcn_raw_buffer_load_b128(bxr, off, 0, 0);
                     i32x4 yq = {0x3f803f80, 0x3f803f80, 0x3f803f80, 0x3f803f80};           // "positive" when there is no ReLU
                     if (p.bn_y) {
@@ -315,7 +328,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p)
                 }
             }
         }
-        if (p.stats) {                                      // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS
+        if (!EPI && p.stats) {                              // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS
 #pragma unroll
             for (int nt = 0; nt < CA_NT; ++nt)
 #pragma unroll
@@ -336,7 +349,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p)
     for (int d = 0; d < CA_D; ++d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[d][0]), "+v"(A[d][1]), "+v"(A[d][2]), "+v"(A[d][3]));
     };
     if (kw == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
-    if (p.bn_red) {
+    if (!EPI && p.bn_red) {
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -347,7 +360,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p)
             }
     }
     float* const dst = p.bn_red ? p.bn_red : p.stats;
-    if (dst) {
+    if (!EPI && dst) {
         __syncthreads();
         if (t < 128) {
             const int which = t >> 6, c = t & 63;
@@ -356,20 +369,27 @@ __global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p)
     }
 }
 
+template <int TW>
+__global__ __launch_bounds__(256, 1) void conv3x3a_kernel(C3aP p) { conv3x3a_body<TW, false>(p); }
+template <int TW>
+__global__ __launch_bounds__(256, 1) void conv3x3a_bias_kernel(C3aP p) { conv3x3a_body<TW, true>(p); }
+
 bool g_c3a_on = getenv("DANET_NO_CONV3X3A") == nullptr;
 
-template <int TW>
+template <int TW, bool EPI>
 int c3a_launch(const C3aP& p, hipStream_t st) {
     static bool attr_set = false;
     static int cus = 0;
+    const void* const fn = EPI ? reinterpret_cast<const void*>(&conv3x3a_bias_kernel<TW>) : reinterpret_cast<const void*>(&conv3x3a_kernel<TW>);
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3a_kernel<TW>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<TW>::LDS);
+        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<TW>::LDS);
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         attr_set = true;
     }
     const int grid = p.ntiles < cus ? p.ntiles : cus;
-    hipLaunchKernelGGL(conv3x3a_kernel<TW>, dim3((unsigned)grid), dim3(256), (size_t)Geo<TW>::LDS, st, p);
+    if (EPI) hipLaunchKernelGGL(conv3x3a_bias_kernel<TW>, dim3((unsigned)grid), dim3(256), (size_t)Geo<TW>::LDS, st, p);
+    else hipLaunchKernelGGL(conv3x3a_kernel<TW>, dim3((unsigned)grid), dim3(256), (size_t)Geo<TW>::LDS, st, p);
     return 0;
 }
 
@@ -405,9 +425,29 @@ extern "C" int danet_conv3x3a(const void* x, const void* wp, void* y, int B, int
     p.addend = (const bf16_t*)addend;
     p.B = B; p.H = H; p.W = W; p.mirrored = transposed ? 1 : 0;
     p.bytes = (int)((long)B * H * W * 128);
-    if (W == 16) { p.strips = H / 16; p.ntiles = B * p.strips; c3a_launch<16>(p, (hipStream_t)stream); }
-    else { p.strips = H / 4; p.ntiles = B * p.strips; c3a_launch<64>(p, (hipStream_t)stream); }
+    if (W == 16) { p.strips = H / 16; p.ntiles = B * p.strips; c3a_launch<16, false>(p, (hipStream_t)stream); }
+    else { p.strips = H / 4; p.ntiles = B * p.strips; c3a_launch<64, false>(p, (hipStream_t)stream); }
     DANET_CHECK_LAUNCH("conv3x3a_kernel");
+    return DANET_OK;
+}
+
+// The folded-inference forward: y = bf16([relu](conv(x, wp) + bias[c] [+ addend])), wp = the mode-0 / chunk-16 packing, bias fp32 [64],
+// addend (optional) bf16 [B,H,W,64] like y -- a BasicBlock's conv -> eval BatchNorm [-> + identity] -> ReLU (inference.py).  No statistics.
+extern "C" int danet_conv3x3a_forward_epi(const void* x, const void* wp, const float* bias, const void* addend, void* y, int B, int H, int W,
+                                          int relu, void* stream)
+{
+    DANET_ENTER();
+    DANET_CHECK_ARG(x && wp && bias && y, "conv3x3a_forward_epi: null pointer");
+    DANET_CHECK_ARG(danet_conv3x3a_ok(B, H, W, 64, 64, 3, 3, 1, 1, 1, 1), "conv3x3a_forward_epi: unsupported problem (see danet_conv3x3a_ok)");
+    DANET_CHECK_ARG(((uintptr_t)bias & 15) == 0, "conv3x3a_forward_epi: bias must be 16-byte aligned");
+    C3aP p{};
+    p.x = (const bf16_t*)x; p.w = (const bf16_t*)wp; p.y = y;
+    p.addend = (const bf16_t*)addend; p.bias = bias; p.relu = relu ? 1 : 0;
+    p.B = B; p.H = H; p.W = W; p.mirrored = 0;
+    p.bytes = (int)((long)B * H * W * 128);
+    if (W == 16) { p.strips = H / 16; p.ntiles = B * p.strips; c3a_launch<16, true>(p, (hipStream_t)stream); }
+    else { p.strips = H / 4; p.ntiles = B * p.strips; c3a_launch<64, true>(p, (hipStream_t)stream); }
+    DANET_CHECK_LAUNCH("conv3x3a_bias_kernel");
     return DANET_OK;
 }
 

@@ -729,34 +729,44 @@ extern "C" int danet_conv_forward(const void* x, const void* wp, const float* bi
 struct ConvJob { const void* x; const void* wp; void* y; float* bn_sums; const void* bn_x; const void* bn_y; const float* bn_saved; float* bn_red; const void* addend;
                  int B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups, transposed, bn_gate; };
 
-// *all3 = every problem runs on the LDS-tile 3x3 kernel (then nt / mts are not needed)
-static int conv_multi_prepare(const ConvJob* jobs, int n, ConvP* ps, int* mts, int* nt_out, bool* all3) {
+// danet_conv_forward_multi_epi's job: a ConvJob plus the epilogue of a folded (eval-mode) BatchNorm: y = bf16([relu](acc + bias[c] [+ addend])).
+struct ConvJobEpi { ConvJob j; const float* bias; int relu; };
+
+// *all3 = every problem runs on the LDS-tile 3x3 kernel (then nt / mts are not needed).  epi (optional, n entries): per-problem bias / ReLU
+// (forward problems without fused statistics; the gather kernel then takes a residual addend as well).
+static int conv_multi_prepare(const ConvJob* jobs, int n, ConvP* ps, int* mts, int* nt_out, bool* all3, const ConvJobEpi* epi = nullptr) {
     if (!jobs || n < 1 || n > 12) return -1;
+    if (epi)
+        for (int i = 0; i < n; ++i)
+            if (jobs[i].transposed || jobs[i].bn_sums || jobs[i].bn_red || jobs[i].bn_gate) return -1;
     int nt = -1;
     *all3 = n <= 4;                         // (the LDS-tile 3x3 kernel takes up to 4 problems, the gather kernel up to 12)
     for (int i = 0; i < n && *all3; ++i) {
         const ConvJob& j = jobs[i];
         bool vec8;
         ps[i] = ConvP{};
-        if (!fill_conv_params(ps[i], vec8, j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups, j.transposed, 0, 0)) return -1;
+        if (!fill_conv_params(ps[i], vec8, j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups, j.transposed,
+                              epi ? epi[i].relu : 0, 0)) return -1;
         if (!conv3x3_ok(ps[i], vec8)) { *all3 = false; break; }
-        ps[i].x = (const bf16_t*)j.x; ps[i].w = (const bf16_t*)j.wp; ps[i].bias = nullptr; ps[i].y = j.y; ps[i].stats = j.bn_sums;
+        ps[i].x = (const bf16_t*)j.x; ps[i].w = (const bf16_t*)j.wp; ps[i].bias = epi ? epi[i].bias : nullptr; ps[i].y = j.y; ps[i].stats = j.bn_sums;
         ps[i].bn_x = (const bf16_t*)j.bn_x; ps[i].bn_y = (const bf16_t*)j.bn_y; ps[i].bn_saved = j.bn_saved; ps[i].bn_red = j.bn_red;
         ps[i].addend = (const bf16_t*)j.addend; ps[i].bn_gate = j.bn_gate;
     }
     if (*all3 && conv3x3_launch(ps, n, nullptr, true) != 0) *all3 = false;      // e.g. a tiling the multi-problem kernel lacks
     if (*all3) { *nt_out = 0; return 0; }
-    for (int i = 0; i < n; ++i) if (jobs[i].addend || jobs[i].bn_gate) return -1;      // the gather kernel has no fused addend / mask gate
+    // the gather kernel has no mask gate, and its addend is only taken without fused statistics / reductions (danet_conv_forward's rule)
+    for (int i = 0; i < n; ++i) if ((jobs[i].addend && !epi) || jobs[i].bn_gate) return -1;
     for (int i = 0; i < n; ++i) {
         const ConvJob& j = jobs[i];
         bool vec8;
         ps[i] = ConvP{};
-        if (!fill_conv_params(ps[i], vec8, j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups, j.transposed, 0, 0)) return -1;
+        if (!fill_conv_params(ps[i], vec8, j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups, j.transposed,
+                              epi ? epi[i].relu : 0, 0)) return -1;
         const int nti = danet_conv_nt(ps[i].Cout_g);
         if (nt < 0) nt = nti; else if (nt != nti) return -1;
         mts[i] = danet_conv_kernel_id(j.B, j.OH, j.OW, j.Cin, j.Cout, j.groups) / 100;
         if (!conv_fast_ok(ps[i], vec8, mts[i])) return -1;
-        ps[i].x = (const bf16_t*)j.x; ps[i].w = (const bf16_t*)j.wp; ps[i].bias = nullptr; ps[i].y = j.y; ps[i].stats = j.bn_sums;
+        ps[i].x = (const bf16_t*)j.x; ps[i].w = (const bf16_t*)j.wp; ps[i].bias = epi ? epi[i].bias : nullptr; ps[i].y = j.y; ps[i].stats = j.bn_sums;
         ps[i].bn_x = (const bf16_t*)j.bn_x; ps[i].bn_y = (const bf16_t*)j.bn_y; ps[i].bn_saved = j.bn_saved; ps[i].bn_red = j.bn_red;
         ps[i].addend = (const bf16_t*)j.addend;
     }
@@ -847,6 +857,50 @@ extern "C" int danet_conv_forward_multi(const void* jobs, int n, void* stream)
         return DANET_OK;
     }
     DANET_CHECK_ARG(conv_fast_launch_multi(ps, mts, n, nt, stream) == 0, "conv_forward_multi: no kernel for %d tiles per block", nt);
+    DANET_CHECK_LAUNCH("conv_fast_multi_kernel");
+    return DANET_OK;
+}
+
+
+// ---- the same sets with a per-problem epilogue (folded eval-mode BatchNorms: inference.py) -----------------------------------------
+// jobs: n ConvJobEpi; forward problems only, no fused statistics / reductions.  Kernel choice as danet_conv_forward_multi: the streamed
+// 3x3 kernel (its general epilogue), the LDS-tile 3x3 kernel, or conv_fast_multi_kernel -- all three read bias / relu / addend from the
+// problem.  y = bf16([relu](acc + bias[c] [+ addend])), rounded once.
+static int conv_multi_prepare_epi(const void* jobs, int n, ConvP* ps, int* mts, int* nt, bool* all3) {
+    if (!jobs || n < 1 || n > 12) return -1;
+    ConvJob js[12];
+    const ConvJobEpi* e = (const ConvJobEpi*)jobs;
+    for (int i = 0; i < n; ++i) js[i] = e[i].j;
+    return conv_multi_prepare(js, n, ps, mts, nt, all3, e);
+}
+
+extern "C" int danet_conv_forward_multi_epi_ok(const void* jobs, int n)
+{
+    ConvP ps[12]; int mts[12], nt; bool all3;
+    if (conv_multi_prepare_epi(jobs, n, ps, mts, &nt, &all3) != 0) return 0;
+    return all3 ? 2 : 1;
+}
+
+extern "C" int danet_conv_forward_multi_epi_kernel(const void* jobs, int n)
+{
+    ConvP ps[12]; int mts[12], nt; bool all3;
+    if (conv_multi_prepare_epi(jobs, n, ps, mts, &nt, &all3) != 0) return 0;
+    if (!all3) return 1;
+    return conv3x3s_launch(ps, n, nullptr, true) == 0 && conv3x3_stream_first() ? 3 : 2;
+}
+
+extern "C" int danet_conv_forward_multi_epi(const void* jobs, int n, void* stream)
+{
+    DANET_ENTER();
+    ConvP ps[12]; int mts[12], nt; bool all3;
+    DANET_CHECK_ARG(conv_multi_prepare_epi(jobs, n, ps, mts, &nt, &all3) == 0, "conv_forward_multi_epi: unsupported set (see danet_conv_forward_multi_epi_ok)");
+    for (int i = 0; i < n; ++i) DANET_CHECK_ARG(ps[i].x && ps[i].w && ps[i].y, "conv_forward_multi_epi: job %d: null pointer", i);
+    if (all3) {
+        DANET_CHECK_ARG(conv3x3_launch(ps, n, stream) == 0, "conv_forward_multi_epi: no 3x3 tiling");
+        DANET_CHECK_LAUNCH("conv3x3_tile_kernel");
+        return DANET_OK;
+    }
+    DANET_CHECK_ARG(conv_fast_launch_multi(ps, mts, n, nt, stream) == 0, "conv_forward_multi_epi: no kernel for %d tiles per block", nt);
     DANET_CHECK_LAUNCH("conv_fast_multi_kernel");
     return DANET_OK;
 }

@@ -86,7 +86,10 @@ __device__ unsigned long long g_stem_diag[256 * 4 * 8];
 #define ST_CLK(v) ((void)0)
 #endif
 
-__global__ __launch_bounds__(256, 1) void conv_stem_kernel(StemP p)
+// EPI = false: the training forward (optional BatchNorm statistics); EPI = true: the folded-inference epilogue (bias, optional ReLU,
+// no statistics).  Two kernels over one body, so conv_stem_kernel itself compiles as before.
+template <bool EPI>
+__device__ __forceinline__ void conv_stem_body(StemP p, const float* bias, int relu)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int t = threadIdx.x, lane = t & 63;
@@ -319,8 +322,16 @@ __global__ __launch_bounds__(256, 1) void conv_stem_kernel(StemP p)
                 for (int np = 0; np < ST_NT; np += 2) {
                     f32x4 va = acc[mt][np], vb = acc[mt][np + 1];
                     asm volatile("" : "+v"(va), "+v"(vb));
+                    if constexpr (EPI) {                    // a lane holds channels nt * 16 + lg * 4 .. + 3 of pixel li (Cout = 64: in range)
+                        va += *reinterpret_cast<const f32x4*>(bias + np * 16 + lg * 4);
+                        vb += *reinterpret_cast<const f32x4*>(bias + (np + 1) * 16 + lg * 4);
+                        if (relu) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) { va[r] = fmaxf(va[r], 0.f); vb[r] = fmaxf(vb[r], 0.f); }
+                        }
+                    }
                     const i32x2 pa = {(int)f2bf_pk(va[0], va[1]), (int)f2bf_pk(va[2], va[3])}, pb = {(int)f2bf_pk(vb[0], vb[1]), (int)f2bf_pk(vb[2], vb[3])};
-                    if (p.stats) {
+                    if (!EPI && p.stats) {
                         auto stat = [&](int nt, const i32x2& pk) {
                             f32x2_ lo = {__uint_as_float((unsigned)pk.x << 16), __uint_as_float((unsigned)pk.x & 0xffff0000u)};
                             f32x2_ hi = {__uint_as_float((unsigned)pk.y << 16), __uint_as_float((unsigned)pk.y & 0xffff0000u)};
@@ -340,7 +351,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_kernel(StemP p)
             };
             body(KW * 4 + m);
         }
-        if (p.stats) {                                      // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS
+        if (!EPI && p.stats) {                              // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS
 #pragma unroll
             for (int nt = 0; nt < ST_NT; ++nt)
 #pragma unroll
@@ -362,7 +373,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_kernel(StemP p)
 #endif
     };
     if (kw == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
-    if (p.stats) {
+    if (!EPI && p.stats) {
         __syncthreads();
         if (t < 128) {
             const int which = t >> 6, c = t & 63;
@@ -370,6 +381,10 @@ __global__ __launch_bounds__(256, 1) void conv_stem_kernel(StemP p)
         }
     }
 }
+
+__global__ __launch_bounds__(256, 1) void conv_stem_kernel(StemP p) { conv_stem_body<false>(p, nullptr, 0); }
+// y = [relu](acc + bias[c]): the folded-inference epilogue (bias / relu as arguments of their own: StemP, and with it conv_stem_kernel, stay as they were)
+__global__ __launch_bounds__(256, 1) void conv_stem_bias_kernel(StemP p, const float* bias, int relu) { conv_stem_body<true>(p, bias, relu); }
 
 bool g_stem_on = getenv("DANET_NO_CONV_STEM") == nullptr;
 
@@ -412,6 +427,34 @@ extern "C" int danet_conv_stem_forward(const void* x, const void* wp, void* y, i
     const int grid = p.ntiles < cus ? p.ntiles : cus;
     hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)grid), dim3(256), (size_t)ST_LDS, (hipStream_t)stream, p);
     DANET_CHECK_LAUNCH("conv_stem_kernel");
+    return DANET_OK;
+}
+
+// The folded-inference form of danet_conv_stem_forward: y = bf16([relu](conv(x, wp) + bias[c])), bias fp32 [Cout], no statistics
+// (a BatchNorm in eval mode folded into the weights and the bias: inference.py fold_conv_bn).
+extern "C" int danet_conv_stem_forward_epi(const void* x, const void* wp, const float* bias, void* y, int B, int H, int W, int Cin, int OH, int OW,
+                                           int Cout, int relu, void* stream)
+{
+    DANET_ENTER();
+    DANET_CHECK_ARG(x && wp && bias && y, "conv_stem_forward_epi: null pointer");
+    DANET_CHECK_ARG(danet_conv_stem_ok(B, H, W, Cin, OH, OW, Cout, ST_R, ST_R, 2, 3, 1, 1), "conv_stem_forward_epi: unsupported problem (see danet_conv_stem_ok)");
+    DANET_CHECK_ARG(((uintptr_t)bias & 15) == 0, "conv_stem_forward_epi: bias must be 16-byte aligned");
+    StemP p{};
+    p.x = (const bf16_t*)x; p.w = (const bf16_t*)wp; p.y = y; p.stats = nullptr;
+    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.OH = OH;
+    p.nslab = Cin / 16; p.strips = OH / ST_TH; p.ntiles = B * p.strips;
+    p.x_bytes = (int)((long)B * H * W * Cin * 2); p.y_bytes = (int)((long)B * OH * OW * Cout * 2);
+    static bool attr_set = false;
+    static int cus = 0;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_stem_bias_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        attr_set = true;
+    }
+    const int grid = p.ntiles < cus ? p.ntiles : cus;
+    hipLaunchKernelGGL(conv_stem_bias_kernel, dim3((unsigned)grid), dim3(256), (size_t)ST_LDS, (hipStream_t)stream, p, bias, relu ? 1 : 0);
+    DANET_CHECK_LAUNCH("conv_stem_bias_kernel");
     return DANET_OK;
 }
 

@@ -61,6 +61,11 @@ class DaNet(nn.Module):
             rd['visualization'].update(out['visualization'])
             return rd
 
+    def inference_engine(self, batch_size, img_size=None, graph=True, mesh=False):
+        """A BatchNorm-folded, graph-captured infer_net for this (eval-mode, GPU) model: inference.InferenceEngine."""
+        from .inference import InferenceEngine
+        return InferenceEngine(self, batch_size, img_size=img_size, graph=graph, mesh=mesh)
+
     def forward(self, in_dict):
         with torch.set_grad_enabled(self.training):
             return self._forward(in_dict)

@@ -374,6 +374,15 @@ int danet_conv_bn_forward_multi_ok(const void* jobs, int n, const void* bn_jobs,
 int danet_conv_bn_forward_multi(const void* jobs, int n, const void* bn_jobs, float momentum, float eps, void* bar, int* fused, void* stream);
 int danet_conv_forward_multi_kernel(const void* jobs, int n);      /* the kernel the set runs on: 0 none, 1 conv_fast_multi_kernel, 2 conv3x3_tile_kernel,
                                                                        3 conv3x3_stream_kernel (csrc/conv3x3s.hip) */
+/* danet_conv_forward_multi with a per-problem epilogue, for convolutions whose eval-mode BatchNorm is folded into the weights and a
+ * bias (inference engine): job = { ConvJob j; const float* bias; int relu; } -- y = bf16([relu](acc + bias[c] [+ j.addend])), rounded
+ * once; bias fp32 [Cout] or NULL.  Forward problems only (transposed = 0) without bn_sums / bn_red / bn_gate.  The set runs where
+ * danet_conv_forward_multi would run it -- the streamed 3x3 kernel (its general epilogue), conv3x3_tile_kernel (<= 4 problems) or
+ * conv_fast_multi_kernel (<= 12, same danet_conv_nt) -- and all three read the epilogue per problem.  _ok: 0 no, 1 conv_fast_multi_kernel,
+ * 2 an LDS 3x3 kernel; _kernel: as danet_conv_forward_multi_kernel. */
+int danet_conv_forward_multi_epi_ok(const void* jobs, int n);
+int danet_conv_forward_multi_epi_kernel(const void* jobs, int n);
+int danet_conv_forward_multi_epi(const void* jobs, int n, void* stream);
 /* ---------------------------------------------------------------------------------------
  * The library's ONE run-time switch board, for A-B timing and tests (production code never calls it; the defaults come from
  * the environment variables the kernels' files name).  danet_knob(id, value): value < 0 only queries; returns the previous value
@@ -418,6 +427,10 @@ int danet_conv3x3_stream_tables(void* workspace, size_t bytes);
 int danet_conv_stem_ok(int B, int H, int W, int Cin, int OH, int OW, int Cout, int R, int S, int stride, int pad, int dil, int groups);
 int danet_conv_stem_forward(const void* x, const void* wp, void* y, int B, int H, int W, int Cin, int OH, int OW, int Cout,
                             float* bn_sums, void* stream);
+/* The stem with a folded eval-mode BatchNorm (inference engine): y = bf16([relu](conv(x, wp) + bias[c])), bias fp32 [64], 16-byte aligned;
+ * the problems danet_conv_stem_ok takes, no statistics (conv_stem_bias_kernel: the same body as conv_stem_kernel). */
+int danet_conv_stem_forward_epi(const void* x, const void* wp, const float* bias, void* y, int B, int H, int W, int Cin, int OH, int OW,
+                                int Cout, int relu, void* stream);
 /* Data gradient of a stem convolution with 64 input and 64 output channels (csrc/conv_stem_dgrad.hip): (B, H, W, Cin) describe dx (the
  * convolution's input), (OH, OW, Cout) dy; weights = danet_conv_pack_weights(mode 1, chunk 16).  bn_x / bn_y / bn_saved / bn_red: the fused
  * BatchNorm-backward sums of danet_conv_forward's arguments of the same names (all NULL: none).  Replaces danet_conv_forward(transposed = 1)
@@ -432,6 +445,11 @@ int danet_conv_stem_dgrad(const void* dy, const void* wp, void* dx, int B, int H
 int danet_conv3x3a_ok(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil, int groups);
 int danet_conv3x3a(const void* x, const void* wp, void* y, int B, int H, int W, int transposed, float* bn_sums,
                    const void* bn_x, const void* bn_y, const float* bn_saved, float* bn_red, int bn_gate, const void* addend, void* stream);
+/* Its forward with a folded eval-mode BatchNorm (inference engine; a BasicBlock's conv -> bn [-> + identity] -> relu): y = bf16([relu](
+ * conv(x, wp) + bias[c] [+ addend])), weights mode 0 / chunk 16, bias fp32 [64] 16-byte aligned, addend bf16 NHWC like y or NULL; the
+ * problems danet_conv3x3a_ok takes, no statistics (conv3x3a_bias_kernel<TW>: the same body as conv3x3a_kernel<TW>). */
+int danet_conv3x3a_forward_epi(const void* x, const void* wp, const float* bias, const void* addend, void* y, int B, int H, int W,
+                               int relu, void* stream);
 /* Profiling hook: device buffer of blocks*8 ints receiving each workgroup's phase timestamps (s_memtime; NULL = off). */
 void danet_conv3x3_debug(int* dev_buf);
 int danet_conv_forward_multi(const void* jobs, int n, void* stream);
