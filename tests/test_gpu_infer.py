@@ -1,5 +1,5 @@
 """The BatchNorm-folded, graph-captured inference engine (danet_densepose2smpl_amd/inference.py) on the device: its new conv epilogues
-against F.conv2d, parity with the reference (golden g17) and with DaNet.infer_net on both backbones, graph replay, refresh / stale, and
+against fp64 within a derived rounding bound (tests/conv_bound.py), parity with the reference (golden g17) and with DaNet.infer_net on both backbones, graph replay, refresh / stale, and
 that it leaves the model alone.  Measured errors go to record(); the tolerances are set from those measurements."""
 import os
 import sys
@@ -8,11 +8,11 @@ import ctypes
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import golden, GOLDEN, record
 sys.path.insert(0, GOLDEN)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from conv_bound import U_BF16, reference, bound, check    # noqa: E402
 from make_golden import formula_input    # noqa: E402
 from test_gpu_f2 import _reference_layout_checkpoint, GRAPH_BUFFERS    # noqa: E402
 
@@ -25,7 +25,7 @@ def _cfg(**kw):
     cfg_from_dict(kw)
 
 
-# ---- the new epilogues, against F.conv2d in fp32 on the bf16-rounded operands ------------------------------------------------------
+# ---- the new epilogues, against fp64 on the bf16-rounded operands (tests/conv_bound.py) -----------------------------------------
 
 def _operands(B, Cin, Cout, H, W, k, seed):
     g = torch.Generator().manual_seed(seed)
@@ -35,58 +35,98 @@ def _operands(B, Cin, Cout, H, W, k, seed):
     return x, w, b
 
 
-def _close(y, ref, tol, what):
-    err = (y.float() - ref).abs().max().item() / ref.abs().max().item()
-    assert err <= tol, (what, err)
-    return err
+def _check(y, x, w, b, res, relu, stride, pad, what, idx=None):
+    """y (at batch items idx) against the fp64 [relu](conv(x, bf16(w)) + b [+ res]) on the operands the kernel consumed, within
+    tests/conv_bound.py's rounding bound and per-channel mean check -- a bound that is itself checked to be below the 1e-2 of max|ref|
+    these tests used to allow."""
+    if idx is not None:
+        y, x, res = y[idx], x[idx], None if res is None else res[idx]
+    ref = reference(x, w.bfloat16(), b, res, relu, stride, pad)
+    scale = ref.r.abs().max().item()
+    assert bound(ref, U_BF16)[0].max().item() < 1e-2 * scale, what
+    elem, mean = check(y, ref, U_BF16, what)
+    return {'elem': elem, 'chan_mean': mean, 'rel': (y.double() - ref.r).abs().max().item() / scale}
+
+
+def _stem_case(B, Cin, relu, bias_shift, seed):
+    from danet_densepose2smpl_amd import conv as dconv, _lib
+    L = _lib.lib()
+    assert L.danet_conv_stem_ok(B, 64, 64, Cin, 32, 32, 64, 7, 7, 2, 3, 1, 1) == 1
+    x, w, b = _operands(B, Cin, 64, 64, 64, 7, seed)
+    b = b + bias_shift
+    wp = dconv.pack_weight(w, 1, 0, 16)
+    y = dconv._empty_nhwc(B, 64, 32, 32, torch.bfloat16, x.device)
+    dconv.check(L.danet_conv_stem_forward_epi(dconv.ptr(x.permute(0, 2, 3, 1)), dconv.ptr(wp), dconv.ptr(b), dconv.ptr(y.permute(0, 2, 3, 1)),
+                                              B, 64, 64, Cin, 32, 32, 64, int(relu), dconv.stream()), 'stem epi')
+    idx = torch.linspace(0, B - 1, min(B, 48)).long().cuda()
+    m = _check(y, x, w, b, None, relu, 2, 3, ('stem', B, Cin, relu), idx)
+    record('infer_stem_epilogue', dict(m, B=B, Cin=Cin, relu=relu, bias_shift=bias_shift))
+    if relu:
+        assert (y >= 0).all()
+    if bias_shift:
+        assert (y < 0).float().mean().item() > 0.5
 
 
 @pytest.mark.parametrize('relu', [True, False])
 def test_stem_bias_relu_epilogue(relu):
     """conv_stem_bias_kernel at the regressor's limb stem: 768 crops, 64 -> 64 channels, 64 x 64, 7x7 / stride 2."""
+    _stem_case(768, 64, relu, 0., 1)
+
+
+@pytest.mark.parametrize('B,Cin', [(64, 64), (96, 32), (70, 16)])
+@pytest.mark.parametrize('relu,bias_shift', [(True, 0.), (False, 0.), (False, -1.5)])
+def test_stem_bias_epilogue_at_the_plain_kernel_shapes(B, Cin, relu, bias_shift):
+    """The same at the shapes the plain stem kernel is tested at (test_gpu_conv.py: odd tile counts per workgroup, 16- and 32-channel
+    slabs); bias_shift < 0: no ReLU and most outputs negative."""
+    _stem_case(B, Cin, relu, bias_shift, B + Cin)
+
+
+@pytest.mark.parametrize('B,Cin', [(768, 64)])
+def test_stem_bias_epilogue_negative_outputs(B, Cin):
+    """The regressor's limb stem without ReLU and with a bias that makes most outputs negative."""
+    _stem_case(B, Cin, False, -1.5, 1)
+
+
+def _c3a_case(B, H, W, with_res, relu, res_scale, seed):
     from danet_densepose2smpl_amd import conv as dconv, _lib
     L = _lib.lib()
-    B = 768
-    x, w, b = _operands(B, 64, 64, 64, 64, 7, 1)
+    assert L.danet_conv3x3a_ok(B, H, W, 64, 64, 3, 3, 1, 1, 1, 1) == 1
+    x, w, b = _operands(B, 64, 64, H, W, 3, seed)
+    res = (torch.randn(B, 64, H, W, generator=torch.Generator().manual_seed(3)) * res_scale).bfloat16().cuda() \
+        .contiguous(memory_format=torch.channels_last)
     wp = dconv.pack_weight(w, 1, 0, 16)
-    y = dconv._empty_nhwc(B, 64, 32, 32, torch.bfloat16, x.device)
-    dconv.check(L.danet_conv_stem_forward_epi(dconv.ptr(x.permute(0, 2, 3, 1)), dconv.ptr(wp), dconv.ptr(b), dconv.ptr(y.permute(0, 2, 3, 1)),
-                                              B, 64, 64, 64, 32, 32, 64, int(relu), dconv.stream()), 'stem epi')
-    idx = torch.linspace(0, B - 1, 48).long().cuda()
-    ref = F.conv2d(x[idx].float(), w.bfloat16().float(), b, 2, 3)
-    ref = F.relu(ref) if relu else ref
-    record('infer_stem_epilogue', {'relu': relu, 'rel': _close(y[idx], ref, 1e-2, 'stem')})
-    if relu:
-        assert (y >= 0).all()
+    y = dconv._empty_nhwc(B, 64, H, W, torch.bfloat16, x.device)
+    dconv.check(L.danet_conv3x3a_forward_epi(dconv.ptr(x.permute(0, 2, 3, 1)), dconv.ptr(wp), dconv.ptr(b),
+                                             dconv.ptr(res.permute(0, 2, 3, 1)) if with_res else None, dconv.ptr(y.permute(0, 2, 3, 1)),
+                                             B, H, W, int(relu), dconv.stream()), 'c3a epi')
+    idx = torch.linspace(0, B - 1, min(B, 64)).long().cuda()
+    m = _check(y, x, w, b, res if with_res else None, relu, 1, 1, ('conv3x3a', B, H, W, with_res, relu, res_scale), idx)
+    record('infer_c3a_epilogue', dict(m, B=B, H=H, W=W, res=with_res, relu=relu, res_scale=res_scale))
 
 
 @pytest.mark.parametrize('with_res', [False, True])
 def test_conv3x3a_bias_addend_relu_epilogue(with_res):
     """conv3x3a_bias_kernel at the regressor's layer1 BasicBlocks: 768 x 16 x 16, 64 -> 64 channels (conv1 -> bn1 -> relu and
     conv2 -> bn2 -> + identity -> relu)."""
-    from danet_densepose2smpl_amd import conv as dconv, _lib
-    L = _lib.lib()
-    B = 768
-    x, w, b = _operands(B, 64, 64, 16, 16, 3, 2)
-    res = torch.randn(B, 64, 16, 16, generator=torch.Generator().manual_seed(3)).bfloat16().cuda().contiguous(memory_format=torch.channels_last)
-    wp = dconv.pack_weight(w, 1, 0, 16)
-    y = dconv._empty_nhwc(B, 64, 16, 16, torch.bfloat16, x.device)
-    dconv.check(L.danet_conv3x3a_forward_epi(dconv.ptr(x.permute(0, 2, 3, 1)), dconv.ptr(wp), dconv.ptr(b),
-                                             dconv.ptr(res.permute(0, 2, 3, 1)) if with_res else None, dconv.ptr(y.permute(0, 2, 3, 1)),
-                                             B, 16, 16, 1, dconv.stream()), 'c3a epi')
-    idx = torch.linspace(0, B - 1, 64).long().cuda()
-    ref = F.conv2d(x[idx].float(), w.bfloat16().float(), b, 1, 1)
-    if with_res:
-        ref = ref + res[idx].float()
-    ref = F.relu(ref)
-    record('infer_c3a_epilogue', {'res': with_res, 'rel': _close(y[idx], ref, 1e-2, 'conv3x3a')})
+    _c3a_case(768, 16, 16, with_res, True, 1., 2)
+
+
+@pytest.mark.parametrize('B,H,W,with_res,relu,res_scale', [
+    shape + flags for shape in [(768, 16, 16), (32, 64, 64), (300, 16, 16), (20, 64, 64), (140, 32, 16)]
+    for flags in [(False, True, 1.), (True, True, 1.), (True, True, 8.), (True, False, 8.)]
+    if not (shape[0] == 768 and flags[2] == 1.)])          # (those two are test_conv3x3a_bias_addend_relu_epilogue)
+def test_conv3x3a_bias_epilogue_shapes_and_large_addend(B, H, W, with_res, relu, res_scale):
+    """The same at the shapes the plain kernel is tested at (test_gpu_conv.py: 16- and 64-wide maps, several strips per image);
+    res_scale = 8: an addend much larger than the convolution, so that adding it in the wrong place (after the ReLU, or rounded
+    separately) shows."""
+    _c3a_case(B, H, W, with_res, relu, res_scale, B + H)
 
 
 def _multi(specs, B, seed):
-    """specs: (Cin, Cout, H, k, stride, relu, with_res) -> the ConvJobEpi set, its outputs and the fp32 references."""
+    """specs: (Cin, Cout, H, k, stride, relu, with_res) -> the ConvJobEpi set, its outputs and each job's operands for _check."""
     from danet_densepose2smpl_amd import conv as dconv, _lib
     jobs = (_lib.ConvJobEpi * len(specs))()
-    keep, refs, ys = [], [], []
+    keep, ops, ys = [], [], []
     for i, (Cin, Cout, H, k, st, relu, with_res) in enumerate(specs):
         x, w, b = _operands(B, Cin, Cout, H, H, k, seed + i)
         OH = (H + 2 * (k // 2) - k) // st + 1
@@ -101,46 +141,74 @@ def _multi(specs, B, seed):
         (j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups, j.transposed, j.bn_gate) = \
             (B, H, H, Cin, OH, OH, Cout, k, k, st, k // 2, 1, 1, 0, 0)
         jobs[i].bias, jobs[i].relu = b.data_ptr(), int(relu)
-        ref = F.conv2d(x.float(), w.bfloat16().float(), b, st, k // 2)
-        if res is not None:
-            ref = ref + res.float()
-        refs.append(F.relu(ref) if relu else ref)
+        ops.append((x, w, b, res, relu, st, k // 2))
         ys.append(y)
         keep += [x, w, b, res, wp]
-    return jobs, ys, refs, keep
+    return jobs, ys, ops, keep
 
 
-@pytest.mark.parametrize('kind', ['hrnet_level_conv1', 'hrnet_level_conv2', 'fuse_stage'])
+_LEVEL = [(48, 48, 64, 3, 1), (96, 96, 32, 3, 1), (192, 192, 16, 3, 1), (384, 384, 8, 3, 1)]
+_POINTWISE = [(48, 48, 32, 1, 1), (96, 96, 16, 1, 1), (192, 192, 8, 1, 1), (48, 96, 32, 1, 1), (96, 48, 16, 1, 1)]
+_MULTI_SETS = {
+    # (B, specs, the kernel danet_conv_forward_multi_epi_kernel must pick: 3 streamed 3x3, 2 LDS-tile 3x3, 1 gather, None: either)
+    'hrnet_level_conv1': (32, [s + (True, False) for s in _LEVEL], 3),
+    'hrnet_level_conv2': (32, [s + (True, True) for s in _LEVEL], 3),
+    'fuse_stage': (32, [(48, 48, 64, 3, 2, True, False), (96, 96, 32, 3, 2, True, False), (48, 96, 64, 3, 2, False, False),
+                        (96, 192, 32, 3, 2, False, False)], None),
+    # mixed ReLU flags, addend and no-addend jobs in one launch: on the 3x3 kernels and on the gather kernel
+    'mixed_level': (32, [s + f for s, f in zip(_LEVEL, [(True, True), (False, False), (False, True), (True, False)])], None),
+    'mixed_pointwise': (32, [s + f for s, f in zip(_POINTWISE, [(True, True), (False, False), (True, False), (False, True), (True, True)])], 1),
+    # a demo batch size
+    'hrnet_level_conv2_b3': (3, [s + (True, True) for s in _LEVEL], None),
+    'mixed_pointwise_b3': (3, [s + f for s, f in zip(_POINTWISE, [(True, True), (False, False), (True, False), (False, True), (True, True)])], 1),
+}
+
+
+@pytest.mark.parametrize('kind', list(_MULTI_SETS))
 def test_multi_problem_epilogue_sets(kind):
     """danet_conv_forward_multi_epi on the sets the engine launches: a four-branch HRNet-W48 block level at B = 32, 256^2 (conv1 with
-    ReLU; conv2 with the identity addend and ReLU) and a fuse stage (strided 3x3 exchange paths, with and without ReLU)."""
+    ReLU; conv2 with the identity addend and ReLU) and a fuse stage (strided 3x3 exchange paths, with and without ReLU); sets that mix
+    ReLU flags and addend / no-addend jobs on the 3x3 and the gather kernels; the same at B = 3."""
     from danet_densepose2smpl_amd import conv as dconv, _lib
     L = _lib.lib()
-    B = 32
-    if kind.startswith('hrnet'):
-        res = kind.endswith('conv2')
-        specs = [(48, 48, 64, 3, 1, True, res), (96, 96, 32, 3, 1, True, res), (192, 192, 16, 3, 1, True, res), (384, 384, 8, 3, 1, True, res)]
-    else:
-        specs = [(48, 48, 64, 3, 2, True, False), (96, 96, 32, 3, 2, True, False), (48, 96, 64, 3, 2, False, False), (96, 192, 32, 3, 2, False, False)]
-    jobs, ys, refs, keep = _multi(specs, B, 10)
+    B, specs, kernel = _MULTI_SETS[kind]
+    jobs, ys, ops, keep = _multi(specs, B, 10)
     n = len(specs)
     ok = L.danet_conv_forward_multi_epi_ok(ctypes.addressof(jobs), n)
-    if kind.startswith('hrnet'):
+    if kind.startswith('hrnet') and B == 32:
         # the branch levels run on the streamed 3x3 kernel, in one launch
-        assert ok == 2 and L.danet_conv_forward_multi_epi_kernel(ctypes.addressof(jobs), n) == 3
-        sets = [list(range(n))]
-    else:
-        sets = [list(range(n))] if ok else [[0, 1], [2, 3]]
+        assert ok == 2
+    if kernel is not None:
+        assert L.danet_conv_forward_multi_epi_kernel(ctypes.addressof(jobs), n) == kernel
+    sets = [list(range(n))] if ok else [[0, 1], [2, 3]]
+    assert ok or kind == 'fuse_stage', kind
     for s in sets:
         arr = (_lib.ConvJobEpi * len(s))(*[jobs[k] for k in s])
         assert L.danet_conv_forward_multi_epi_ok(ctypes.addressof(arr), len(s))
         dconv.check(L.danet_conv_forward_multi_epi(ctypes.addressof(arr), len(s), dconv.stream()), 'multi epi')
-    errs = [_close(y, r, 1e-2, (kind, i)) for i, (y, r) in enumerate(zip(ys, refs))]
-    record('infer_multi_epilogue', {'kind': kind, 'rel': errs})
+    ms = [_check(y, *op, what=(kind, i)) for i, (y, op) in enumerate(zip(ys, ops))]
+    record('infer_multi_epilogue', {'kind': kind, 'B': B, 'elem': [m['elem'] for m in ms], 'chan_mean': [m['chan_mean'] for m in ms],
+                                    'rel': [m['rel'] for m in ms]})
     # a missing job list is refused, not dereferenced
     assert L.danet_conv_forward_multi_epi_ok(None, n) == 0
 
 
+def test_multi_problem_epilogue_refuses_an_unsupported_set():
+    """Five pointwise jobs (too many for the 3x3 kernels) whose channel-block counts differ (48 vs 64 output channels): no kernel
+    takes the set, the predicate says so and the launch is refused before anything runs."""
+    from danet_densepose2smpl_amd import conv as dconv, _lib
+    L = _lib.lib()
+    specs = [(48, 48, 32, 1, 1, True, False), (64, 64, 32, 1, 1, True, False), (48, 48, 16, 1, 1, False, True), (64, 64, 16, 1, 1, False, False),
+             (48, 48, 8, 1, 1, True, False)]
+    jobs, ys, ops, keep = _multi(specs, 4, 30)
+    assert L.danet_conv_nt(48) != L.danet_conv_nt(64)
+    assert L.danet_conv_forward_multi_epi_ok(ctypes.addressof(jobs), len(specs)) == 0
+    assert L.danet_conv_forward_multi_epi_kernel(ctypes.addressof(jobs), len(specs)) == 0
+    assert L.danet_conv_forward_multi_epi(ctypes.addressof(jobs), len(specs), dconv.stream()) != 0
+    # each equal-count subset is taken
+    for s in ([0, 2, 4], [1, 3]):
+        arr = (_lib.ConvJobEpi * len(s))(*[jobs[k] for k in s])
+        assert L.danet_conv_forward_multi_epi_ok(ctypes.addressof(arr), len(s)) == 1
 # ---- the engine against the reference (golden g17: reference inference at 128^2, B = 2) ------------------------------------------
 
 @pytest.fixture(scope='module')
