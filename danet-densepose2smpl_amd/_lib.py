@@ -136,6 +136,11 @@ _SIGNATURES = {
     'danet_gcn_tail_debug': (c_i, [c_f]),
     'danet_gcn_tail_forward': (c_i, [c_f, c_f]),
     'danet_gcn_tail_backward': (c_i, [c_f, c_f]),
+    'danet_lstm_tree_ok': (c_i, [c_i]),
+    'danet_lstm_tree_ws_floats': (c_sz, [c_i]),
+    'danet_lstm_tree_scratch_floats': (c_sz, [c_i]),
+    'danet_lstm_tree_forward': (c_i, [c_f, c_f]),
+    'danet_lstm_tree_backward': (c_i, [c_f, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations
@@ -194,6 +199,16 @@ class GcnTailArgs(ctypes.Structure):
                 ('gedge', ctypes.c_void_p),
                 ('gWp', ctypes.c_void_p * 2), ('gbp', ctypes.c_void_p * 2), ('gWc', ctypes.c_void_p * 2), ('gbc', ctypes.c_void_p * 2),
                 ('scratch', ctypes.c_void_p), ('bar', ctypes.c_void_p), ('B', c_i), ('momentum', ctypes.c_float), ('eps', ctypes.c_float)]
+
+
+_PTR5x2 = (ctypes.c_void_p * 2) * 5
+
+
+class LstmTreeArgs(ctypes.Structure):
+    """struct danet_lstm_tree_args (include/danet_hip.h)."""
+    _fields_ = [('pos', ctypes.c_void_p)] + [(k, _PTR5x2) for k in ('w_ih', 'w_hh', 'b_ih', 'b_hh')] + \
+               [(k, ctypes.c_void_p) for k in ('out', 'ws', 'g_out', 'scratch', 'g_pos')] + \
+               [(k, _PTR5x2) for k in ('g_w_ih', 'g_w_hh', 'g_b_ih', 'g_b_hh')] + [('B', c_i)]
 
 
 class ConvJob(ctypes.Structure):

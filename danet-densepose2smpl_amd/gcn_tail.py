@@ -35,6 +35,8 @@ def _layers(pred):
 
 def applicable(pred, rot_feats):
     from .config import cfg
+    if getattr(pred, 'refine_strategy', 'gcn') != 'gcn':
+        return False                                   # (only the 'gcn' strategy has this tail)
     if not (GCN_TAIL and rot_feats.is_cuda and pred.training and torch.is_grad_enabled()):
         return False
     if not (cfg.DANET.REFINEMENT.REFINE_ON and cfg.DANET.REFINEMENT.POS_INTERSUPV and cfg.DANET.JOINT_POSITION_WEIGHTS > 0):

@@ -70,7 +70,7 @@ def fold_plan(model):
     """Pair every BatchNorm2d of `model` with the convolution that feeds it (host only, no kernels)."""
     from .resnet import ConvBN, BasicBlock, Bottleneck, PoseResNet, SmplResNet
     from .hrnet import PoseHighResolutionNet
-    from .smpl_regressor import _StemNet, DecomposedPredictor
+    from .smpl_regressor import _StemNet, _MlpBnRelu, DecomposedPredictor
     names = {id(m): n for n, m in model.named_modules()}
     pairs, skip = [], set()
 
@@ -79,10 +79,13 @@ def fold_plan(model):
 
     for _, m in model.named_modules():
         if isinstance(m, DecomposedPredictor):
-            for unused in (m.rot2pos, m.pos2rot):                     # allocated, never called (smpl_regressor.py)
-                skip.update(id(u) for u in unused.modules())
+            if m.refine_strategy == 'gcn':
+                for unused in (m.rot2pos, m.pos2rot):                 # allocated, never called (smpl_regressor.py)
+                    skip.update(id(u) for u in unused.modules())
         elif isinstance(m, (ConvBN, _StemNet)):
             add(m._modules['0'], m._modules['1'])
+        elif isinstance(m, _MlpBnRelu):                               # REFINE_STRATEGY 'lstm': rot2pos / pos2rot
+            add(m._modules['0'], m._modules['1']); add(m._modules['3'], m._modules['4'])
         elif isinstance(m, BasicBlock):
             add(m.conv1, m.bn1); add(m.conv2, m.bn2)
         elif isinstance(m, Bottleneck):

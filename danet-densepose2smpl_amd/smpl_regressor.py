@@ -18,6 +18,7 @@ from .config import cfg
 from .gcn import GCN, adjacency, normalize_digraph, normalize_undigraph
 from .geometry import perspective_projection, rot6d_to_rotmat
 from .iuv_estimator import SMPL_PARENTS, SMPL_CHILDREN, DP2SMPL_MAPPING
+from .lstm_tree import CHAINS as LSTM_CHAINS, LimbLSTM, lstm_tree
 from .nn import Conv2d, BatchNorm2d
 from .resnet import SmplResNet, LimbResLayers
 from .smpl import SMPL
@@ -37,6 +38,37 @@ class _StemNet(nn.Module):
 
     def forward(self, x):
         return self._modules['3'](self._modules['1'](self._modules['0'](x), relu=True))
+
+
+class _MlpBnRelu(nn.Module):
+    """nn.Sequential(Conv2d 1x1, BatchNorm2d, ReLU, Conv2d 1x1, BatchNorm2d, ReLU) with the same child indices 0,1,3,4: the
+    reference's rot2pos / pos2rot blocks of REFINE_STRATEGY 'lstm' (smpl_regressor.py:538-557), on the project's kernels."""
+
+    def __init__(self, cin, mid, cout):
+        super().__init__()
+        self.add_module('0', Conv2d(cin, mid, 1))
+        self.add_module('1', BatchNorm2d(mid))
+        self.add_module('3', Conv2d(mid, cout, 1))
+        self.add_module('4', BatchNorm2d(cout))
+
+    def __getitem__(self, i):
+        return self._modules[str(i)]
+
+    def forward(self, x):
+        m = self._modules
+        return m['4'](m['3'](m['1'](m['0'](x), relu=True)), relu=True)
+
+
+# the joints of the SMPL tree by depth: a joint's rot2pos input is its parent's output (smpl_regressor.py:786-792).  The root is its
+# own parent (P[0] = 0) and is in the reference's first branch: its output replaces pos[0] = rot_feats[:, 0] before its children run.
+def _tree_levels():
+    depth = [0] * 24
+    for j in range(1, 24):
+        depth[j] = depth[SMPL_PARENTS[j]] + 1
+    return [[j for j in range(24) if depth[j] == lv] for lv in range(max(depth) + 1)]
+
+
+TREE_LEVELS = _tree_levels()
 
 
 def _pool_conv1x1_grouped(cin, cout, groups):
@@ -269,8 +301,20 @@ class DecomposedPredictor(nn.Module):
         super().__init__()
         if cfg.DANET.INPUT_MODE not in ('iuv', 'iuv_gt'):
             raise NotImplementedError("only DANET.INPUT_MODE == 'iuv' is on the hot path")
-        if cfg.DANET.REFINE_STRATEGY != 'gcn':
-            raise NotImplementedError("only DANET.REFINE_STRATEGY == 'gcn' (the default) is on the hot path")
+        strategy = cfg.DANET.REFINE_STRATEGY
+        if strategy == 'gcn_direct':
+            raise NotImplementedError("DANET.REFINE_STRATEGY 'gcn_direct' is not supported: with USE_6D_ROT the reference's branch "
+                                      "returns a para of width 157 instead of 229 (it skips the 6D-to-rotation-matrix step), so "
+                                      "there is no correct behaviour to match")
+        if strategy not in ('gcn', 'lstm', 'lstm_direct'):
+            raise NotImplementedError("DANET.REFINE_STRATEGY must be 'gcn', 'lstm' or 'lstm_direct' (got %r)" % (strategy,))
+        if strategy != 'gcn' and cfg.DANET.REFINEMENT.STACK_NUM != 1:
+            raise NotImplementedError(
+                "DANET.REFINEMENT.STACK_NUM must be 1 with REFINE_STRATEGY %r: " % strategy +
+                ("the reference builds only two pose_regressors in 'lstm_direct'" if strategy == 'lstm_direct' else
+                 "in the reference's 'lstm' training pass stack 1's pre-LSTM position head would be coord_regressors[1], which "
+                 "takes 256-wide features while the pre-LSTM positions are 128 wide"))
+        self.refine_strategy = strategy
         self.in_channels = 3 * (1 + 24)
         self.register_buffer('mean_cam_shape', torch.cat(mean_params[:2], dim=1))
         self.register_buffer('mean_pose', mean_params[2])
@@ -285,6 +329,9 @@ class DecomposedPredictor(nn.Module):
         fd = cfg.DANET.REFINEMENT.FEAT_DIM
         self.rot_feat_len = self.pos_feat_len = fd
         self.limb_reslayer = LimbResLayers(limb_num_layers, inplanes=256, outplanes=fd, groups=24)
+        if strategy != 'gcn':
+            self._init_lstm(fd)
+            return
 
         # allocated by the reference for every 'gcn' model but unused by its forward (:583-600)
         self.rot2pos = nn.ModuleList([nn.Sequential(nn.Conv2d(2 * fd, 512, 1), nn.BatchNorm2d(512), nn.ReLU(True),
@@ -331,6 +378,53 @@ class DecomposedPredictor(nn.Module):
         self.r2p_gcn = GCN(128, 128, 128, num_layers=1, num_nodes=24)
         self.register_buffer('p2r_A', torch.from_numpy(normalize_digraph(p2r, AD_mode=False)).float().unsqueeze(0))
         self.p2r_gcn = GCN(128, 128, 128, num_layers=1, num_nodes=24)
+
+    def _init_lstm(self, fd):
+        """The modules of REFINE_STRATEGY 'lstm' / 'lstm_direct' (smpl_regressor.py:509-579), one stack."""
+        self.limb_lstm = nn.ModuleList([nn.ModuleList([LimbLSTM(fd, fd) for _ in range(len(LSTM_CHAINS) - 1)])])
+        if self.refine_strategy == 'lstm_direct':
+            self.pose_regressors = nn.ModuleList([_pool_conv1x1_grouped(fd * 24, 9 * 24, 24), _pool_conv1x1_grouped(2 * fd * 24, 9 * 24, 24)])
+            return
+        # pos2rot's input rows gather (parent, joint, child) of every joint: a device index (not in the state dict), so the gather is
+        # capturable (a Python list index would be copied from the host at every call)
+        self.register_buffer('tri_index', torch.tensor([[SMPL_PARENTS[j], j, SMPL_CHILDREN[j]] for j in range(24)]).reshape(-1),
+                             persistent=False)
+        self.rot2pos = nn.ModuleList([nn.ModuleList([_MlpBnRelu(2 * fd, 512, fd) for _ in range(24)])])
+        self.pos2rot = nn.ModuleList([_MlpBnRelu(2 * fd * 3, 1024, fd)])
+        if cfg.DANET.REFINEMENT.POS_INTERSUPV:
+            self.coord_regressors = nn.ModuleList([_pool_conv1x1_grouped(fd * 24, 3 * 24, 24), _pool_conv1x1_grouped(2 * fd * 24, 3 * 24, 24)])
+        self.pose_regressors = nn.ModuleList([_pool_conv1x1_grouped(fd * 24, 6 * 24, 24) for _ in range(2)])
+
+    def _lstm_refine(self, rot_feats, rd):
+        """smpl_regressor.py:727-842: the joint rotations [B,216] behind `para`; appends the heads' outputs to rd."""
+        nbs = rot_feats.shape[0]
+        if self.refine_strategy == 'lstm_direct':
+            rd['joint_rotation'].append(self._grouped_head(self.pose_regressors[0], rot_feats).reshape(nbs, -1))
+            ref = lstm_tree(rot_feats, self.limb_lstm[0])
+            return self._grouped_head(self.pose_regressors[1], ref).reshape(nbs, -1)
+        if self.training:
+            p0 = self._grouped_head(self.pose_regressors[0], rot_feats).reshape(nbs, -1) + self.mean_pose
+            rd['joint_rotation'].append(rot6d_to_rotmat(p0).reshape(nbs, -1))
+        fd = rot_feats.shape[2]
+        pos = [None] * 24
+        pos[0] = rot_feats[:, 0]
+        for level in TREE_LEVELS:               # every joint depends on its parent's result only (the root on rot_feats[:, 0] twice)
+            for j in level:
+                p = SMPL_PARENTS[j]
+                x = torch.cat([pos[p], rot_feats[:, p]], dim=1).view(nbs, 2 * fd, 1, 1)
+                pos[j] = self.rot2pos[0][j](x).reshape(nbs, fd).float()
+        pos = torch.stack(pos, dim=1)                                                   # [B,24,128]
+        sup = self.training and cfg.DANET.JOINT_POSITION_WEIGHTS > 0 and cfg.DANET.REFINEMENT.POS_INTERSUPV
+        if sup:
+            rd['joint_position'].append(self._grouped_head(self.coord_regressors[0], pos))
+        ref = lstm_tree(pos, self.limb_lstm[0])                                        # [B,24,256]
+        if sup:
+            rd['joint_position'].append(self._grouped_head(self.coord_regressors[1], ref))
+        tri = ref.index_select(1, self.tri_index).reshape(nbs, 24, 3 * 2 * fd)         # [B,24,768] = (pos'[P], pos', pos'[Ch])
+        tri = tri.transpose(0, 1).reshape(24 * nbs, 6 * fd, 1, 1)                       # joint-major rows: one BatchNorm over all 24B
+        rot = self.pos2rot[0](tri).reshape(24, nbs, fd).float().transpose(0, 1)         # [B,24,128]
+        pose6 = self._grouped_head(self.pose_regressors[1], rot).reshape(nbs, -1) + self.mean_pose
+        return rot6d_to_rotmat(pose6).reshape(nbs, -1)
 
     @staticmethod
     def _grouped_head(seq, feats):
@@ -382,8 +476,20 @@ class DecomposedPredictor(nn.Module):
         lf = self.limb_reslayer(_glue.regroup_parts(lf, nbs) if REGROUP_PARTS else lf.reshape(nbs, -1, lf.size(-2), lf.size(-1)))      # [B,24*128,1,1]
         rot_feats = lf.reshape(nbs, 24, -1).float()                                   # [B,24,128]
 
-        rd['joint_position'] = []
         rd['joint_rotation'] = []
+        if self.refine_strategy != 'gcn':
+            if self.refine_strategy == 'lstm':
+                rd['joint_position'] = []
+            smpl_pose = self._lstm_refine(rot_feats, rd)
+            if side is not None:
+                cur.wait_stream(side)
+                global_para.record_stream(cur)
+                _nn.SIDE_LIVE = max(0, _nn.SIDE_LIVE - 1)
+            rd['para'] = torch.cat([global_para, smpl_pose], dim=1)
+            if window:
+                rd['para'] = _SideWindowOpen.apply(rd['para'])
+            return rd
+        rd['joint_position'] = []
         # the whole graph tail below as ONE launch per direction when the configuration is the trained default (csrc/gcn_tail.hip, round 6)
         fused = _gcn_tail.fused_tail(self, rot_feats)
         if fused is not None:

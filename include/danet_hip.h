@@ -156,6 +156,33 @@ int danet_gcn_tail_forward(const void* args, void* stream);
 int danet_gcn_tail_backward(const void* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * LSTM tree refinement of REFINE_STRATEGY 'lstm' / 'lstm_direct' (csrc/lstm_tree.hip).  Replaces the five bidirectional
+ * nn.LSTM(128, 128, batch_first=True) of /root/reference/models/danet/smpl_regressor.py:742-822 run along the six chains of the
+ * SMPL tree, the stack/cat glue around them and the final `cat(pos, pos) + refined`: pos [B,24,128] -> out [B,24,256].
+ * w_ih / w_hh [512,128] and b_ih / b_hh [512] per LSTM k (limb_lstm.0.k) and direction d (0 forward, 1 = `_reverse`), gate order
+ * i, f, g, o as nn.LSTM.  forward: two launches; writes out and ws (danet_lstm_tree_ws_floats(B) floats: gates, c and h of every
+ * chain position, kept for the backward).  backward: three launches; reads pos, the weights, ws as the forward left it and g_out
+ * [B,24,256], uses scratch (danet_lstm_tree_scratch_floats(B) floats) and writes every g_* buffer completely (nothing is
+ * accumulated: g_b_ih and g_b_hh are equal).  fp32 throughout, no atomics: bitwise reproducible.  danet_lstm_tree_ok(B) = 1 when
+ * the op takes a batch of B rows (1 <= B <= 2^20). */
+struct danet_lstm_tree_args {
+    const float* pos;                                 /* [B,24,128] */
+    const float* w_ih[5][2]; const float* w_hh[5][2]; const float* b_ih[5][2]; const float* b_hh[5][2];
+    float* out;                                       /* [B,24,256] (forward) */
+    float* ws;                                        /* danet_lstm_tree_ws_floats(B) floats: forward -> backward */
+    const float* g_out;                               /* [B,24,256] (backward) */
+    float* scratch;                                   /* danet_lstm_tree_scratch_floats(B) floats (backward only) */
+    float* g_pos;                                     /* [B,24,128] */
+    float* g_w_ih[5][2]; float* g_w_hh[5][2]; float* g_b_ih[5][2]; float* g_b_hh[5][2];
+    int B;
+};
+int danet_lstm_tree_ok(int B);
+size_t danet_lstm_tree_ws_floats(int B);
+size_t danet_lstm_tree_scratch_floats(int B);
+int danet_lstm_tree_forward(const void* args, void* stream);
+int danet_lstm_tree_backward(const void* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Global (25-class) IUV glue (csrc/iuv_ops.hip).  Replaces utils/iuvmap.py:6-38,103-147 (iuvmap_clean, iuv_img2map),
  * models/danet/iuv_estimator.py:304-341 (body_uv_losses) and danet.py:194-205,247 (part drop, clean, concat), and
  * utils/keypoints.py:334-394 (soft-argmax of the joint heat-maps).
