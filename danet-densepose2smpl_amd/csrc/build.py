@@ -38,6 +38,7 @@ UNITS = {
     'conv_f32.hip': ['-ffp-contract=off'],
     'conv_f32m.hip': MFMA_VGPR,
     'part_ops.hip': [],
+    'part_gt.hip': [],
     'iuv_ops.hip': [],
     'loss_ops.hip': [],
     'adam.hip': [],

@@ -1,14 +1,15 @@
 """DaNet orchestration with the reference's interface (/root/reference/models/danet/danet.py):
 ``DaNet(options, smpl_mean_params, pretrained)``, ``forward(in_dict)`` (training) and
 ``infer_net(image)`` (inference); sub-modules ``img2iuv``, ``iuv2smpl`` (+ ``iuv2smpl.smpl``) and the
-attribute ``iuv_renderer``.  Default configuration only (INPUT_MODE 'iuv', DECOMPOSED, 'gcn')."""
+attribute ``iuv_renderer``.  INPUT_MODE 'iuv' (the default) and 'iuv_gt' (the regressor on ground-truth IUV, danet.py:46-58,
+67-88,159-191,245-262,314-323), DECOMPOSED."""
 import torch
 import torch.nn as nn
 
 from .config import cfg
 from .geometry import batch_rodrigues
 from .iuv_estimator import IUV_Estimator, DP2SMPL_MAPPING
-from .iuvmap import iuvmap_clean
+from .iuvmap import iuv_img2map, iuvmap_clean
 from . import part_ops
 from . import segments
 
@@ -22,7 +23,7 @@ class DaNet(nn.Module):
         super().__init__()
         self.options = options
         self.img2iuv = IUV_Estimator(pretrained)
-        final_feat_dim = getattr(self.img2iuv.iuv_est, 'final_feat_dim', None)
+        final_feat_dim = getattr(getattr(self.img2iuv, 'iuv_est', None), 'final_feat_dim', None)       # (None in 'iuv_gt')
         self.iuv2smpl = SMPL_Regressor(options, cfg.DANET.INIMG_SIZE, final_feat_dim, smpl_mean_params, pretrained,
                                        smpl_model=smpl_model)
         self.iuv_renderer = IUV_Renderer(cfg.DANET.INIMG_SIZE, cfg.DANET.HEATMAP_SIZE, densepose=densepose,
@@ -46,6 +47,8 @@ class DaNet(nn.Module):
         if self.training:
             raise ValueError('You should call this function only on inference.'
                              'Set the network in inference mode by net.eval().')
+        if self.img2iuv.input_mode == 'iuv_gt':
+            return self._infer_iuv_gt(image)
         with torch.no_grad():
             rd = {'visualization': {}}
             uv = self.img2iuv(image)
@@ -56,6 +59,29 @@ class DaNet(nn.Module):
                 rd['visualization']['part_iuv_pred'] = uv['part_iuv_pred']
                 part_iuv_map = self._clean_partial(uv['part_iuv_pred'])
             iuv_map = torch.cat([u, v, idx], dim=1)
+            out = self.iuv2smpl.smpl_infer_net({'iuv_map': iuv_map, 'part_iuv_map': part_iuv_map})
+            rd['para'] = out['para']
+            rd['visualization'].update(out['visualization'])
+            return rd
+
+    def _infer_iuv_gt(self, inputs):
+        """danet.py:67-73,85-88,117-120: inputs = (image, iuv_image_gt [B,3,H,W], smpl_kps_gt [B,24,2|3]); the global maps are
+        iuv_img2map of the ground truth (no clean), the partial maps its 24 crops (no jitter in eval)."""
+        if not isinstance(inputs, (tuple, list)) or len(inputs) != 3:
+            raise ValueError("DANET.INPUT_MODE 'iuv_gt': infer_net takes (image, iuv_image_gt, smpl_kps_gt)")
+        image, iuv_gt, kps = inputs
+        from . import conv as _conv
+        with torch.no_grad():
+            rd = {'visualization': {'iuv_pred': list(iuv_img2map(iuv_gt))}}
+            fused = FUSED_PART_OPS and iuv_gt.is_cuda and _conv.PRECISION != 'fp32'
+            uv = self.img2iuv(image, iuv_gt, kps, part_clean=(None,) if fused else None)
+            if 'part_x24' in uv:
+                iuv_map = uv['iuv_map']
+                part_iuv_map = part_ops.padded_part_view(uv['part_x24'])
+                part_iuv_map._nhwc_padded = uv['part_x24']
+            else:
+                iuv_map = torch.cat(rd['visualization']['iuv_pred'][:3], dim=1)
+                part_iuv_map = uv['part_iuv_gt']
             out = self.iuv2smpl.smpl_infer_net({'iuv_map': iuv_map, 'part_iuv_map': part_iuv_map})
             rd['para'] = out['para']
             rd['visualization'].update(out['visualization'])
@@ -103,6 +129,8 @@ class DaNet(nn.Module):
         pk = None
         if keep is not None:                                                  # danet.py:264-274
             pk = keep25[:, self._partial_src]                                # [B,24,7]
+        if self.img2iuv.input_mode == 'iuv_gt':
+            return self._forward_iuv_gt(in_dict, rd, uv_image_gt, target, keep25, pk)
         # (the cleaned partial maps are made together with the partial losses when the regressor will run: part_ops.part_joint)
         want_x24 = FUSED_PART_OPS and image.is_cuda and _conv.PRECISION != 'fp32' and not in_dict.get('pretrain_mode', False)
         uv = self.img2iuv(image, uv_image_gt, target_smpl_kps, uvia_dp_gt=in_dict.get('dp_dict'), has_iuv=has_iuv, has_dp=has_dp,
@@ -152,6 +180,54 @@ class DaNet(nn.Module):
         for key in ('losses', 'metrics', 'visualization', 'prediction'):
             if key in uv:
                 rd[key].update(uv[key])
+            if smpl_rd is not None:
+                rd[key].update(smpl_rd[key])
+        for key in ('losses', 'metrics'):
+            for k, v in rd[key].items():
+                if v.dim() == 0:
+                    rd[key][k] = v.unsqueeze(0)
+        return rd
+
+    def _forward_iuv_gt(self, in_dict, rd, uv_image_gt, target, keep25, pk):
+        """INPUT_MODE 'iuv_gt' training pass (danet.py:159-191,193-205,245-262,314-323): the regressor reads the ground truth -- the
+        dropped, cleaned global maps and the dropped (not cleaned) crops; the loss dict is the regressor's alone.  The crops' only
+        gradient is the one with respect to their sampling grid, which reaches the learned crop ratios / offsets."""
+        from . import conv as _conv
+        B = uv_image_gt.shape[0]
+        fused = FUSED_PART_OPS and uv_image_gt.is_cuda and _conv.PRECISION != 'fp32'
+        uv = self.img2iuv(in_dict['img'], uv_image_gt, in_dict.get('target_smpl_kps'), keep25=keep25, part_clean=(pk,) if fused else None)
+        if 'part_x24' in uv:
+            # one launch (part_ops.part_gt): [U | V | I | 5 zeros] bf16 body operand and the zero-padded limb operand, keep applied
+            iuv_map, x24 = uv['iuv_map'], uv['part_x24']
+            rd['visualization']['iuv_pred'] = [iuv_map[:, :25].detach(), iuv_map[:, 25:50].detach(), iuv_map[:, 50:75].detach(), None]
+            part_iuv_map = None
+        else:
+            u, v, i, a = iuv_img2map(uv_image_gt)
+            if keep25 is not None:
+                k4 = keep25.view(B, 25, 1, 1)
+                u, v, i = u * k4, v * k4, i * k4
+            u, v, i, a = iuvmap_clean(u, v, i, a)
+            rd['visualization']['iuv_pred'] = [u.detach(), v.detach(), i.detach(), a.detach()]
+            iuv_map = torch.cat([u, v, i], dim=1)
+            part_iuv_map = uv['part_iuv_gt']
+            if pk is not None:
+                part_iuv_map = part_iuv_map * pk.view(B, 24, 1, 7, 1, 1)
+        if in_dict.get('vis_on', False):
+            rd['visualization']['gt_uv'] = uv_image_gt
+        smpl_rd = None
+        if not in_dict.get('pretrain_mode', False):
+            if part_iuv_map is None:
+                iuv_map, x24 = segments.cut([iuv_map, x24])
+                part_iuv_map = part_ops.padded_part_view(x24)
+                part_iuv_map._nhwc_padded = x24
+            else:
+                iuv_map, part_iuv_map = segments.cut([iuv_map, part_iuv_map])
+            rd['visualization']['part_iuv_pred'] = part_iuv_map
+            smpl_rd = self.iuv2smpl({'iuv_map': iuv_map, 'part_iuv_map': part_iuv_map, 'target': target,
+                                     'target_kps': in_dict.get('keypoints'), 'target_verts': in_dict.get('target_verts'),
+                                     'target_kps3d': in_dict.get('pose_3d'), 'has_kp3d': in_dict.get('has_pose_3d'),
+                                     'has_smpl': in_dict.get('valid_fit')})
+        for key in ('losses', 'metrics', 'visualization', 'prediction'):
             if smpl_rd is not None:
                 rd[key].update(smpl_rd[key])
         for key in ('losses', 'metrics'):

@@ -383,6 +383,9 @@ class InferenceEngine(object):
     so a captured graph stays valid.  close() releases the graph and its memory pool."""
 
     def __init__(self, model, batch_size, img_size=None, graph=True, mesh=False):
+        if getattr(model.img2iuv, 'input_mode', 'iuv') == 'iuv_gt':
+            raise NotImplementedError("InferenceEngine folds the IUV backbone's BatchNorms and captures image -> para; DANET.INPUT_MODE "
+                                      "'iuv_gt' has no backbone and takes (image, iuv_image_gt, smpl_kps_gt): use DaNet.infer_net")
         if model.training:
             raise ValueError('You should call this function only on inference.'
                              'Set the network in inference mode by net.eval().')

@@ -1,7 +1,8 @@
 """IUV estimator: backbone + global IUV heads + joint-centric part decomposition + IUV losses.
 
 Mirrors /root/reference/models/danet/iuv_estimator.py (IUV_Estimator :17-301, body_uv_losses
-:304-341, part_iuv_simp :422-445) for the default path (INPUT_MODE 'iuv', DECOMPOSED).  The 24
+:304-341, part_iuv_simp :422-445) for the default path (INPUT_MODE 'iuv', DECOMPOSED) and for INPUT_MODE 'iuv_gt'
+(:64-89: no backbone, the 24 crops of the ground-truth IUV image, differentiable in the learned crop ratios).  The 24
 affine resamplings of the feature map are one HIP launch (nn.stn_gather); all batch filtering by
 has_iuv is expressed as per-sample weights, so there is no boolean-mask indexing, no
 torch.unique and no host synchronisation inside the step (hipGraph-capturable).
@@ -39,6 +40,40 @@ DP2SMPL_MAPPING = [[7, 8, 9, 10, 1, 2], [1, 2, 8, 10, 12, 14], [1, 2, 7, 9, 11, 
                    [15, 17, 19, 21, 4, 4], [16, 18, 20, 22, 3, 3], [15, 17, 19, 21, 4, 4], [16, 18, 20, 22, 3, 3]]
 
 _LEARNED_RATIO_PATHS = ('data/pretrained_model/learned_ratio.pkl',)
+
+
+def save_learned_ratio(model_or_estimator, path):
+    """Write the 24 + 24 raw (un-ReLU'd) crop ratios / offsets of a DaNet or IUV_Estimator as the pickle load_learned_ratio reads
+    ({'ratio', 'offset'}, float32) -- e.g. after training them in DANET.INPUT_MODE 'iuv_gt', the one mode in which they get a gradient."""
+    est = getattr(model_or_estimator, 'img2iuv', model_or_estimator)
+    d = {'ratio': est.learned_ratio.detach().cpu().to(torch.float32).numpy().copy(),
+         'offset': est.learned_offset.detach().cpu().to(torch.float32).numpy().copy()}
+    with open(path, 'wb') as f:
+        pickle.dump(d, f)
+
+
+# why the reference's other DANET.INPUT_MODEs are refused: their training passes do not run in the reference itself
+_MODE_REFUSED = {
+    'feat': "the reference's training pass calls iuv2smpl without has_smpl (danet.py:296-332), so SMPL_Regressor._forward raises "
+            "KeyError (smpl_regressor.py:139)",
+    'rgb': "no iuv2smpl branch of the reference's training pass matches it (danet.py:296-332), so smpl_return_dict is never assigned",
+}
+for _m in ('iuv_feat', 'iuv_gt_feat', 'seg'):
+    _MODE_REFUSED[_m] = _MODE_REFUSED['feat']
+
+
+def check_input_mode():
+    """-> cfg.DANET.INPUT_MODE if this project builds it ('iuv', or 'iuv_gt' with DECOMPOSED); NotImplementedError naming the reason
+    otherwise."""
+    mode = cfg.DANET.INPUT_MODE
+    if mode in _MODE_REFUSED:
+        raise NotImplementedError("DANET.INPUT_MODE %r is not supported: %s" % (mode, _MODE_REFUSED[mode]))
+    if mode not in ('iuv', 'iuv_gt'):
+        raise NotImplementedError("unknown DANET.INPUT_MODE %r ('iuv' and 'iuv_gt' are supported)" % (mode,))
+    if mode == 'iuv_gt' and not cfg.DANET.DECOMPOSED:
+        raise NotImplementedError("DANET.INPUT_MODE 'iuv_gt' needs DANET.DECOMPOSED: the reference's GlobalPredictor returns no "
+                                  "'joint_rotation', so its training pass raises KeyError (smpl_regressor.py:147)")
+    return mode
 
 
 def load_learned_ratio(path=None):
@@ -82,10 +117,13 @@ def _sample_points(maps, pts, align):
 class IUV_Estimator(nn.Module):
     def __init__(self, pretrained=True, learned_ratio_path=None):
         super().__init__()
-        if cfg.DANET.INPUT_MODE != 'iuv':
-            raise NotImplementedError("only DANET.INPUT_MODE == 'iuv' (the default) is on the hot path")
+        self.input_mode = check_input_mode()
         ratio, offset = load_learned_ratio(learned_ratio_path) if cfg.DANET.USE_LEARNED_RATIO else (None, None)
-        if ratio is not None:
+        if ratio is not None and self.input_mode == 'iuv_gt':
+            # (iuv_estimator.py:26-28: trained in this mode -- the crops' sampling grid carries their gradient)
+            self.learned_ratio = nn.Parameter(torch.from_numpy(ratio))
+            self.learned_offset = nn.Parameter(torch.from_numpy(offset))
+        elif ratio is not None:
             self.register_buffer('learned_ratio', torch.from_numpy(ratio))
             self.register_buffer('learned_offset', torch.from_numpy(offset))
         else:
@@ -96,7 +134,9 @@ class IUV_Estimator(nn.Module):
         self.smpl2dp_part = SMPL2DP_PART
         self.dp2smpl_mapping = DP2SMPL_MAPPING
         part_out_dim = 1 + len(DP2SMPL_MAPPING[0])
-        if cfg.DANET.IUV_REGRESSOR == 'resnet':
+        if self.input_mode == 'iuv_gt':
+            pass                                             # no backbone: the crops come from the ground-truth IUV image
+        elif cfg.DANET.IUV_REGRESSOR == 'resnet':
             self.iuv_est = PoseResNet(part_out_dim=part_out_dim)
             if pretrained:
                 self.iuv_est.init_weights(cfg.MSRES_MODEL.get('PRETRAINED', ''))
@@ -139,7 +179,7 @@ class IUV_Estimator(nn.Module):
         if jit > 0:
             scale = scale * (1 + jit * (torch.rand_like(scale) - 0.5))
         B = c.shape[0]
-        theta = torch.zeros(B, 24, 2, 3, device=c.device, dtype=torch.float32)
+        theta = torch.zeros(B, 24, 2, 3, device=c.device, dtype=torch.float64 if c.dtype == torch.float64 else torch.float32)
         theta[:, :, 0, 0] = scale
         theta[:, :, 1, 1] = scale
         theta[:, :, :, 2] = c.detach()
@@ -246,6 +286,8 @@ class IUV_Estimator(nn.Module):
         autograd node as the partial losses (part_ops.part_joint)."""
         rd = {'losses': {}, 'metrics': {}, 'visualization': {}}
         align = bool(cfg.DANET.get('ALIGN_CORNERS', True))
+        if self.input_mode == 'iuv_gt':
+            return self._forward_iuv_gt(rd, iuv_image_gt, smpl_kps_gt, keep25, part_clean, align)
         est = self.iuv_est(data)
         u_pred, v_pred = est['predict_u'], est['predict_v']
         index_pred, ann_pred = est['predict_uv_index'], est['predict_ann_index']
@@ -381,4 +423,29 @@ class IUV_Estimator(nn.Module):
             # the index loss a mean over pixels -- the joint axis is already inside the mean here
             rd['losses'].update({'loss_pU': lU / 24., 'loss_pV': lV / 24., 'loss_pIndexUV': lI})
         rd['part_iuv_pred'] = part_pred
+        return rd
+
+    def _forward_iuv_gt(self, rd, iuv_image_gt, smpl_kps_gt, keep25, part_clean, align):
+        """INPUT_MODE 'iuv_gt' (iuv_estimator.py:64-89): the 24 crops of the ground-truth IUV image, centred on the ground-truth joints.
+        theta is not detached: the crops' sampling grid carries the gradient to learned_ratio / learned_offset (affine_para).  No losses.
+        part_clean = (keep [B,24,7] or None,) (the caller feeds the regressor the fused operands): rd['part_x24'] and rd['iuv_map'] (the
+        body operand: keep25-dropped, cleaned global maps) from one launch (part_ops.part_gt); otherwise rd['part_iuv_gt']
+        [B,24,3,7,H,W] from the tensor-op formulation (the oracle; fp32 verification mode and CPU tensors)."""
+        if iuv_image_gt is None or smpl_kps_gt is None:
+            raise ValueError("DANET.INPUT_MODE 'iuv_gt' needs the ground-truth IUV image and the joint centres")
+        centers = smpl_kps_gt[:, :, :2]
+        centers = centers if centers.dtype == torch.float64 else centers.to(torch.float32)
+        if self.training and cfg.DANET.STN_CENTER_JITTER > 0:
+            centers = centers + cfg.DANET.STN_CENTER_JITTER * (torch.rand_like(centers) - 0.5)
+        thetas, _ = self.affine_para(centers)
+        from . import conv as _conv
+        if part_clean is not None and iuv_image_gt.is_cuda and _conv.PRECISION != 'fp32':
+            rd['part_x24'], rd['iuv_map'] = part_ops.part_gt(iuv_image_gt, thetas, self._dp_sel, part_clean[0], keep25, align, body=True)
+            return rd
+        U, V, I, _ = iuv_img2map(iuv_image_gt.to(thetas.dtype))
+        simp = self.part_iuv_simp(U, V, I)                                               # [B,24,3,7,H,W]
+        B, H, W = simp.shape[0], simp.shape[-2], simp.shape[-1]
+        flat = simp.reshape(B * 24, 21, H, W)
+        grid = F.affine_grid(thetas.reshape(B * 24, 2, 3).to(flat.dtype), list(flat.shape), align_corners=align)
+        rd['part_iuv_gt'] = F.grid_sample(flat, grid, mode='bilinear', padding_mode='zeros', align_corners=align).reshape(B, 24, 3, 7, H, W)
         return rd

@@ -198,3 +198,56 @@ def part_joint(pred, keep, iuv_img, theta, sample_w, sel, align, scales):
         B, J, T, K, H, W = pred.shape
         pred = getattr(pred, '_padded', None) if getattr(pred, '_padded', None) is not None else pred.reshape(B, J * T * K, H, W)
     return PartJointFunction.apply(pred, keep, iuv_img, theta, sample_w, sel, align, scales)
+
+
+class PartGtFunction(torch.autograd.Function):
+    """Ground-truth part crops of DANET.INPUT_MODE 'iuv_gt' (csrc/part_gt.hip), differentiable in theta:
+    (iuv_img [B,3,H,W], theta [B,24,2,3], sel [24,6], keep [B,24,7] | None, keep25 [B,25] | None, align, body) ->
+    x24 [B*24,24,H,W] bf16 channels_last (channels 21..23 zero) and, when `body`, the body operand [B,80,H,W] bf16 channels_last
+    (no gradient).  Backward: d theta, all six entries (the IUV image carries no gradient)."""
+
+    @staticmethod
+    def forward(ctx, iuv_img, theta, sel, keep, keep25, align, body):
+        img = iuv_img.detach().to(torch.float32).contiguous()
+        th = theta.detach().to(torch.float32).contiguous()
+        sel = sel.to(torch.int32).contiguous()
+        B, _, H, W = img.shape
+        if img.shape != (B, 3, H, W) or th.shape != (B, NJ, 2, 3) or sel.shape != (NJ, 6):
+            raise ValueError('part_gt: bad shapes %s %s %s' % (tuple(img.shape), tuple(th.shape), tuple(sel.shape)))
+        k = None if keep is None else keep.detach().to(torch.float32).contiguous()
+        k25 = None if keep25 is None else keep25.detach().to(torch.float32).contiguous()
+        if (k is not None and k.shape != (B, NJ, NC)) or (k25 is not None and k25.shape != (B, 25)):
+            raise ValueError('part_gt: bad keep shapes')
+        x24 = torch.empty(B * NJ, H, W, 24, dtype=torch.bfloat16, device=img.device)
+        mp = torch.empty(B, H, W, 80, dtype=torch.bfloat16, device=img.device) if body else None
+        check(_lib.lib().danet_part_gt_forward(ptr(img), ptr(th), ptr(sel), ptr(k), ptr(k25), B, H, W, int(bool(align)), ptr(x24), ptr(mp),
+                                               stream()), 'danet_part_gt_forward')
+        ctx.save_for_backward(img, th, sel, k)
+        ctx.align = int(bool(align))
+        ctx.theta_dtype = theta.dtype
+        ctx.set_materialize_grads(False)
+        if mp is None:
+            return x24.permute(0, 3, 1, 2)
+        ctx.mark_non_differentiable(mp)
+        return x24.permute(0, 3, 1, 2), mp.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g24, *_):
+        if g24 is None or not ctx.needs_input_grad[1]:
+            return (None,) * 7
+        img, th, sel, k = ctx.saved_tensors
+        B, _, H, W = img.shape
+        g24 = nhwc_bf16(g24)
+        dth = torch.empty(B, NJ, 2, 3, dtype=torch.float32, device=img.device)
+        check(_lib.lib().danet_part_gt_backward(ptr(img), ptr(th), ptr(sel), ptr(k), ptr(g24.permute(0, 2, 3, 1)), B, H, W, ctx.align,
+                                                ptr(dth), stream()), 'danet_part_gt_backward')
+        return None, dth.to(ctx.theta_dtype), None, None, None, None, None
+
+
+def part_gt(iuv_img, theta, sel, keep=None, keep25=None, align=True, body=False):
+    """x24 [B*24,24,H,W] bf16 channels_last = keep * (part_iuv_simp + affine_grid/grid_sample of the IUV image by theta), channels 21..23
+    zero (the regressor's limb operand, as part_clean makes it); with body=True also the body operand [B,80,H,W] (iuvmap_clean of the
+    keep25-dropped iuv_img2map, [U | V | I | 5 zeros]).  Differentiable in theta.  GPU only."""
+    if not iuv_img.is_cuda:
+        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % iuv_img.device)
+    return PartGtFunction.apply(iuv_img, theta, sel, keep, keep25, align, body)

@@ -293,6 +293,18 @@ int danet_part_loss_backward(const void* pred, const float* iuv_img, const float
 int danet_part_backward_fused(const void* pred, const float* iuv_img, const float* theta, const float* sample_w,
                               const int* sel, const float* scale, const void* g24, const float* keep,
                               int B, int H, int W, int align, int cpj, void* gpred, void* stream);
+/* Ground-truth part crops of DANET.INPUT_MODE 'iuv_gt' (/root/reference/models/danet/iuv_estimator.py:64-89), differentiable in theta.
+ *  danet_part_gt_forward   iuv_img [B,3,H,W] f32, theta [B,24,2,3] f32, sel [24][6] int, keep [B,24,7] (NULL = 1) ->
+ *                          x24 [B*24,H,W,24] bf16 = keep * grid_sample(part_iuv_simp(iuv_img), affine_grid(theta)) (channels 21..23 zero;
+ *                          the layout of danet_part_clean_forward).  body (NULL = not written): [B,H,W,80] bf16 = [U | V | I | 5 zeros]
+ *                          of iuvmap_clean(keep25 * iuv_img2map(iuv_img)), keep25 [B,25] (NULL = 1).  One launch.
+ *  danet_part_gt_backward  g24 = d x24 (layout of x24) -> dtheta [B,24,2,3] f32, all six entries; one workgroup per (b, joint),
+ *                          fixed-order reduction (bitwise reproducible).
+ */
+int danet_part_gt_forward(const float* iuv_img, const float* theta, const int* sel, const float* keep, const float* keep25,
+                          int B, int H, int W, int align, void* x24, void* body, void* stream);
+int danet_part_gt_backward(const float* iuv_img, const float* theta, const int* sel, const float* keep, const void* g24,
+                           int B, int H, int W, int align, float* dtheta, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Convolution (replaces the cuDNN/ATen kernels behind every nn.Conv2d on the hot path:
