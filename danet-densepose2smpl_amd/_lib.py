@@ -143,6 +143,11 @@ _SIGNATURES = {
     'danet_lstm_tree_scratch_floats': (c_sz, [c_i]),
     'danet_lstm_tree_forward': (c_i, [c_f, c_f]),
     'danet_lstm_tree_backward': (c_i, [c_f, c_f]),
+    'danet_iuv_map2img_forward': (c_i, [c_f] * 4 + [ctypes.POINTER(ctypes.c_int64)] + [c_i] * 7 + [c_f, c_f, c_f]),
+    'danet_mesh_shade_ws_bytes': (c_sz, [c_i, c_i]),
+    'danet_mesh_shade_vertices': (c_i, [c_f, c_i, c_i, c_f, c_i, c_f, c_f, ctypes.POINTER(c_fl), c_fl, c_fl, c_fl, c_f, c_sz, c_f]),
+    'danet_mesh_shade_pixels': (c_i, [c_f, c_f, c_i, c_i, c_f, c_i, c_f, c_f, c_fl, c_fl, c_i, c_f, c_f, c_f]),
+    'danet_demo_compose': (c_i, [c_f] * 7 + [c_i] * 3 + [c_f, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations

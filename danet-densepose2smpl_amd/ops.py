@@ -148,6 +148,101 @@ def iuv_raster(verts, cam, vert_mapping, faces, tex, focal, orig, out_size, retu
     return (out, fidx, depth) if return_aux else out
 
 
+def _dev_tensor(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError('danet_hip ops run on the GPU only (%s: got a %s tensor); there is no CPU path'
+                           % (what, t.device if torch.is_tensor(t) else type(t).__name__))
+    return t.detach()
+
+
+def iuv_map2img(U, V, I, A=None, table=None):
+    """The decode kernel behind iuvmap.iuv_map2img / part_iuv_map2img (csrc/vis_ops.hip), one launch.  U, V, I: [N,K,H,W] or
+    [B,J,K,H,W] fp32 / bf16 with any strides (they are passed on, nothing is copied); A: [N,KA,H,W] or None; table: device
+    [J,K] f32 or None.  -> [N,3,H,W] / [B,J,3,H,W] f32."""
+    import ctypes
+    L = _lib.lib()
+    ts = [_dev_tensor(t, 'iuv_map2img') for t in (U, V, I)] + ([] if A is None else [_dev_tensor(A, 'iuv_map2img')])
+    dt = ts[0].dtype
+    if dt not in (torch.float32, torch.bfloat16) or any(t.dtype != dt for t in ts):
+        ts = [t.to(torch.float32) for t in ts]
+        dt = torch.float32
+    five = ts[0].dim() == 5
+    if ts[0].dim() not in (4, 5) or any(t.dim() != ts[0].dim() for t in ts) or any(t.shape != ts[0].shape for t in ts[:3]):
+        raise ValueError('iuv_map2img: U, V, Index must share one [N,K,H,W] or [B,J,K,H,W] shape, got %s' % [tuple(t.shape) for t in ts])
+    if not five:
+        ts = [t.unsqueeze(1) for t in ts]
+    NB, J, K, H, W = ts[0].shape
+    KA = 0
+    if A is not None:
+        if ts[3].shape[:2] != (NB, J) or ts[3].shape[3:] != (H, W):
+            raise ValueError('iuv_map2img: AnnIndex %s does not match %s' % (tuple(ts[3].shape), tuple(ts[0].shape)))
+        KA = ts[3].shape[2]
+    if table is not None and (table.dtype != torch.float32 or tuple(table.shape) != (J, K) or not table.is_contiguous()):
+        raise ValueError('iuv_map2img: table must be contiguous [%d,%d] f32' % (J, K))
+    strides = (ctypes.c_int64 * 20)(*([st for t in ts for st in t.stride()] + [0] * (20 - 5 * len(ts))))
+    out = torch.empty(NB * J, 3, H, W, device=ts[0].device, dtype=torch.float32)
+    check(L.danet_iuv_map2img_forward(ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), None if A is None else ts[3].data_ptr(),
+                                      strides, NB, J, K, KA, H, W, 0 if dt == torch.float32 else 1,
+                                      None if table is None else _dev_tensor(table, 'iuv_map2img').data_ptr(), ptr(out), stream()),
+          'danet_iuv_map2img_forward')
+    return out.view(NB, J, 3, H, W) if five else out
+
+
+def mesh_shade_vertices(verts, faces, csr_off, csr_face, lights, rot_y=0., albedo=0.9):
+    """verts [B,V,3] -> workspace holding the vertices multiplied by rotateY(rot_y) and their colours (DESIGN.md shading rule);
+    `lights`: 18 host floats (3 positions, 3 colours).  Returns (ws, rotated vertices [B,V,3] -- a view of ws)."""
+    import ctypes
+    import math
+    L = _lib.lib()
+    v = _f32c(_dev_tensor(verts, 'mesh_shade'))
+    B, V = v.shape[0], v.shape[1]
+    nws = L.danet_mesh_shade_ws_bytes(B, V)
+    ws = torch.empty(nws // 4, device=v.device, dtype=torch.float32)
+    lt = (ctypes.c_float * 18)(*[float(x) for x in lights])
+    check(L.danet_mesh_shade_vertices(ptr(v), B, V, ptr(faces), faces.shape[0], ptr(csr_off), ptr(csr_face), lt,
+                                      float(math.cos(rot_y)), float(math.sin(rot_y)), float(albedo), ptr(ws), nws, stream()),
+          'danet_mesh_shade_vertices')
+    return ws, ws[:B * V * 3].view(B, V, 3)
+
+
+def mesh_shade_pixels(ws, cam, V, faces2, fidx, images, focal, orig):
+    """The colours of mesh_shade_vertices mixed over the rasteriser's face-index plane fidx [B,S,S] -> (rgb [B,3,S,S], alpha [B,S,S])."""
+    L = _lib.lib()
+    c = _f32c(_dev_tensor(cam, 'mesh_shade'))
+    B, S = fidx.shape[0], fidx.shape[-1]
+    img = None
+    if images is not None:
+        img = _f32c(_dev_tensor(images, 'mesh_shade'))
+        if tuple(img.shape) != (B, 3, S, S):
+            raise ValueError('mesh_shade: images %s, expected %s' % (tuple(img.shape), (B, 3, S, S)))
+    rgb = torch.empty(B, 3, S, S, device=c.device, dtype=torch.float32)
+    alpha = torch.empty(B, S, S, device=c.device, dtype=torch.float32)
+    check(L.danet_mesh_shade_pixels(ptr(ws), ptr(c), B, V, ptr(faces2), faces2.shape[0], ptr(fidx), ptr(img), float(focal), float(orig), S,
+                                    ptr(rgb), ptr(alpha), stream()), 'danet_mesh_shade_pixels')
+    return rgb, alpha
+
+
+def demo_compose(images, glob, part, riuv, mesh=None, side=None, side_alpha=None):
+    """The result panels of demo.py:115-177 in one launch -> [B, S, 4.5 S (6.5 S with the mesh panels), 4] f32 RGBA."""
+    L = _lib.lib()
+    img = _f32c(_dev_tensor(images, 'demo_compose'))
+    B, _, S, _ = img.shape
+    hm = glob.shape[-1]
+    if tuple(img.shape) != (B, 3, S, S) or 4 * hm != S or tuple(glob.shape) != (B, 3, hm, hm) or tuple(riuv.shape) != (B, 3, hm, hm) \
+            or tuple(part.shape) != (B, 24, 3, hm, hm):
+        raise ValueError('demo_compose: shapes %s %s %s %s' % (tuple(img.shape), tuple(glob.shape), tuple(part.shape), tuple(riuv.shape)))
+    three = [mesh, side, side_alpha]
+    if any(t is None for t in three) != all(t is None for t in three):
+        raise ValueError('demo_compose: the two mesh panels come together')
+    if mesh is not None and (tuple(mesh.shape) != (B, 3, S, S) or tuple(side.shape) != (B, 3, S, S) or tuple(side_alpha.shape) != (B, S, S)):
+        raise ValueError('demo_compose: mesh panels %s %s %s' % (tuple(mesh.shape), tuple(side.shape), tuple(side_alpha.shape)))
+    f = lambda t: None if t is None else _f32c(_dev_tensor(t, 'demo_compose'))
+    out = torch.empty(B, S, (13 if mesh is not None else 9) * S // 2, 4, device=img.device, dtype=torch.float32)
+    check(L.danet_demo_compose(ptr(img), ptr(f(glob)), ptr(f(part)), ptr(f(riuv)), ptr(f(mesh)), ptr(f(side)), ptr(f(side_alpha)),
+                               B, S, hm, ptr(out), stream()), 'danet_demo_compose')
+    return out
+
+
 def _rodrigues(theta, which):
     L = _lib.lib()
     if theta.requires_grad:

@@ -1,5 +1,6 @@
 """IUV_Renderer with the reference's call signature (/root/reference/utils/renderer.py:202-298).
-The rasterisation (neural_renderer in the reference) is the HIP kernel of csrc/iuv_raster.hip."""
+The rasterisation (neural_renderer in the reference) is the HIP kernel of csrc/iuv_raster.hip.  MeshRenderer is the shaded
+view of /root/reference/utils/renderer.py:125-199 (opendr there) on the same rasteriser plus csrc/vis_ops.hip."""
 import numpy as np
 import torch
 
@@ -100,3 +101,69 @@ class PartRenderer(object):
                                       return_aux=True)
         mask = (fidx >= 0).to(torch.float32)
         return mask, self.get_parts(rgb, mask)
+
+
+def rotateY(points, angle):
+    """renderer.py:97-104: row vectors times the rotation about y, in double."""
+    ry = np.array([[np.cos(angle), 0., np.sin(angle)], [0., 1., 0.], [-np.sin(angle), 0., np.cos(angle)]])
+    return np.dot(points, ry)
+
+
+def vertex_face_csr(faces, num_verts):
+    """Vertex -> incident-faces table in CSR form: (offsets [V+1] int32, face ids [3F] int32), the faces of a vertex in
+    ascending face order (a face that names a vertex twice is listed twice)."""
+    faces = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    if faces.size and (faces.min() < 0 or faces.max() >= num_verts):
+        raise ValueError('faces name vertex %d of %d' % (int(faces.max()), num_verts))
+    flat = faces.reshape(-1)
+    order = np.argsort(flat, kind='stable')                 # stable: ascending face index within a vertex
+    off = np.zeros(num_verts + 1, dtype=np.int64)
+    np.cumsum(np.bincount(flat, minlength=num_verts), out=off[1:])
+    return off.astype(np.int32), (order // 3).astype(np.int32)
+
+
+LIGHT_POSITIONS = ((-200., -100., -100.), (800., 10., 300.), (-500., 500., 1000.))      # renderer.py:160-184, before rotateY(120 deg)
+LIGHT_COLORS = ((1., 1., 1.), (1., 1., 1.), (.7, .7, .7))
+ALBEDO = 0.9
+
+
+class MeshRenderer(object):
+    """Shaded view of a mesh over an image: `opendr_render.render` (/root/reference/utils/renderer.py:125-199) under the
+    shading rule of DESIGN.md (opendr is absent; what it does beyond that rule is unpinned).
+
+    MeshRenderer(faces, focal_length=5000., img_res=224, color=None)
+    __call__(vertices [B,V,3], cam [B,3] (s, tx, ty), images=None | [B,3,R,R], rot_y=0.) -> (rgb [B,3,R,R] in [0,1], alpha [B,R,R])
+
+    Coverage and depth are the HIP rasteriser's with both windings of every face (PartRenderer's mask, bit for bit); the
+    colours are two launches of csrc/vis_ops.hip.  `rot_y` (radians) multiplies the vertices by rotateY first (the side view)."""
+
+    def __init__(self, faces, focal_length=5000., img_res=224, color=None):
+        self.focal_length = focal_length
+        self.img_res = int(img_res)
+        faces = np.asarray(faces).astype(np.int32).reshape(-1, 3)
+        self.faces = torch.from_numpy(faces.copy())
+        cols = LIGHT_COLORS if color is None else (tuple(float(c) for c in np.broadcast_to(np.asarray(color, dtype=np.float64), (3,))),) * 3
+        pos = [rotateY(np.array(p), np.radians(120)) for p in LIGHT_POSITIONS]
+        self.lights = [float(x) for p in pos for x in p] + [float(x) for c in cols for x in c]
+        self._faces_np = faces
+        self._tables = {}
+
+    def _dev(self, device, nv):
+        key = (str(device), nv)
+        if key not in self._tables:
+            f = self._faces_np
+            off, inc = vertex_face_csr(f, nv)
+            f2 = np.concatenate([f, f[:, ::-1]], 0).astype(np.int32).copy()             # fill_back, as PartRenderer
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            self._tables[key] = (torch.arange(nv, dtype=torch.int32, device=device), t(f), t(f2), t(off), t(inc),
+                                 torch.zeros(f2.shape[0], 3, dtype=torch.float32, device=device))
+        return self._tables[key]
+
+    def __call__(self, vertices, cam, images=None, rot_y=0.):
+        if not vertices.is_cuda:
+            raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % vertices.device)
+        R = self.img_res
+        vm, f, f2, off, inc, tex = self._dev(vertices.device, vertices.shape[1])
+        ws, rverts = ops.mesh_shade_vertices(vertices, f, off, inc, self.lights, rot_y, ALBEDO)
+        _, fidx, _ = ops.iuv_raster(rverts, cam, vm, f2, tex, self.focal_length, R, R, return_aux=True)
+        return ops.mesh_shade_pixels(ws, cam, vertices.shape[1], f2, fidx, images, self.focal_length, R)

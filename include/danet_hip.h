@@ -673,6 +673,37 @@ int danet_maxpool3x3s2_backward(const void* gy, const void* idx, void* dx, int B
 int danet_maxpool3x3s2_forward_f32(const void* x, void* y, void* idx, int B, int H, int W, int C, void* stream);
 int danet_maxpool3x3s2_backward_f32(const void* gy, const void* idx, void* dx, int B, int H, int W, int C, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Visualisation ops of the demo pipeline (csrc/vis_ops.hip; forward only).
+ *
+ * iuv_map2img (/root/reference/utils/iuvmap.py:41-100 with uv_rois=None): U, V, I are [NB, J, K, H, W] views and A (may be
+ * NULL) a [NB, J, KA, H, W] view of fp32 (dtype 0) or bf16 (dtype 1) tensors; `strides` is a HOST array of 4 x 5 element
+ * strides (U, V, I, A; each NB, J, K, H, W).  out [NB*J, 3, H, W] f32: plane 0 = index / (K - 1), or table[j*K + index] when
+ * `table` (device, [J, K] f32) is given; planes 1, 2 = U, V of the arg-max channel (0 for index 0).  The first maximum wins
+ * a tie; the index is zeroed where the arg-max over A is 0.
+ *
+ * Shaded mesh view (DESIGN.md "shading rule"): mesh_shade_vertices writes into the workspace the vertices multiplied by
+ * rotateY (cos_y, sin_y) and their colours (area-weighted normals through the CSR vertex -> face table csr_off [V+1] /
+ * csr_face [3F], walked in table order; `lights` is a HOST array: 3 positions then 3 colours, 18 floats);
+ * mesh_shade_pixels mixes the colours of the face named by the rasteriser's face-index plane (faces2: the face table that
+ * was rasterised, [F2,3]) over `images` [B,3,S,S] (NULL: black) into rgb [B,3,S,S] and alpha [B,S,S].
+ *
+ * demo_compose (/root/reference/demo.py:115-177): images [B,3,S,S], glob / riuv [B,3,hm,hm] (S = 4 hm), part [B,24,3,hm,hm],
+ * mesh / side [B,3,S,S] + side_alpha [B,S,S] (all three NULL: no mesh panels) -> out [B, S, 4.5 S or 6.5 S, 4] f32 RGBA.
+ */
+int danet_iuv_map2img_forward(const void* U, const void* V, const void* I, const void* A, const int64_t* strides,
+                              int NB, int J, int K, int KA, int H, int W, int dtype, const float* table,
+                              float* out, void* stream);
+size_t danet_mesh_shade_ws_bytes(int B, int V);
+int danet_mesh_shade_vertices(const float* verts, int B, int V, const int32_t* faces, int F, const int32_t* csr_off,
+                              const int32_t* csr_face, const float* lights, float cos_y, float sin_y, float albedo,
+                              void* ws, size_t ws_bytes, void* stream);
+int danet_mesh_shade_pixels(const void* ws, const float* cam, int B, int V, const int32_t* faces2, int F2,
+                            const int32_t* face_idx, const float* images, float focal, float orig, int S,
+                            float* rgb, float* alpha, void* stream);
+int danet_demo_compose(const float* images, const float* glob, const float* part, const float* riuv, const float* mesh,
+                       const float* side, const float* side_alpha, int B, int S, int hm, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
