@@ -5,8 +5,10 @@ in the torch layout (state-dict compatible with the reference) and are packed to
 parameter version.  Gradients: dX through the transposed gather of the same MFMA kernel, dW
 through the wgrad kernel (fp32), dbias as a channel sum.
 """
+import contextlib
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -70,6 +72,11 @@ class ZeroArena(object):
         self.high = max(self.high, self.off)
         self.dirty = max(self.dirty, self.off)
         return t
+
+    def zeros(self, n, device):
+        """n zero floats: a slice of the arena, else (inactive, full, or refused to a capture) a zeroed tensor of their own."""
+        t = self.alloc(n)
+        return torch.zeros(n, dtype=torch.float32, device=device) if t is None else t
 
 
 ARENA = ZeroArena()
@@ -135,6 +142,27 @@ class KernelProfiler(object):
             out[(key, shape)] = (n + 1, t + e0.elapsed_time(e1) * 1e-3, f + flops)
         return out
 
+
+@contextlib.contextmanager
+def _profiled(name, flops, shape):
+    tok = PROFILER.begin(name() if callable(name) else name, flops() if callable(flops) else flops, shape)
+    yield
+    PROFILER.end(tok)
+
+
+_UNTIMED = contextlib.nullcontext()
+
+
+def _timed(name, flops, shape=None):
+    """`with _timed(...):` around ONE launch: a PROFILER record of it, nothing without a profiler.  `name` and `flops` may be
+    callables (a kernel-name lookup that asks the library, a sum over a list of problems): they run only under a profiler."""
+    return _UNTIMED if PROFILER is None else _profiled(name, flops, shape)
+
+
+def _flops(dims):
+    """Multiply-add count x 2 of one problem dims = (B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups)."""
+    B, _, _, Cin, OH, OW, Cout, R, S, _, _, _, groups = dims
+    return 2.0 * B * OH * OW * Cout * (Cin // groups) * R * S
 
 
 PRECISION = 'bf16'     # 'fp32': BASELINE config C4's arithmetic: fp32 NHWC activations, convolutions on the fp32 MFMA kernels of
@@ -223,11 +251,9 @@ class Conv2dF32Function(torch.autograd.Function):
                     b = F.pad(b.view(groups, Cout_g), (0, Cout_gp - Cout_g)).reshape(-1)
             wp = _pack_weight_f32(None if gpad else weight, w, groups, 0, Cout_gp, Cin_gp)
             y = torch.empty(B, OH, OW, Cout_p, dtype=torch.float32, device=x.device)
-            tok = PROFILER.begin('conv_f32m_kernel', 2.0 * B * OH * OW * Cout * R * S * Cin_g, (B, H, W, Cin, Cout, R, stride, groups)) if PROFILER is not None else None
-            check(L.danet_conv_f32m_forward(ptr(xh), ptr(wp), ptr(None if b is None else _pad_last(b, Cout_p)), ptr(y), B, H, W, Cin_p, OH, OW, Cout_p,
-                                            R, S, stride, pad, dil, groups, 0, 0, stream()), 'danet_conv_f32m_forward')
-            if tok is not None:
-                PROFILER.end(tok)
+            with _timed('conv_f32m_kernel', 2.0 * B * OH * OW * Cout * R * S * Cin_g, (B, H, W, Cin, Cout, R, stride, groups)):
+                check(L.danet_conv_f32m_forward(ptr(xh), ptr(wp), ptr(None if b is None else _pad_last(b, Cout_p)), ptr(y), B, H, W, Cin_p, OH, OW, Cout_p,
+                                                R, S, stride, pad, dil, groups, 0, 0, stream()), 'danet_conv_f32m_forward')
             y = y.view(B, OH, OW, groups, Cout_gp)[..., :Cout_g].reshape(B, OH, OW, Cout) if gpad else y[..., :Cout]
         else:
             y = torch.empty(B, OH, OW, Cout, dtype=torch.float32, device=x.device)
@@ -256,11 +282,9 @@ class Conv2dF32Function(torch.autograd.Function):
             if mfma and L.danet_conv_f32m_ok(B, OH, OW, Cout_p, H, W, Cin_p, R, S, stride, pad, dil, groups, 1):
                 wp = _pack_weight_f32(ctx.weight, w, groups, 1, Cout_gp, Cin_gp)
                 gx = torch.empty(B, H, W, Cin_p, dtype=torch.float32, device=g.device)
-                tok = PROFILER.begin('conv_f32m_kernel', 2.0 * B * OH * OW * Cout * R * S * Cin_g, ('dgrad', B, H, W, Cin, Cout, R, stride, groups)) if PROFILER is not None else None
-                check(L.danet_conv_f32m_forward(ptr(gp), ptr(wp), None, ptr(gx), B, OH, OW, Cout_p, H, W, Cin_p, R, S, stride, pad, dil, groups, 1, 0,
-                                                stream()), 'danet_conv_f32m_forward')
-                if tok is not None:
-                    PROFILER.end(tok)
+                with _timed('conv_f32m_kernel', 2.0 * B * OH * OW * Cout * R * S * Cin_g, ('dgrad', B, H, W, Cin, Cout, R, stride, groups)):
+                    check(L.danet_conv_f32m_forward(ptr(gp), ptr(wp), None, ptr(gx), B, OH, OW, Cout_p, H, W, Cin_p, R, S, stride, pad, dil, groups, 1, 0,
+                                                    stream()), 'danet_conv_f32m_forward')
                 gx = gx[..., :Cin]
             else:
                 wr = w.view(groups, Cout_gp, Cin_g, R, S)[:, :Cout_g].reshape(Cout, Cin_g, R, S) if (mfma and gpad) else w
@@ -476,30 +500,39 @@ def stream_tables(device):
     return t
 
 
+# What nn.BatchNorm2d leaves on its output as `_bn_ctx`: its input, whether it applied a ReLU, its saved (mean, rstd), and the ReLU
+# byte mask with the mode the BatchNorm's own backward reads it in (nn.py).
+BnCtx = namedtuple('BnCtx', 'x relu saved mask mask_mode', defaults=(None, 0))
+# What a data-gradient launch needs to also reduce that BatchNorm's backward sums: x, the tensor the ReLU gate is taken from (None: no
+# ReLU), saved, the zeroed accumulator, and the gate mode (0: gate_t is the BatchNorm's output, 2: its byte mask; see _bn_gate).
+BnBwd = namedtuple('BnBwd', 'x gate_t saved red gate')
+
+
+def _bn_bwd_ptrs(bn_bwd):
+    """(x, gate, saved, red pointers, gate mode) of a BnBwd -- or any 5-sequence in its order -- as the kernels take them; all NULL
+    / mode 0 for None.  A byte mask goes as it lies in memory, an activation as its NHWC storage; no gate tensor is mode 0."""
+    if bn_bwd is None:
+        return None, None, None, None, 0
+    x, gate_t, saved, red, gate = bn_bwd
+    gate = int(gate) if gate_t is not None else 0
+    by = None if gate_t is None else ptr(gate_t if gate else gate_t.permute(0, 2, 3, 1))
+    return ptr(x.permute(0, 2, 3, 1)), by, ptr(saved), ptr(red), gate
+
+
 def _conv_fwd_raw(x, wp, bias, B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups, transposed, relu, out_fp32,
                   bn_sums=None, bn_bwd=None, addend=None):
-    """bn_bwd = (bn_x, gate tensor or None, saved, red, bn_gate) (see _bn_gate): data-gradient launches also reduce the
-    BatchNorm-backward sums of the BN that produced the conv's input (see include/danet_hip.h)."""
+    """bn_bwd = a BnBwd (see _bn_gate): data-gradient launches also reduce the BatchNorm-backward sums of the BN that produced
+    the conv's input (see include/danet_hip.h)."""
     L = _lib.lib()
     stream_tables(x.device)
     y = _empty_nhwc(B, Cout, OH, OW, torch.float32 if out_fp32 else torch.bfloat16, x.device)
-    tok = None
-    if PROFILER is not None:
-        kid = L.danet_conv_forward_kernel(B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups, int(transposed), int(out_fp32))
-        name = _kernel_name(kid, (B, H, W, Cin, Cout) if bn_bwd is None else None)
-        tok = PROFILER.begin(name,
-                             2.0 * B * OH * OW * Cout * (Cin // groups) * R * S,
-                             ('dgrad' if transposed else 'fwd', B, H, W, Cin, Cout, R, stride, groups))
-    check(L.danet_conv_forward(ptr(x.permute(0, 2, 3, 1)), ptr(wp), ptr(bias), ptr(y.permute(0, 2, 3, 1)),
-                               B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups, int(transposed),
-                               int(relu), int(out_fp32), ptr(bn_sums),
-                               None if bn_bwd is None else ptr(bn_bwd[0].permute(0, 2, 3, 1)),
-                               None if bn_bwd is None or bn_bwd[1] is None else (ptr(bn_bwd[1]) if bn_bwd[1].dim() == 1 else ptr(bn_bwd[1].permute(0, 2, 3, 1))),
-                               None if bn_bwd is None else ptr(bn_bwd[2]), None if bn_bwd is None else ptr(bn_bwd[3]),
-                               None if addend is None else ptr(addend.permute(0, 2, 3, 1)),
-                               0 if bn_bwd is None else bn_bwd[4], stream()), 'danet_conv_forward')
-    if tok is not None:
-        PROFILER.end(tok)
+    dims = (B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups)
+    bx, by, sv, rd, gate = _bn_bwd_ptrs(bn_bwd)
+    with _timed(lambda: _kernel_name(L.danet_conv_forward_kernel(*dims, int(transposed), int(out_fp32)), (B, H, W, Cin, Cout) if bn_bwd is None else None),
+                lambda: _flops(dims), ('dgrad' if transposed else 'fwd', B, H, W, Cin, Cout, R, stride, groups)):
+        check(L.danet_conv_forward(ptr(x.permute(0, 2, 3, 1)), ptr(wp), ptr(bias), ptr(y.permute(0, 2, 3, 1)), *dims, int(transposed),
+                                   int(relu), int(out_fp32), ptr(bn_sums), bx, by, sv, rd,
+                                   None if addend is None else ptr(addend.permute(0, 2, 3, 1)), gate, stream()), 'danet_conv_forward')
     if TRACE is not None:
         TRACE.append(('dgrad' if transposed else 'conv', (B, H, W, Cin, Cout, R, stride), y.float().abs().mean()))
     return y
@@ -509,11 +542,9 @@ def _conv_stem_raw(x, wp16, B, H, W, Cin, OH, OW, Cout, bn_sums=None):
     """csrc/conv_stem.hip: 7x7 / stride 2 / pad 3 forward on LDS tiles; wp16 = pack_weight(w, 1, 0, chunk=16)."""
     L = _lib.lib()
     y = _empty_nhwc(B, Cout, OH, OW, torch.bfloat16, x.device)
-    tok = PROFILER.begin('conv_stem_kernel', 2.0 * B * OH * OW * Cout * Cin * 49, ('fwd', B, H, W, Cin, Cout, 7, 2, 1)) if PROFILER is not None else None
-    check(L.danet_conv_stem_forward(ptr(x.permute(0, 2, 3, 1)), ptr(wp16), ptr(y.permute(0, 2, 3, 1)), B, H, W, Cin, OH, OW, Cout, ptr(bn_sums), stream()),
-          'danet_conv_stem_forward')
-    if tok is not None:
-        PROFILER.end(tok)
+    with _timed('conv_stem_kernel', 2.0 * B * OH * OW * Cout * Cin * 49, ('fwd', B, H, W, Cin, Cout, 7, 2, 1)):
+        check(L.danet_conv_stem_forward(ptr(x.permute(0, 2, 3, 1)), ptr(wp16), ptr(y.permute(0, 2, 3, 1)), B, H, W, Cin, OH, OW, Cout, ptr(bn_sums), stream()),
+              'danet_conv_stem_forward')
     return y
 
 
@@ -523,38 +554,25 @@ C3A_WIDTHS = (16,)        # map widths csrc/conv3x3a.hip is used for (measured, 
 
 def _conv3x3a_raw(x, wp16, B, H, W, transposed, bn_sums=None, bn_bwd=None, addend=None):
     """csrc/conv3x3a.hip: 3x3 / stride 1 / pad 1, 64 -> 64 channels, forward (wp16 = pack_weight(w, 1, 0, chunk=16)) or data gradient
-    (transposed: x is dy, wp16 = pack_weight(w, 1, 1, chunk=16)); bn_bwd = (bn_x, gate tensor or None, saved, red, gate mode 0 / 2)."""
+    (transposed: x is dy, wp16 = pack_weight(w, 1, 1, chunk=16)); bn_bwd = a BnBwd, gate mode 0 / 2."""
     L = _lib.lib()
     y = _empty_nhwc(B, 64, H, W, torch.bfloat16, x.device)
-    bx = by = sv = rd = None
-    gate = 0
-    if bn_bwd is not None:
-        gate = int(bn_bwd[4])
-        by = None if bn_bwd[1] is None else (ptr(bn_bwd[1].permute(0, 2, 3, 1)) if gate == 0 else bn_bwd[1].data_ptr())
-        bx, sv, rd = ptr(bn_bwd[0].permute(0, 2, 3, 1)), ptr(bn_bwd[2]), ptr(bn_bwd[3])
-        if by is None:
-            gate = 0
-    tok = PROFILER.begin('conv3x3a_kernel', 2.0 * B * H * W * 64 * 64 * 9, ('dgrad' if transposed else 'fwd', B, H, W, 64, 64, 3, 1, 1)) if PROFILER is not None else None
-    check(L.danet_conv3x3a(ptr(x.permute(0, 2, 3, 1)), ptr(wp16), ptr(y.permute(0, 2, 3, 1)), B, H, W, int(transposed), ptr(bn_sums), bx, by, sv, rd, gate,
-                           None if addend is None else ptr(addend.permute(0, 2, 3, 1)), stream()), 'danet_conv3x3a')
-    if tok is not None:
-        PROFILER.end(tok)
+    bx, by, sv, rd, gate = _bn_bwd_ptrs(bn_bwd)
+    with _timed('conv3x3a_kernel', 2.0 * B * H * W * 64 * 64 * 9, ('dgrad' if transposed else 'fwd', B, H, W, 64, 64, 3, 1, 1)):
+        check(L.danet_conv3x3a(ptr(x.permute(0, 2, 3, 1)), ptr(wp16), ptr(y.permute(0, 2, 3, 1)), B, H, W, int(transposed), ptr(bn_sums), bx, by, sv, rd, gate,
+                               None if addend is None else ptr(addend.permute(0, 2, 3, 1)), stream()), 'danet_conv3x3a')
     return y
 
 
 def _conv_stem_dgrad_raw(gy, wp16t, B, H, W, Cin, OH, OW, Cout, bn_bwd=None):
     """csrc/conv_stem_dgrad.hip: data gradient of a 7x7 / stride 2 / pad 3 stem (64 -> 64 channels) on LDS tiles; wp16t =
-    pack_weight(w, 1, 1, chunk=16); bn_bwd = (bn_x, gate tensor or None, saved, red, gate mode 0) as for _conv_fwd_raw."""
+    pack_weight(w, 1, 1, chunk=16); bn_bwd = a BnBwd with gate mode 0 (the kernel knows no other) as for _conv_fwd_raw."""
     L = _lib.lib()
     gx = _empty_nhwc(B, Cin, H, W, torch.bfloat16, gy.device)
-    bx = by = sv = rd = None
-    if bn_bwd is not None:
-        bx, by, sv, rd = ptr(bn_bwd[0].permute(0, 2, 3, 1)), None if bn_bwd[1] is None else ptr(bn_bwd[1].permute(0, 2, 3, 1)), ptr(bn_bwd[2]), ptr(bn_bwd[3])
-    tok = PROFILER.begin('conv_stem_dgrad_kernel', 2.0 * B * OH * OW * Cout * Cin * 49, ('dgrad', B, OH, OW, Cout, Cin, 7, 2, 1)) if PROFILER is not None else None
-    check(L.danet_conv_stem_dgrad(ptr(gy.permute(0, 2, 3, 1)), ptr(wp16t), ptr(gx.permute(0, 2, 3, 1)), B, H, W, Cin, OH, OW, Cout, bx, by, sv, rd, stream()),
-          'danet_conv_stem_dgrad')
-    if tok is not None:
-        PROFILER.end(tok)
+    bx, by, sv, rd, _ = _bn_bwd_ptrs(bn_bwd)
+    with _timed('conv_stem_dgrad_kernel', 2.0 * B * OH * OW * Cout * Cin * 49, ('dgrad', B, OH, OW, Cout, Cin, 7, 2, 1)):
+        check(L.danet_conv_stem_dgrad(ptr(gy.permute(0, 2, 3, 1)), ptr(wp16t), ptr(gx.permute(0, 2, 3, 1)), B, H, W, Cin, OH, OW, Cout, bx, by, sv, rd, stream()),
+              'danet_conv_stem_dgrad')
     return gx
 
 
@@ -637,27 +655,23 @@ class Conv2dFunction(torch.autograd.Function):
             # (ctx.bn_ctx is only there when conv2d decided for the fused reduction: FUSE_BN_BWD_REDUCE, or FUSE_BN_BWD_STEM for this layer)
             if ctx.bn_ctx is not None and \
                     L.danet_conv_forward_kernel(B, OH, OW, Cout, H, W, Cin, R, S, stride, pad, dil, groups, 1, 0) % 10 in (1, 2):
-                bn_x, saved = ctx.bn_ctx[0], ctx.bn_ctx[2]
+                bn_ctx = ctx.bn_ctx
                 c3 = L.danet_conv_forward_kernel(B, OH, OW, Cout, H, W, Cin, R, S, stride, pad, dil, groups, 1, 0) % 10 == 2
-                gate_t, gate = _bn_gate(ctx.bn_ctx, x, c3)
-                if bn_x.shape == x.shape:
-                    n = L.danet_bn_ws_floats(Cin)
-                    red = ARENA.alloc(n)
-                    if red is None:
-                        red = torch.zeros(n, dtype=torch.float32, device=x.device)
-                    bn_bwd = (bn_x, gate_t, saved, red, gate)
+                gate_t, gate = _bn_gate(bn_ctx, x, c3)
+                if bn_ctx.x.shape == x.shape:
+                    bn_bwd = BnBwd(bn_ctx.x, gate_t, bn_ctx.saved, ARENA.zeros(L.danet_bn_ws_floats(Cin), x.device), gate)
             addend = None
             if ctx.link is not None and ctx.link.dres is not None:
                 addend, ctx.link.dres = ctx.link.dres, None
             fused_add = addend is not None and addend.shape == x.shape and bn_bwd is None and \
                 L.danet_conv_forward_kernel(B, OH, OW, Cout, H, W, Cin, R, S, stride, pad, dil, groups, 1, 0) % 10 in (1, 2, 3)      # gather, LDS-tile 3x3, pointwise
             if (addend is None or (bn_bwd is None and addend.shape == x.shape and addend.dtype == torch.bfloat16)) and \
-                    (bn_bwd is None or bn_bwd[0].dtype == torch.bfloat16) and W in C3A_WIDTHS and L.danet_conv3x3a_ok(B, H, W, Cin, Cout, R, S, stride, pad, dil, groups):
+                    (bn_bwd is None or bn_bwd.x.dtype == torch.bfloat16) and W in C3A_WIDTHS and L.danet_conv3x3a_ok(B, H, W, Cin, Cout, R, S, stride, pad, dil, groups):
                 gx = _conv3x3a_raw(gy, pack_weight(weight, groups, 1, 16, wpad), B, H, W, True, None, bn_bwd, addend)
                 if addend is not None:
                     FUSION['residual_grad_fused'] += 1
                     addend = None
-            elif addend is None and (bn_bwd is None or (bn_bwd[4] == 0 and bn_bwd[0].dtype == torch.bfloat16)) and \
+            elif addend is None and (bn_bwd is None or (bn_bwd.gate == 0 and bn_bwd.x.dtype == torch.bfloat16)) and \
                     L.danet_conv_stem_dgrad_ok(B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups):
                 # the part-crop stem (64 -> 64 channels, 7x7 / stride 2): LDS-tile kernel with the same fused BatchNorm-backward sums
                 gx = _conv_stem_dgrad_raw(gy, pack_weight(weight, groups, 1, 16, wpad), B, H, W, Cin, OH, OW, Cout, bn_bwd)
@@ -669,7 +683,7 @@ class Conv2dFunction(torch.autograd.Function):
                 if not fused_add:
                     gx = gx + addend
             if bn_bwd is not None:
-                gx._bn_red = bn_bwd[3]       # consumed by the producing BatchNorm's backward if gx reaches it unsummed
+                gx._bn_red = bn_bwd.red      # consumed by the producing BatchNorm's backward if gx reaches it unsummed
         if has_bias and ctx.needs_input_grad[2]:
             gb = channel_sum(gy)
             if TRACE is not None:
@@ -701,6 +715,10 @@ CHSUM_COPIES = int(os.environ.get('DANET_CHSUM_COPIES', '16'))            # repl
 
 DEFER_WGRAD = False       # queue weight gradients during backward; flush_wgrads() computes them in multi-problem launches
 DEFER_PADDED = bool(int(os.environ.get('DANET_DEFER_PADDED_WGRAD', '1')))       # ... those of channel-padded layers as well (A-B knob)
+# A queued weight gradient: the ADDRESS the kernel writes (never the tensor, see _enqueue_wgrad), the parameter, the operands, dims =
+# (B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups), and for a channel-padded layer post = (padded temporary, address of
+# the tensor it is cropped into, the two crop views)
+WgradJob = namedtuple('WgradJob', 'gptr weight x gy dims post')
 _WQ = []                  # 3x3 / stride 1 or 2 problems (conv_wgrad3x3.hip)
 _WQG = []                 # everything else (conv_wgrad.hip)
 GRAD_STORE = None         # distributed.GradStore of the running trainer: weight gradients are written into its views
@@ -721,14 +739,47 @@ def _check_adopted(queue):
     """autograd must have kept the returned (still unwritten) gradient tensor itself as .grad -- a copy, or an
     accumulation into an existing .grad (shared weights, gradient accumulation), would have read garbage."""
     for q in queue:
-        gptr, weight = q[0], q[1]
-        if q[-1] is not None:             # (a channel-padded layer: the kernel writes a padded temporary, .grad is the tensor it is cropped into)
-            gptr = q[-1][1]
+        weight = q.weight
+        gptr = q.gptr if q.post is None else q.post[1]      # (a channel-padded layer: the kernel writes a padded temporary, .grad is the tensor it is cropped into)
         if weight.grad is None or weight.grad.data_ptr() != gptr:
             _WQ.clear()
             _WQG.clear()
             raise RuntimeError('deferred weight gradient of a %s parameter was copied or accumulated by autograd; '
                                'set DANET_DEFER_WGRAD=0 for this model' % (tuple(weight.shape),))
+
+
+def _flush_queue(queue, mine, hold, name, job_type, fill, scratch, launch):
+    """One queue's share of flush_wgrads: the entries `mine` selects, in a multi-problem launch (profiler key `name`) for the layers at
+    their own widths and one for the channel-padded ones; fill(job, dims) sets a job's geometry, scratch(jobs, n, device) ->
+    (workspace, its floats), launch = the library entry."""
+    import ctypes
+    # (channel-padded layers -- post is not None -- go out in launches of their own: the multi-problem planners deal a fixed number of
+    # workgroups over the jobs of a call, and a dozen tiny layers in the same call took workgroups away from every other launch: +0.3 ms)
+    for wq in ([q for q in queue if mine(q) and q.post is None], [q for q in queue if mine(q) and q.post is not None]):
+        if not wq:
+            continue
+        _check_adopted(wq)
+        jobs = (job_type * len(wq))()
+        for j, q in zip(jobs, wq):
+            j.x, j.dy, j.dw = q.x.data_ptr(), q.gy.data_ptr(), q.gptr
+            fill(j, q.dims)
+        n = len(wq)
+        ws, need = scratch(ctypes.addressof(jobs), n, wq[0].x.device)
+        with _timed(name, lambda: sum(_flops(q.dims) for q in wq), ('wgrad-multi', n)):
+            check(launch(ctypes.addressof(jobs), n, ptr(ws), need, 0.0, stream()), 'danet_' + name)
+        _crop_posts(wq)
+        if hold is not None:
+            hold.extend(wq)
+    queue[:] = [q for q in queue if not mine(q)]
+
+
+def _fill_wg3(j, dims):
+    B, H, W, Cin, _, _, Cout, _, _, stride, _, _, groups = dims
+    j.B, j.H, j.W, j.Cin, j.Cout, j.groups, j.stride = B, H, W, Cin, Cout, groups, stride
+
+
+def _fill_wg(j, dims):
+    (j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups) = dims
 
 
 def flush_wgrads(bucket=None, hold=None):
@@ -737,7 +788,6 @@ def flush_wgrads(bucket=None, hold=None):
     in order and all-reduces each one while the next one's launches run).  hold: a list that receives the processed queue
     entries -- a caller that flushes on a SIDE stream keeps the operands (x, dy: allocated on the step's stream) alive until the
     streams have joined again."""
-    import ctypes
     L = _lib.lib()
 
     if bucket is not None and not isinstance(bucket, int):
@@ -746,59 +796,27 @@ def flush_wgrads(bucket=None, hold=None):
     def mine(q):
         if bucket is None or GRAD_STORE is None:
             return True
-        b = GRAD_STORE.bucket_of.get(id(q[1]), -1)
+        b = GRAD_STORE.bucket_of.get(id(q.weight), -1)
         return b == bucket if isinstance(bucket, int) else b in bucket
-    # (channel-padded layers -- post is not None -- go out in launches of their own: the multi-problem planners deal a fixed number of
-    # workgroups over the jobs of a call, and a dozen tiny layers in the same call took workgroups away from every other launch: +0.3 ms)
-    for wq in ([q for q in _WQ if mine(q) and q[-1] is None], [q for q in _WQ if mine(q) and q[-1] is not None]):
-        if not wq:
-            continue
-        _check_adopted(wq)
-        jobs = (_lib.Wg3Job * len(wq))()
-        for j, (gptr, weight, x, gy, B, H, W, Cin, Cout, groups, stride, _post) in zip(jobs, wq):
-            j.x, j.dy, j.dw = x.data_ptr(), gy.data_ptr(), gptr
-            j.B, j.H, j.W, j.Cin, j.Cout, j.groups, j.stride = B, H, W, Cin, Cout, groups, stride
-        n = len(wq)
-        need = L.danet_conv_wgrad3x3_multi_ws_floats(ctypes.addressof(jobs), n)
-        ws = torch.empty(need, dtype=torch.float32, device=wq[0][2].device)
-        tok = PROFILER.begin('conv_wgrad3x3_multi', sum(2.0 * q[4] * (q[5] // q[10]) * (q[6] // q[10]) * q[8] * (q[7] // q[9]) * 9 for q in wq),
-                             ('wgrad-multi', n)) if PROFILER is not None else None
-        check(L.danet_conv_wgrad3x3_multi(ctypes.addressof(jobs), n, ptr(ws), need, 0.0, stream()), 'danet_conv_wgrad3x3_multi')
-        if tok is not None:
-            PROFILER.end(tok)
-        _crop_posts(wq)
-        if hold is not None:
-            hold.extend(wq)
-    _WQ[:] = [q for q in _WQ if not mine(q)]
-    for wqg in ([q for q in _WQG if mine(q) and q[-1] is None], [q for q in _WQG if mine(q) and q[-1] is not None]):
-        if not wqg:
-            continue
-        _check_adopted(wqg)
-        jobs = (_lib.WgJob * len(wqg))()
-        for j, (gptr, weight, x, gy, dims, _post) in zip(jobs, wqg):
-            j.x, j.dy, j.dw = x.data_ptr(), gy.data_ptr(), gptr
-            (j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups) = dims
-        n = len(wqg)
-        need = L.danet_conv_wgrad_multi_ws_floats(ctypes.addressof(jobs), n)
-        zfrom = L.danet_conv_wgrad_multi_ws_zero_from(ctypes.addressof(jobs), n)
+
+    def scratch3(jobs, n, device):
+        need = L.danet_conv_wgrad3x3_multi_ws_floats(jobs, n)
+        return torch.empty(need, dtype=torch.float32, device=device), need
+
+    def scratch(jobs, n, device):
+        need = L.danet_conv_wgrad_multi_ws_floats(jobs, n)
         # the leading part (partial sums of the pointwise kernel: ~290 MB of the bench step's 377 MB) needs no zeroing: only the packed
         # accumulators behind it come out of the zeroed arena when the two can be adjacent -- else a buffer of its own, tail zeroed
-        ws = _wgrad_scratch(need, zfrom, wqg[0][2].device)
-        tok = PROFILER.begin('conv_wgrad_multi', sum(2.0 * d[0] * d[4] * d[5] * d[6] * (d[3] // d[12]) * d[7] * d[8] for d in (q[4] for q in wqg)),
-                             ('wgrad-multi', n)) if PROFILER is not None else None
-        check(L.danet_conv_wgrad_multi(ctypes.addressof(jobs), n, ptr(ws), need, 0.0, stream()), 'danet_conv_wgrad_multi')
-        if tok is not None:
-            PROFILER.end(tok)
-        _crop_posts(wqg)
-        if hold is not None:
-            hold.extend(wqg)
-    _WQG[:] = [q for q in _WQG if not mine(q)]
+        return _wgrad_scratch(need, L.danet_conv_wgrad_multi_ws_zero_from(jobs, n), device), need
+
+    _flush_queue(_WQ, mine, hold, 'conv_wgrad3x3_multi', _lib.Wg3Job, _fill_wg3, scratch3, L.danet_conv_wgrad3x3_multi)
+    _flush_queue(_WQG, mine, hold, 'conv_wgrad_multi', _lib.WgJob, _fill_wg, scratch, L.danet_conv_wgrad_multi)
 
 
 def _crop_posts(queue):
     """The channel-padded layers of a flushed queue: their gradients, computed at the padded widths, are cropped into the tensors autograd
     holds as .grad (one launch per 16 layers)."""
-    posts = [(q[-1], q[1].grad) for q in queue if q[-1] is not None]          # (.grad IS the tensor returned from the backward node: _check_adopted)
+    posts = [(q.post, q.weight.grad) for q in queue if q.post is not None]          # (.grad IS the tensor returned from the backward node: _check_adopted)
     if posts:
         from .glue import crop_into
         crop_into([p[0] for p, _ in posts], [p[2] for p, _ in posts], [p[3] for p, _ in posts], [g for _, g in posts])
@@ -812,12 +830,11 @@ def _enqueue_wgrad(gptr, weight, x, gy, B, H, W, Cin, OH, OW, Cout, R, S, stride
         return False
     if L.danet_conv_wgrad_rows_ok(B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups):
         return False
-    if USE_WGRAD3X3 and (L.danet_conv_wgrad3x3_ok(H, W, Cin, Cout, R, S, stride, pad, dil, groups) or
-                         L.danet_conv_wgrad3x3_pair_ok(B, H, W, Cin, Cout, R, S, stride, pad, dil, groups)):      # (4 x 4 maps: two images per chunk)
-        # only the ADDRESS of the target is kept: holding the tensor would make autograd clone it instead of adopting it as .grad
-        _WQ.append((gptr, weight, x, gy, B, H, W, Cin, Cout, groups, stride, post))      # x, gy stay alive until the flush
-    else:
-        _WQG.append((gptr, weight, x, gy, (B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups), post))
+    w3 = USE_WGRAD3X3 and (L.danet_conv_wgrad3x3_ok(H, W, Cin, Cout, R, S, stride, pad, dil, groups) or
+                           L.danet_conv_wgrad3x3_pair_ok(B, H, W, Cin, Cout, R, S, stride, pad, dil, groups))      # (4 x 4 maps: two images per chunk)
+    queue = _WQ if w3 else _WQG
+    # only the ADDRESS of the target is kept: holding the tensor would make autograd clone it instead of adopting it as .grad
+    queue.append(WgradJob(gptr, weight, x, gy, (B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups), post))      # x, gy stay alive until the flush
     return True
 
 
@@ -835,12 +852,9 @@ def _wgrad_into(gw, x, gy, B, H, W, Cin, OH, OW, Cout, Cin_g, R, S, stride, pad,
         # the regressor ResNets' 7x7 stride-2 stems over the 768 part crops: a chip-filling launch of its own, never queued
         nws = L.danet_conv_wgrad_rows_ws_floats(B, OH, OW, Cin, Cout, R, S, groups)
         ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-        tok = PROFILER.begin('conv_wgrad_rows_kernel', 2.0 * B * OH * OW * Cout * Cin_g * R * S,
-                             ('wgrad', B, H, W, Cin, Cout, R, stride, groups)) if PROFILER is not None else None
-        check(L.danet_conv_wgrad_rows(ptr(x.permute(0, 2, 3, 1)), ptr(gy.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), nws,
-                                      B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, groups, 0.0, stream()), 'danet_conv_wgrad_rows')
-        if tok is not None:
-            PROFILER.end(tok)
+        with _timed('conv_wgrad_rows_kernel', 2.0 * B * OH * OW * Cout * Cin_g * R * S, ('wgrad', B, H, W, Cin, Cout, R, stride, groups)):
+            check(L.danet_conv_wgrad_rows(ptr(x.permute(0, 2, 3, 1)), ptr(gy.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), nws,
+                                          B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, groups, 0.0, stream()), 'danet_conv_wgrad_rows')
         return
     if _enqueue_wgrad(gw.data_ptr(), weight, x, gy, B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups):
         return
@@ -865,17 +879,14 @@ def _wgrad_into(gw, x, gy, B, H, W, Cin, OH, OW, Cout, Cin_g, R, S, stride, pad,
     ws_zero = ws is not None
     if ws is None:
         ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-    tok = None
-    if PROFILER is not None:
+
+    def name():
         kid = L.danet_conv_wgrad_kernel_id(Cin, Cout, groups, R * S)
-        tok = PROFILER.begin('conv_wgrad_kernel<%d, %d, %d>' % (kid // 100, (kid // 10) % 10, kid % 10),
-                             2.0 * B * OH * OW * Cout * Cin_g * R * S,
-                             ('wgrad', B, H, W, Cin, Cout, R, stride, groups))
-    check(L.danet_conv_wgrad(ptr(x.permute(0, 2, 3, 1)), ptr(gy.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), nws,
-                             B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups, 0.0, int(ws_zero), stream()),
-          'danet_conv_wgrad')
-    if tok is not None:
-        PROFILER.end(tok)
+        return 'conv_wgrad_kernel<%d, %d, %d>' % (kid // 100, (kid // 10) % 10, kid % 10)
+    with _timed(name, 2.0 * B * OH * OW * Cout * Cin_g * R * S, ('wgrad', B, H, W, Cin, Cout, R, stride, groups)):
+        check(L.danet_conv_wgrad(ptr(x.permute(0, 2, 3, 1)), ptr(gy.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), nws,
+                                 B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups, 0.0, int(ws_zero), stream()),
+              'danet_conv_wgrad')
 
 
 PACK_IMAGE = bool(int(os.environ.get('DANET_PACK_IMAGE', '1')))      # A-B knob
@@ -894,6 +905,30 @@ def _pad_channels_nhwc(x, mult=8):
     return F.pad(x.permute(0, 2, 3, 1), (0, padc)).permute(0, 3, 1, 2)
 
 
+def channel_padding(x_channels, cin_w, cout, groups):
+    """-> (padc, pad_x, padn): the zero channels a layer runs with so that forward, dgrad and wgrad all take the 16-byte vector path.
+    padc: input channels appended to the weight's cin_w; pad_x: the input tensor needs them appended too (False: its producer already
+    padded it to a multiple of 8, part_ops.part_clean, so only the weight is padded); padn: output channels appended to every group.
+    Grouped layers never pad their input.  A channel count that fits neither rule comes back unpadded, for Conv2dFunction to refuse."""
+    padc, pad_x = 0, False
+    if groups == 1 and x_channels != cin_w and x_channels == cin_w + (-cin_w) % 8:
+        padc = x_channels - cin_w
+    elif groups == 1 and x_channels % 8 != 0:
+        padc, pad_x = (-x_channels) % 8, True
+    return padc, pad_x, (-(cout // groups)) % 8
+
+
+def _crop_group_padding(y, groups, cout_g, padn):
+    """[B, groups * (cout_g + padn), OH, OW] as a convolution at padded output widths wrote it -> the layer's own groups * cout_g channels."""
+    if groups == 1:              # a view: channels stay at the epilogue's padded pixel stride (iuv_ops reads it as it is)
+        yv = y[:, :cout_g]
+        yv._padded_base = y      # (iuv_ops.iuv_global differentiates through the padded tensor itself when it gets this view)
+        return yv
+    B, _, OH, OW = y.shape
+    y = y.permute(0, 2, 3, 1).reshape(B, OH, OW, groups, cout_g + padn)[..., :cout_g]
+    return y.reshape(B, OH, OW, groups * cout_g).permute(0, 3, 1, 2)
+
+
 def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, out_fp32=False, want_stats=False,
            keep_group_padding=False, link=None, weight_pad=None):
     """Convolution on the MFMA kernels.  Channel counts that are not a multiple of 8 (3-channel image,
@@ -907,14 +942,10 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, out_
         Cout, Cin_w = int(weight_pad[0]), int(weight_pad[1])
     else:
         Cout, Cin_w = weight.shape[0], weight.shape[1]
-    padc = 0
-    if groups == 1 and x.shape[1] != Cin_w and x.shape[1] == Cin_w + (-Cin_w) % 8:
-        padc = x.shape[1] - Cin_w        # the producer already zero-padded the channels to a multiple of 8 (part_ops.part_clean): pad the weight only
-    elif groups == 1 and x.shape[1] % 8 != 0:
-        padc = (-x.shape[1]) % 8
+    padc, pad_x, padn = channel_padding(x.shape[1], Cin_w, Cout, groups)
+    if pad_x:
         x = _pad_channels_nhwc(x)
     Cout_g = Cout // groups
-    padn = (-Cout_g) % 8
     wpad = weight_pad
     if padc or padn:
         if weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous() and weight_pad is None:
@@ -936,19 +967,10 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, out_
         y = Conv2dFunction.apply(x, weight, bias, stride, padding, dilation, groups, out_fp32, None, None, None, wpad)
         if keep_group_padding:       # [B, groups*(Cout_g+padn), OH, OW]: the caller consumes the padded layout (part_ops)
             return y
-        if groups == 1:              # a view: channels stay at the epilogue's padded pixel stride (iuv_ops reads it as it is)
-            yv = y[:, :Cout]
-            yv._padded_base = y      # (iuv_ops.iuv_global differentiates through the padded tensor itself when it gets this view)
-            return yv
-        B, _, OH, OW = y.shape
-        y = y.permute(0, 2, 3, 1).reshape(B, OH, OW, groups, Cout_g + padn)[..., :Cout_g]
-        return y.reshape(B, OH, OW, Cout).permute(0, 3, 1, 2)
+        return _crop_group_padding(y, groups, Cout_g, padn)
     sums = None
     if FUSE_BN_STATS and want_stats and bias is None and not out_fp32:
-        n = _lib.lib().danet_bn_ws_floats(Cout)
-        sums = ARENA.alloc(n)
-        if sums is None:
-            sums = torch.zeros(n, dtype=torch.float32, device=x.device)
+        sums = ARENA.zeros(_lib.lib().danet_bn_ws_floats(Cout), x.device)
     # the BatchNorm that produced x (if any) leaves its tensors on x: the data gradient then also reduces that
     # BatchNorm's backward sums (saves one pass over dy, x, y per BatchNorm with a single consumer)
     bn_ctx = getattr(x, '_bn_ctx', None) if (FUSE_BN_BWD_REDUCE and torch.is_grad_enabled()) else None
@@ -973,33 +995,27 @@ BN_GATE_MODES = bool(int(os.environ.get('DANET_BN_GATE_MODES', '1')))    # A/B k
 
 def _bn_gate(bn_ctx, x, c3):
     """Where a fused BatchNorm-backward reduction takes that BatchNorm's ReLU gate from: (tensor or None, bn_gate).
-    bn_ctx = (bn_x, relu, saved, mask, mask_mode) as left on the BatchNorm's output by nn.BatchNorm2d; x is that
-    output (the conv's input).  The LDS-tile 3x3 kernel reads the byte mask (1 byte instead of 8 per lane); the gather
-    kernel reads the output."""
-    relu = bn_ctx[1]
-    mask, mode = (bn_ctx[3], bn_ctx[4]) if len(bn_ctx) > 3 else (None, 0)
-    if not relu:
+    bn_ctx = the BnCtx left on the BatchNorm's output by nn.BatchNorm2d; x is that output (the conv's input).  The LDS-tile
+    3x3 kernel reads the byte mask (1 byte instead of 8 per lane); the gather kernel reads the output."""
+    if not bn_ctx.relu:
         return None, 0
-    if c3 and BN_GATE_MODES and mask is not None:
-        return mask, 2
+    if c3 and BN_GATE_MODES and bn_ctx.mask is not None:
+        return bn_ctx.mask, 2
     return x, 0
 
 
+def _job_geometry(job, dims, transposed):
+    (job.B, job.H, job.W, job.Cin, job.OH, job.OW, job.Cout, job.R, job.S, job.stride, job.pad, job.dil, job.groups) = dims
+    job.transposed = int(transposed)
+
+
 def _conv_job(job, x, wp, y, dims, transposed, bn_sums=None, bn_bwd=None, addend=None):
-    (B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups) = dims
     stream_tables(x.device)
     job.x, job.wp, job.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
     job.bn_sums = None if bn_sums is None else bn_sums.data_ptr()
     job.addend = None if addend is None else addend.data_ptr()
-    if bn_bwd is None:
-        job.bn_x = job.bn_y = job.bn_saved = job.bn_red = None
-        job.bn_gate = 0
-    else:
-        job.bn_gate = bn_bwd[4]
-        job.bn_x, job.bn_y = bn_bwd[0].data_ptr(), None if bn_bwd[1] is None else bn_bwd[1].data_ptr()
-        job.bn_saved, job.bn_red = bn_bwd[2].data_ptr(), bn_bwd[3].data_ptr()
-    (job.B, job.H, job.W, job.Cin, job.OH, job.OW, job.Cout, job.R, job.S, job.stride, job.pad, job.dil, job.groups) = dims
-    job.transposed = int(transposed)
+    job.bn_x, job.bn_y, job.bn_saved, job.bn_red, job.bn_gate = _bn_bwd_ptrs(bn_bwd)
+    _job_geometry(job, dims, transposed)
 
 
 class MultiConvFunction(torch.autograd.Function):
@@ -1025,18 +1041,12 @@ class MultiConvFunction(torch.autograd.Function):
             dims = (B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups)
             wp = pack_weight(ws[i], groups, 0)
             y = _empty_nhwc(B, Cout, OH, OW, torch.bfloat16, xs[i].device)
-            sums = None
-            if want_stats and FUSE_BN_STATS:
-                nfl = L.danet_bn_ws_floats(Cout)
-                sums = ARENA.alloc(nfl)
-                if sums is None:
-                    sums = torch.zeros(nfl, dtype=torch.float32, device=y.device)
+            sums = ARENA.zeros(L.danet_bn_ws_floats(Cout), y.device) if (want_stats and FUSE_BN_STATS) else None
             _conv_job(jobs[i], xs[i], wp, y, dims, False, sums)
             ys.append(y); sums_l.append(sums); dims_l.append(dims); keep.append(wp)
         tok = None
         if PROFILER is not None:
-            tok = PROFILER.begin(_multi_kernel_name(jobs, n, dims_l[0][6] // dims_l[0][12]),
-                                 sum(2.0 * d[0] * d[4] * d[5] * d[6] * (d[3] // d[12]) * d[7] * d[8] for d in dims_l), ('fwd-multi', n))
+            tok = PROFILER.begin(_multi_kernel_name(jobs, n, dims_l[0][6] // dims_l[0][12]), sum(_flops(d) for d in dims_l), ('fwd-multi', n))
         done = None
         if bn is not None and all(s_ is not None for s_ in sums_l):
             # conv -> BatchNorm (+ residual) (+ ReLU) in ONE launch when the streamed 3x3 kernel takes the set (csrc/conv3x3s.hip
@@ -1113,14 +1123,9 @@ class MultiConvFunction(torch.autograd.Function):
                 wp1 = pack_weight(ws[i], groups, 1)
                 gx = _empty_nhwc(B, Cin, H, W, torch.bfloat16, xs[i].device)
                 bn_bwd = None
-                if FUSE_BN_BWD_REDUCE and bn_ctxs[i] is not None and bn_ctxs[i][0].shape == xs[i].shape:
-                    bn_x, saved = bn_ctxs[i][0], bn_ctxs[i][2]
-                    nfl = L.danet_bn_ws_floats(Cin)
-                    red = ARENA.alloc(nfl)
-                    if red is None:
-                        red = torch.zeros(nfl, dtype=torch.float32, device=gx.device)
+                if FUSE_BN_BWD_REDUCE and bn_ctxs[i] is not None and bn_ctxs[i].x.shape == xs[i].shape:
                     gate_t, gate = _bn_gate(bn_ctxs[i], xs[i], True)       # as for the LDS-tile 3x3 kernel; revised below if not
-                    bn_bwd = (bn_x, gate_t, saved, red, gate)
+                    bn_bwd = BnBwd(bn_ctxs[i].x, gate_t, bn_ctxs[i].saved, ARENA.zeros(L.danet_bn_ws_floats(Cin), gx.device), gate)
                 addend = None
                 if links is not None and links[i] is not None and links[i].dres is not None:
                     addend, links[i].dres = links[i].dres, None
@@ -1130,7 +1135,7 @@ class MultiConvFunction(torch.autograd.Function):
                 # data gradient = the transposed gather: roles of (H, W, Cin) and (OH, OW, Cout) swap
                 _conv_job(jobs[k], gys[i], wp1, gx, (B, OH, OW, Cout, H, W, Cin, R, S, stride, pad, dil, groups), True, None, bn_bwd, addend)
                 gxs[i] = gx
-                reds.append(None if bn_bwd is None else bn_bwd[3])
+                reds.append(None if bn_bwd is None else bn_bwd.red)
                 keep.append(wp1)
             ok = L.danet_conv_forward_multi_ok(ctypes.addressof(jobs), len(need))
             if ok != 2 and any(j.bn_gate for j in jobs):      # not the LDS-tile 3x3 kernel: its gate modes do not apply
@@ -1139,14 +1144,9 @@ class MultiConvFunction(torch.autograd.Function):
                         jobs[k].bn_y, jobs[k].bn_gate = xs[i].data_ptr(), 0
                 ok = L.danet_conv_forward_multi_ok(ctypes.addressof(jobs), len(need))
             if ok:
-                tok = None
-                if PROFILER is not None:
-                    dd = [dims_l[i] for i in need]
-                    tok = PROFILER.begin(_multi_kernel_name(jobs, len(need), dd[0][3] // dd[0][12]),
-                                         sum(2.0 * d[0] * d[4] * d[5] * d[6] * (d[3] // d[12]) * d[7] * d[8] for d in dd), ('dgrad-multi', len(need)))
-                check(L.danet_conv_forward_multi(ctypes.addressof(jobs), len(need), stream()), 'danet_conv_forward_multi')
-                if tok is not None:
-                    PROFILER.end(tok)
+                dd = [dims_l[i] for i in need]
+                with _timed(lambda: _multi_kernel_name(jobs, len(need), dd[0][3] // dd[0][12]), lambda: sum(_flops(d) for d in dd), ('dgrad-multi', len(need))):
+                    check(L.danet_conv_forward_multi(ctypes.addressof(jobs), len(need), stream()), 'danet_conv_forward_multi')
                 for k, i in enumerate(need):
                     if reds[k] is not None:
                         gxs[i]._bn_red = reds[k]
@@ -1171,14 +1171,9 @@ class MultiConvFunction(torch.autograd.Function):
                         sj = (_lib.ConvJob * len(sub))(*[jobs[k] for k in sub])
                         if L.danet_conv_forward_multi_ok(ctypes.addressof(sj), len(sub)) != 1:
                             continue
-                        tok = None
-                        if PROFILER is not None:
-                            dd = [dims_l[need[k]] for k in sub]
-                            tok = PROFILER.begin(_multi_kernel_name(sj, len(sub), dd[0][3] // dd[0][12]),
-                                                 sum(2.0 * d[0] * d[4] * d[5] * d[6] * (d[3] // d[12]) * d[7] * d[8] for d in dd), ('dgrad-multi', len(sub)))
-                        check(L.danet_conv_forward_multi(ctypes.addressof(sj), len(sub), stream()), 'danet_conv_forward_multi')
-                        if tok is not None:
-                            PROFILER.end(tok)
+                        dd = [dims_l[need[k]] for k in sub]
+                        with _timed(lambda: _multi_kernel_name(sj, len(sub), dd[0][3] // dd[0][12]), lambda: sum(_flops(d) for d in dd), ('dgrad-multi', len(sub))):
+                            check(L.danet_conv_forward_multi(ctypes.addressof(sj), len(sub), stream()), 'danet_conv_forward_multi')
                         FUSION['dgrad_subset_multi'] += len(sub)
                         for k in sub:
                             left.remove(k)
@@ -1216,8 +1211,7 @@ def multi_conv(convs, xs, links=None, bn=None):
                 ok = False
                 break
             st, pd, dl = c.stride[0], c.padding[0], c.dilation[0]
-            (j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups, j.transposed) = \
-                (B, H, W, Cin, conv_out_size(H, R, st, pd, dl), conv_out_size(W, S, st, pd, dl), Cout, R, S, st, pd, dl, c.groups, 0)
+            _job_geometry(j, (B, H, W, Cin, conv_out_size(H, R, st, pd, dl), conv_out_size(W, S, st, pd, dl), Cout, R, S, st, pd, dl, c.groups), False)
         ok = ok and bool(L.danet_conv_forward_multi_ok(ctypes.addressof(jobs), n))
     if not ok:
         return [c(x, link=None if links is None else links[i]) for i, (c, x) in enumerate(zip(convs, xs))]

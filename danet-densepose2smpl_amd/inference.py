@@ -198,17 +198,12 @@ class _FoldedConv(tnn.Module):
         return _nn.sum_relu([y], [0], True) if relu else y
 
     def _widths(self, x):
-        """(x as the kernels take it, padc, Cout padded, Cin_g padded) -- conv.conv2d's channel padding rules."""
-        g = self.groups
+        """(x as the kernels take it, padc, padn, Cout padded, Cin_g padded) by conv.channel_padding, the rule conv2d pads by."""
         Cout, Cin_w = self.w.shape[0], self.w.shape[1]
-        padc = 0
-        if g == 1 and x.shape[1] != Cin_w and x.shape[1] == Cin_w + (-Cin_w) % 8:
-            padc = x.shape[1] - Cin_w
-        elif g == 1 and x.shape[1] % 8 != 0:
-            padc = (-x.shape[1]) % 8
+        padc, pad_x, padn = _conv.channel_padding(x.shape[1], Cin_w, Cout, self.groups)
+        if pad_x:
             x = _conv._pad_channels_nhwc(x)
-        padn = (-(Cout // g)) % 8
-        return nhwc_bf16(x), padc, padn, g * (Cout // g + padn), Cin_w + padc
+        return nhwc_bf16(x), padc, padn, self.groups * (Cout // self.groups + padn), Cin_w + padc
 
     def _run_bf16(self, x, res, relu):
         L = _lib.lib()
@@ -250,11 +245,7 @@ class _FoldedConv(tnn.Module):
                                 relu and (res is None or fuse_res), False, addend=add)
         self.engine.launches['conv'] += 1
         if padn:
-            if g == 1:
-                y = y[:, :Cout_p - padn]
-            else:
-                y = y.permute(0, 2, 3, 1).reshape(B, OH, OW, g, Cout_p // g)[..., :Cout_p // g - padn]
-                y = y.reshape(B, OH, OW, -1).permute(0, 3, 1, 2)
+            y = _conv._crop_group_padding(y, g, Cout_p // g - padn, padn)
         if res is not None and not fuse_res:
             self.engine.launches['sum_relu'] += 1
             y = _nn.sum_relu([y, res], [0, 0], relu)
@@ -274,13 +265,7 @@ class _FoldedConv(tnn.Module):
         wp, b = self._packed(('g', 0), Cout_p, Cin_gp, 0, 0)
         y = _empty_nhwc(B, Cout_p, OH, OW, torch.bfloat16, x.device)
         add = None if res is None else nhwc_bf16(res)
-        _conv.stream_tables(x.device)
-        j = job.j
-        j.x, j.wp, j.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
-        j.bn_sums = j.bn_x = j.bn_y = j.bn_saved = j.bn_red = None
-        j.addend = None if add is None else add.data_ptr()
-        (j.B, j.H, j.W, j.Cin, j.OH, j.OW, j.Cout, j.R, j.S, j.stride, j.pad, j.dil, j.groups, j.transposed, j.bn_gate) = \
-            (B, H, W, Cin, OH, OW, Cout_p, self.R, self.S, self.stride, self.pad, self.dil, self.groups, 0, 0)
+        _conv._conv_job(job.j, x, wp, y, (B, H, W, Cin, OH, OW, Cout_p, self.R, self.S, self.stride, self.pad, self.dil, self.groups), False, addend=add)
         job.bias, job.relu = b.data_ptr(), int(relu)
         return (y, x, wp, b, add)          # (keeps the operands alive until the launch is queued)
 

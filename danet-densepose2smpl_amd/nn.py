@@ -195,7 +195,7 @@ class BatchNormActFunction(torch.autograd.Function):
             _conv.TRACE.append(('bn', tuple(x.shape), y.float().abs().mean()))
         if training:
             # lets a consumer conv fuse this BN's backward reduction (no reference to y: no cycle)
-            y._bn_ctx = (x, bool(relu), saved, mask, ctx.mask_mode)
+            y._bn_ctx = _conv.BnCtx(x, bool(relu), saved, mask, ctx.mask_mode)
         return y
 
     @staticmethod
@@ -342,9 +342,7 @@ class MultiBatchNormFunction(torch.autograd.Function):
             saved = torch.empty(2, C, dtype=torch.float32, device=xs[i].device)
             sums, state = fused[i], 2
             if sums is None:
-                sums, state = ARENA.alloc(L.danet_bn_ws_floats(C)), 1
-                if sums is None:
-                    sums = torch.zeros(L.danet_bn_ws_floats(C), dtype=torch.float32, device=xs[i].device)
+                sums, state = ARENA.zeros(L.danet_bn_ws_floats(C), xs[i].device), 1
             keep.append(sums)
             mask = torch.empty(B * H * W * C // 4, dtype=torch.uint8, device=xs[i].device) \
                 if (relus[i] and RELU_MASK and (ress[i] is not None or _conv.FUSE_BN_BWD_REDUCE)) else None
@@ -365,7 +363,7 @@ class MultiBatchNormFunction(torch.autograd.Function):
         ctx.save_for_backward(*xs, *[y if (rl and md == 0) else None for y, md, rl in zip(ys, modes, relus)], *gammas, *saveds, *betas, *masks)
         ctx.cfg = (n, relus, [r is not None for r in ress], links, modes)
         for y, x, saved, mask, md, rl in zip(ys, xs, saveds, masks, modes, relus):
-            y._bn_ctx = (x, bool(rl), saved, mask, md)
+            y._bn_ctx = _conv.BnCtx(x, bool(rl), saved, mask, md)
         return tuple(ys)
 
     @staticmethod
@@ -383,9 +381,7 @@ class MultiBatchNormFunction(torch.autograd.Function):
             _conv.FUSION['bn_bwd_reduce_fused' if red is not None else 'bn_bwd_reduce_own'] += 1
             state = 2
             if red is None:
-                red, state = ARENA.alloc(L.danet_bn_ws_floats(C)), 1
-                if red is None:
-                    red = torch.zeros(L.danet_bn_ws_floats(C), dtype=torch.float32, device=xs[i].device)
+                red, state = ARENA.zeros(L.danet_bn_ws_floats(C), xs[i].device), 1
             gy = nhwc_as(gys[i], dt)
             dx = _empty_nhwc(B, C, H, W, dt, xs[i].device)
             dres = _empty_nhwc(B, C, H, W, dt, xs[i].device) if has_res[i] else None

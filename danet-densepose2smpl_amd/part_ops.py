@@ -83,9 +83,7 @@ class PartLossFunction(torch.autograd.Function):
         ctx.cpj = _cpj(C)
         if img.shape != (B, 3, H, W) or th.shape != (B, NJ, 2, 3) or sel.shape != (NJ, 6):
             raise ValueError('part_losses: bad shapes %s %s %s' % (tuple(img.shape), tuple(th.shape), tuple(sel.shape)))
-        sums = ARENA.alloc(32 * 3 * 2)              # [32][3] doubles: exact, order-independent adds of the workgroups' partial sums
-        if sums is None:
-            sums = torch.zeros(32 * 3 * 2, dtype=torch.float32, device=pred.device)
+        sums = ARENA.zeros(32 * 3 * 2, pred.device)              # [32][3] doubles: exact, order-independent adds of the workgroups' partial sums
         check(_lib.lib().danet_part_loss_forward(ptr(pred.permute(0, 2, 3, 1)), ptr(img), ptr(th), ptr(w), ptr(sel), B, H, W, int(align), ctx.cpj,
                                                  ptr(sums), stream()), 'danet_part_loss_forward')
         ctx.save_for_backward(pred, img, th, w, sel)
@@ -148,9 +146,7 @@ class PartJointFunction(torch.autograd.Function):
         sel = sel.to(torch.int32).contiguous()
         if img.shape != (B, 3, H, W) or th.shape != (B, NJ, 2, 3) or sel.shape != (NJ, 6):
             raise ValueError('part_joint: bad shapes %s %s %s' % (tuple(img.shape), tuple(th.shape), tuple(sel.shape)))
-        sums = ARENA.alloc(32 * 3 * 2)
-        if sums is None:
-            sums = torch.zeros(32 * 3 * 2, dtype=torch.float32, device=pred.device)
+        sums = ARENA.zeros(32 * 3 * 2, pred.device)
         check(L.danet_part_loss_forward(ptr(pred.permute(0, 2, 3, 1)), ptr(img), ptr(th), ptr(w), ptr(sel), B, H, W, int(align), cpj, ptr(sums), stream()),
               'danet_part_loss_forward')
         out = loss_finalize(3, scales, w, B, sums=sums, rows=32)

@@ -441,3 +441,23 @@ def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
     assert again == written
     for n in written:
         np.testing.assert_array_equal(np.load(str(tmp_path / 'b' / (n + '.npy'))), arrays[n])
+
+
+def test_channel_padding_rule_is_one_function():
+    """conv.channel_padding(x channels, weight Cin, Cout, groups) -> (padc, pad_x, padn) for the layer kinds of the network, and the
+    inference engine's folded layers take their widths from it instead of restating the rule."""
+    import inspect
+    from danet_densepose2smpl_amd import conv, inference
+    cases = [((3, 3, 64, 1), (5, True, 0)),            # image stem
+             ((24, 21, 64, 1), (3, False, 0)),         # the producer already padded (part_ops.part_clean): weight only
+             ((256, 256, 25, 1), (0, False, 7)),       # 25-channel head
+             ((64, 64, 64, 1), (0, False, 0)),         # plain
+             ((1152, 48, 72, 24), (0, False, 5)),      # 24-group partial-IUV head: 3 outputs per group
+             ((21, 7, 21, 3), (0, False, 1)),          # grouped: the input is never padded
+             ((16, 12, 8, 1), (4, False, 0)),          # 12 + 4 = 16: weight padded only
+             ((32, 12, 8, 1), (0, False, 0))]          # a mismatch that is no padding: left to Conv2dFunction's ValueError
+    for args, want in cases:
+        got = conv.channel_padding(*args)
+        assert tuple(got) == want and isinstance(got[1], bool), (args, got, want)
+    src = inspect.getsource(inference._FoldedConv._widths)
+    assert 'channel_padding(' in src and '% 8' not in src, src

@@ -23,8 +23,9 @@ seen = []
 
 def spy(*a, **k):
     if conv._WQ or conv._WQG:
-        seen.append(([(q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[-1] is not None) for q in conv._WQ],
-                     [tuple(q[4]) + (q[-1] is not None,) for q in conv._WQG]))
+        # (3x3 queue: B, H, W, Cin, Cout, groups, stride of the 13 dims)
+        seen.append(([tuple(q.dims[i] for i in (0, 1, 2, 3, 6, 12, 9)) + (q.post is not None,) for q in conv._WQ],
+                     [tuple(q.dims) + (q.post is not None,) for q in conv._WQG]))
     return orig(*a, **k)
 
 

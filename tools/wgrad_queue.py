@@ -22,20 +22,19 @@ flops = collections.Counter()
 orig = conv.flush_wgrads
 
 
-def spy(bucket=None):
+def spy(bucket=None, **kw):
     for q in conv._WQ:
-        (gptr, weight, x, gy, B_, H, W, Cin, Cout, groups, stride_) = q
+        B_, H, W, Cin, _, _, Cout, _, _, _, _, _, groups = q.dims
         k = ('w3x3', B_, H, W, Cin, Cout, groups)
-        if (id(weight), bucket) not in spy.done:
+        if (id(q.weight), bucket) not in spy.done:
             seen[k] += 1; flops[k] += 2.0 * B_ * H * W * Cout * (Cin // groups) * 9
-            spy.done.add((id(weight), bucket))
+            spy.done.add((id(q.weight), bucket))
     for q in conv._WQG:
-        (gptr, weight, x, gy, d) = q
-        k = ('generic',) + tuple(d)
-        if (id(weight), 'g') not in spy.done:
-            seen[k] += 1; flops[k] += 2.0 * d[0] * d[4] * d[5] * d[6] * (d[3] // d[12]) * d[7] * d[8]
-            spy.done.add((id(weight), 'g'))
-    return orig(bucket)
+        k = ('generic',) + tuple(q.dims)
+        if (id(q.weight), 'g') not in spy.done:
+            seen[k] += 1; flops[k] += conv._flops(q.dims)
+            spy.done.add((id(q.weight), 'g'))
+    return orig(bucket, **kw)
 
 
 spy.done = set()
