@@ -1,0 +1,363 @@
+// Scoring ops of the evaluation pipeline for gfx950 (the reference's eval.py; evaluate.py is the caller).
+//
+//   pose_eval           eval.py:183-216 + utils/pose_utils.py:10-58 as one launch, one workgroup per sample: the 17 x V joint
+//                       regression as a block reduction (every lane walks vertices tid, tid + 256, ...: the regressor rows and the
+//                       vertices are read as consecutive words by consecutive lanes; the regressor stays in L2 across workgroups),
+//                       then one lane centres, maps, takes the MPJPE and solves the Procrustes problem in fp64: Jacobi on the
+//                       symmetric K^T K gives V and the order of the singular values, U follows from K V, and the last singular
+//                       pair takes the sign that makes det R = +1 (the reference's Z).  HBM / latency bound, no MFMA.
+//   seg_confusion       eval.py:222-266 for a batch as one launch: one lane per label pixel looks its predicted value up through
+//                       the paste rectangle and the two nearest-neighbour index tables of the uncrop rule, so no
+//                       uncropped image exists.  Counts are wave ballots + popcounts kept in wave-uniform registers over the
+//                       block's pixel chunk, then one LDS atomic per counter and wave, then one global atomic per counter and
+//                       block.  All sums are integers: the result does not depend on the order.
+//   rotmat_to_angle_axis  the inverse of batch_rodrigues under the rule of DESIGN.md ("axis-angle rule"), one lane per matrix.
+#include "common.h"
+
+namespace {
+
+constexpr int kNJ = 17;                 // rows of the H36M joint regressor
+constexpr int kPoseThreads = 256;
+
+struct Mapper { int idx[kNJ]; };
+
+// sum over the 256 lanes of a block; the result is valid in lane 0 of wave 0.  `red` holds 4 doubles per value.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+__device__ void regress17(const float* __restrict__ verts, const float* __restrict__ Jr, int V, double* __restrict__ red /* [4][51] */,
+                          float* __restrict__ out /* LDS [51] */)
+{
+    float acc[kNJ * 3];
+#pragma unroll
+    for (int k = 0; k < kNJ * 3; ++k) acc[k] = 0.0f;
+    for (int v = threadIdx.x; v < V; v += kPoseThreads) {
+        const float x = verts[v * 3 + 0], y = verts[v * 3 + 1], z = verts[v * 3 + 2];
+#pragma unroll
+        for (int j = 0; j < kNJ; ++j) {
+            const float w = Jr[(size_t)j * V + v];
+            acc[j * 3 + 0] += w * x;
+            acc[j * 3 + 1] += w * y;
+            acc[j * 3 + 2] += w * z;
+        }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < kNJ * 3; ++k) {
+        const double s = wave_sum((double)acc[k]);
+        if (lane == 0) red[wave * (kNJ * 3) + k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < kNJ * 3) {
+        const int k = threadIdx.x;
+        out[k] = (float)(red[k] + red[kNJ * 3 + k] + red[2 * kNJ * 3 + k] + red[3 * kNJ * 3 + k]);
+    }
+    __syncthreads();
+}
+
+// eigenvectors of the symmetric 3 x 3 matrix A (destroyed) by cyclic Jacobi rotations: A -> diagonal, E -> columns
+__device__ void jacobi3(double A[3][3], double E[3][3]) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) E[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+        const double diag = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+        if (off <= 1e-30 * diag || off == 0.0) break;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (A[p][q] == 0.0) continue;
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 3; ++k) {                       // A <- A G
+                    const double akp = A[k][p], akq = A[k][q];
+                    A[k][p] = c * akp - s * akq;
+                    A[k][q] = s * akp + c * akq;
+                }
+                for (int k = 0; k < 3; ++k) {                       // A <- G^T A
+                    const double apk = A[p][k], aqk = A[q][k];
+                    A[p][k] = c * apk - s * aqk;
+                    A[q][k] = s * apk + c * aqk;
+                }
+                for (int k = 0; k < 3; ++k) {
+                    const double ekp = E[k][p], ekq = E[k][q];
+                    E[k][p] = c * ekp - s * ekq;
+                    E[k][q] = s * ekp + c * ekq;
+                }
+            }
+    }
+}
+
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+__device__ __forceinline__ bool normalize3(double* a) {
+    const double n = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    if (!(n > 0.0)) return false;
+    a[0] /= n; a[1] /= n; a[2] /= n;
+    return true;
+}
+
+// a unit vector orthogonal to the unit vector a
+__device__ __forceinline__ void any_orthogonal(const double* a, double* o) {
+    const int k = fabs(a[0]) <= fabs(a[1]) ? (fabs(a[0]) <= fabs(a[2]) ? 0 : 2) : (fabs(a[1]) <= fabs(a[2]) ? 1 : 2);
+    double e[3] = {0.0, 0.0, 0.0};
+    e[k] = 1.0;
+    cross3(a, e, o);
+    normalize3(o);
+}
+
+// pose_utils.py:10-58 for S1, S2 [J][3] fp32 (J <= 17): the mean distance between S2 and S1 under the best similarity transform
+__device__ double procrustes_error(const float* __restrict__ S1, const float* __restrict__ S2, int J) {
+    double mu1[3] = {0, 0, 0}, mu2[3] = {0, 0, 0};
+    for (int j = 0; j < J; ++j)
+        for (int k = 0; k < 3; ++k) { mu1[k] += (double)S1[j * 3 + k]; mu2[k] += (double)S2[j * 3 + k]; }
+    for (int k = 0; k < 3; ++k) { mu1[k] /= J; mu2[k] /= J; }
+    double K[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, var1 = 0.0;
+    for (int j = 0; j < J; ++j) {
+        double x1[3], x2[3];
+        for (int k = 0; k < 3; ++k) { x1[k] = (double)S1[j * 3 + k] - mu1[k]; x2[k] = (double)S2[j * 3 + k] - mu2[k]; }
+        for (int a = 0; a < 3; ++a) {
+            var1 += x1[a] * x1[a];
+            for (int b = 0; b < 3; ++b) K[a][b] += x1[a] * x2[b];          // K = X1 X2^T
+        }
+    }
+    // K = U S V^T: V and S^2 from K^T K
+    double A[3][3], E[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) A[a][b] = K[0][a] * K[0][b] + K[1][a] * K[1][b] + K[2][a] * K[2][b];
+    jacobi3(A, E);
+    int o0 = 0, o1 = 1, o2 = 2;                                             // descending eigenvalues
+    if (A[o0][o0] < A[o1][o1]) { const int t = o0; o0 = o1; o1 = t; }
+    if (A[o0][o0] < A[o2][o2]) { const int t = o0; o0 = o2; o2 = t; }
+    if (A[o1][o1] < A[o2][o2]) { const int t = o1; o1 = o2; o2 = t; }
+    double v0[3] = {E[0][o0], E[1][o0], E[2][o0]}, v1[3] = {E[0][o1], E[1][o1], E[2][o1]}, v2[3];
+    cross3(v0, v1, v2);
+    double u0[3], u1[3], u2[3];
+    for (int a = 0; a < 3; ++a) {
+        u0[a] = K[a][0] * v0[0] + K[a][1] * v0[1] + K[a][2] * v0[2];
+        u1[a] = K[a][0] * v1[0] + K[a][1] * v1[1] + K[a][2] * v1[2];
+    }
+    if (!normalize3(u0)) { u0[0] = 1.0; u0[1] = 0.0; u0[2] = 0.0; }          // K = 0: any rotation is optimal
+    const double d = u0[0] * u1[0] + u0[1] * u1[1] + u0[2] * u1[2];
+    for (int a = 0; a < 3; ++a) u1[a] -= d * u0[a];
+    if (!normalize3(u1)) any_orthogonal(u0, u1);                            // rank one
+    cross3(u0, u1, u2);
+    // R = V Z U^T with det R = +1: both triples are right-handed, so the third pair carries the sign of Z
+    double R[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) R[a][b] = v0[a] * u0[b] + v1[a] * u1[b] + v2[a] * u2[b];
+    double tr = 0.0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) tr += R[a][b] * K[b][a];                // trace(R K)
+    const double scale = tr / var1;
+    double t[3];
+    for (int a = 0; a < 3; ++a) t[a] = mu2[a] - scale * (R[a][0] * mu1[0] + R[a][1] * mu1[1] + R[a][2] * mu1[2]);
+    double err = 0.0;
+    for (int j = 0; j < J; ++j) {
+        double e2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double h = scale * (R[a][0] * (double)S1[j * 3 + 0] + R[a][1] * (double)S1[j * 3 + 1] + R[a][2] * (double)S1[j * 3 + 2]) + t[a];
+            const double df = h - (double)S2[j * 3 + a];
+            e2 += df * df;
+        }
+        err += sqrt(e2);
+    }
+    return err / J;
+}
+
+__global__ __launch_bounds__(kPoseThreads) void pose_eval_kernel(
+    const float* __restrict__ pred_vertices, const float* __restrict__ Jr, Mapper mapper, int J,
+    const float* __restrict__ gt_kp, const float* __restrict__ gt_vertices, int V,
+    float* __restrict__ mpjpe, float* __restrict__ recon, float* __restrict__ joints17)
+{
+    __shared__ double red[4 * kNJ * 3];
+    __shared__ float pj[kNJ * 3], gj[kNJ * 3];
+    __shared__ float s1[kNJ * 3], s2[kNJ * 3];
+    const int b = blockIdx.x;
+    regress17(pred_vertices + (size_t)b * V * 3, Jr, V, red, pj);
+    if (threadIdx.x < kNJ * 3) joints17[(size_t)b * kNJ * 3 + threadIdx.x] = pj[threadIdx.x];
+    if (gt_vertices) regress17(gt_vertices + (size_t)b * V * 3, Jr, V, red, gj);
+    if (threadIdx.x < J * 3) {
+        const int j = threadIdx.x / 3, k = threadIdx.x - j * 3;
+        const int m = mapper.idx[j];
+        s1[threadIdx.x] = pj[m * 3 + k] - pj[k];                              // centred on the regressed pelvis (joint 0)
+        s2[threadIdx.x] = gt_vertices ? gj[m * 3 + k] - gj[k] : gt_kp[(size_t)b * J * 3 + threadIdx.x];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double e = 0.0;
+        for (int j = 0; j < J; ++j) {
+            double e2 = 0.0;
+            for (int k = 0; k < 3; ++k) { const double df = (double)s1[j * 3 + k] - (double)s2[j * 3 + k]; e2 += df * df; }
+            e += sqrt(e2);
+        }
+        mpjpe[b] = (float)(e / J);
+        recon[b] = (float)procrustes_error(s1, s2, J);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int kSegThreads = 256;
+constexpr int kSegChunk = 4096;           // label pixels per block
+constexpr int kNC = 32;                   // counters (include/danet_hip.h DANET_SEG_*)
+
+__device__ __forceinline__ int popc(bool p) { return __popcll(__ballot(p)); }
+
+__global__ __launch_bounds__(kSegThreads) void seg_confusion_kernel(
+    const float* __restrict__ mask, const long long* __restrict__ parts,
+    const unsigned char* __restrict__ gt_mask, const unsigned char* __restrict__ gt_parts, long long label_bytes,
+    const long long* __restrict__ offsets, const int* __restrict__ shapes, const int* __restrict__ rects,
+    const int* __restrict__ tables, int table_len, int res, unsigned long long* __restrict__ counters)
+{
+    __shared__ int blk[kNC];
+    const int b = blockIdx.y;
+    const int H = shapes[b * 2 + 0], W = shapes[b * 2 + 1];
+    const long long npix = (long long)H * W;
+    const long long first = (long long)blockIdx.x * kSegChunk;
+    if (first >= npix || H <= 0 || W <= 0) return;                           // (uniform over the block)
+    if (threadIdx.x < kNC) blk[threadIdx.x] = 0;
+    __syncthreads();
+    const long long base = offsets[b];
+    const int y0 = rects[b * 6 + 0], y1 = rects[b * 6 + 1], x0 = rects[b * 6 + 2], x1 = rects[b * 6 + 3];
+    const int* rt = tables + rects[b * 6 + 4];
+    const int* ct = tables + rects[b * 6 + 5];
+    const int rt_room = table_len - rects[b * 6 + 4], ct_room = table_len - rects[b * 6 + 5];
+    int cnt[kNC];                                                            // wave-uniform
+#pragma unroll
+    for (int k = 0; k < kNC; ++k) cnt[k] = 0;
+    for (int it = 0; it < kSegChunk / kSegThreads; ++it) {
+        const long long p = first + it * kSegThreads + threadIdx.x;
+        const bool live = p < npix && base >= 0 && base + p < label_bytes;
+        if (!__any(live)) break;
+        int sy = -1, sx = -1;                                                // source pixel of the rendered images, -1: outside the paste
+        if (live) {
+            const int y = (int)(p / W), x = (int)(p - (long long)y * W);
+            if (y >= y0 && y < y1 && x >= x0 && x < x1 && rects[b * 6 + 4] >= 0 && rects[b * 6 + 5] >= 0 &&
+                y - y0 < rt_room && x - x0 < ct_room) {
+                sy = rt[y - y0];
+                sx = ct[x - x0];
+                if (sy < 0 || sy >= res || sx < 0 || sx >= res) sy = sx = -1;
+            }
+        }
+        const size_t src = (size_t)b * res * res + (sy >= 0 ? sy * res + sx : 0);
+        if (gt_mask) {
+            const bool g = live && gt_mask[base + p] > 0;
+            const bool q = live && sy >= 0 && mask[src] > 0.0f;
+            const int n11 = popc(g && q), n10 = popc(g && !q), n01 = popc(live && !g && q), n00 = popc(live && !g && !q);
+            cnt[DANET_SEG_TP + 0] += n00; cnt[DANET_SEG_FP + 0] += n10; cnt[DANET_SEG_FN + 0] += n01;
+            cnt[DANET_SEG_TP + 1] += n11; cnt[DANET_SEG_FP + 1] += n01; cnt[DANET_SEG_FN + 1] += n10;
+            cnt[DANET_SEG_ACC] += n00 + n11;
+        }
+        if (gt_parts) {
+            const int g = live ? (int)gt_parts[base + p] : -1;
+            const int q = live ? (sy >= 0 ? (int)(unsigned char)parts[src] : 0) : -2;     // (astype(uint8), as eval.py:250)
+#pragma unroll
+            for (int c = 0; c < 7; ++c) {
+                const bool cg = g == c, cp = q == c && g != 255;
+                cnt[DANET_SEG_PARTS_TP + c] += popc(cg && cp);
+                cnt[DANET_SEG_PARTS_FP + c] += popc(live && !cg && cp);
+                cnt[DANET_SEG_PARTS_FN + c] += popc(cg && !cp);
+            }
+            cnt[DANET_SEG_PARTS_ACC] += popc(live && (g == 255 ? 0 : g) == (q == 255 ? 0 : q));
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kNC; ++k)
+            if (cnt[k]) atomicAdd(&blk[k], cnt[k]);
+    }
+    __syncthreads();
+    if (threadIdx.x < kNC) {
+        unsigned long long v = (unsigned long long)blk[threadIdx.x];
+        if (blockIdx.x == 0) {                                               // the image's size once per sample
+            if (threadIdx.x == DANET_SEG_PIXELS && gt_mask) v = (unsigned long long)npix;
+            if (threadIdx.x == DANET_SEG_PARTS_PIXELS && gt_parts) v = (unsigned long long)npix;
+        }
+        if (v) atomicAdd(&counters[threadIdx.x], v);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ void rotmat_to_angle_axis_kernel(const float* __restrict__ Rm, int N, float* __restrict__ aa) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float* R = Rm + (size_t)i * 9;
+    const float r00 = R[0], r01 = R[1], r02 = R[2], r10 = R[3], r11 = R[4], r12 = R[5], r20 = R[6], r21 = R[7], r22 = R[8];
+    // matrix -> quaternion, the case of the largest of (trace, r00, r11, r22): the square root is taken of a number >= 1
+    float w, x, y, z;
+    const float tr = r00 + r11 + r22;
+    if (tr > 0.0f) {
+        const float s = 2.0f * sqrtf(tr + 1.0f);
+        w = 0.25f * s; x = (r21 - r12) / s; y = (r02 - r20) / s; z = (r10 - r01) / s;
+    } else if (r00 >= r11 && r00 >= r22) {
+        const float s = 2.0f * sqrtf(1.0f + r00 - r11 - r22);
+        w = (r21 - r12) / s; x = 0.25f * s; y = (r01 + r10) / s; z = (r02 + r20) / s;
+    } else if (r11 >= r22) {
+        const float s = 2.0f * sqrtf(1.0f + r11 - r00 - r22);
+        w = (r02 - r20) / s; x = (r01 + r10) / s; y = 0.25f * s; z = (r12 + r21) / s;
+    } else {
+        const float s = 2.0f * sqrtf(1.0f + r22 - r00 - r11);
+        w = (r10 - r01) / s; x = (r02 + r20) / s; y = (r12 + r21) / s; z = 0.25f * s;
+    }
+    if (w < 0.0f) { w = -w; x = -x; y = -y; z = -z; }                        // the angle in [0, pi]
+    // quaternion -> axis-angle: angle = 2 atan2(|xyz|, w), axis = xyz / |xyz|; small angles: 2 xyz / w
+    const float sn = sqrtf(x * x + y * y + z * z);
+    const float k = sn < 1e-6f ? 2.0f / w : 2.0f * atan2f(sn, w) / sn;
+    aa[(size_t)i * 3 + 0] = x * k;
+    aa[(size_t)i * 3 + 1] = y * k;
+    aa[(size_t)i * 3 + 2] = z * k;
+}
+
+}  // namespace
+
+extern "C" int danet_pose_eval(const float* pred_vertices, const float* J_regressor, const int32_t* joint_mapper, int J,
+                               const float* gt_keypoints_3d, const float* gt_vertices, int B, int V,
+                               float* mpjpe, float* recon_err, float* pred_joints17, void* stream)
+{
+    DANET_ENTER();
+    DANET_CHECK_ARG(B > 0 && B < (1 << 24) && V > 0 && V < (1 << 24), "pose_eval: bad sizes B=%d V=%d", B, V);
+    DANET_CHECK_ARG(J >= 3 && J <= kNJ, "pose_eval: %d mapped joints (3..17)", J);
+    DANET_CHECK_ARG(pred_vertices && J_regressor && joint_mapper && mpjpe && recon_err && pred_joints17, "pose_eval: null pointer");
+    DANET_CHECK_ARG((gt_keypoints_3d != nullptr) != (gt_vertices != nullptr), "pose_eval: give exactly one of gt_keypoints_3d / gt_vertices");
+    Mapper m;
+    for (int j = 0; j < kNJ; ++j) m.idx[j] = 0;
+    for (int j = 0; j < J; ++j) {
+        DANET_CHECK_ARG(joint_mapper[j] >= 0 && joint_mapper[j] < kNJ, "pose_eval: joint_mapper[%d] = %d", j, joint_mapper[j]);
+        m.idx[j] = joint_mapper[j];
+    }
+    hipLaunchKernelGGL(pose_eval_kernel, dim3(B), dim3(kPoseThreads), 0, (hipStream_t)stream, pred_vertices, J_regressor, m, J,
+                       gt_keypoints_3d, gt_vertices, V, mpjpe, recon_err, pred_joints17);
+    DANET_CHECK_LAUNCH("pose_eval_kernel");
+    return DANET_OK;
+}
+
+extern "C" int danet_seg_confusion(const float* mask, const int64_t* parts, const uint8_t* gt_mask, const uint8_t* gt_parts,
+                                   int64_t label_bytes, const int64_t* offsets, const int32_t* shapes, const int32_t* rects,
+                                   const int32_t* tables, int table_len, int B, int res, int max_pixels, int64_t* counters, void* stream)
+{
+    DANET_ENTER();
+    DANET_CHECK_ARG(B > 0 && B < 65536 && res > 0 && res <= 4096 && max_pixels > 0 && label_bytes > 0 && table_len > 0,
+                    "seg_confusion: bad sizes B=%d res=%d max_pixels=%d label_bytes=%lld table_len=%d", B, res, max_pixels, (long long)label_bytes, table_len);
+    DANET_CHECK_ARG(mask && parts && offsets && shapes && rects && tables && counters, "seg_confusion: null pointer");
+    DANET_CHECK_ARG(gt_mask || gt_parts, "seg_confusion: no label images");
+    hipLaunchKernelGGL(seg_confusion_kernel, dim3(danet::cdiv(max_pixels, kSegChunk), B), dim3(kSegThreads), 0, (hipStream_t)stream,
+                       mask, (const long long*)parts, gt_mask, gt_parts, (long long)label_bytes, (const long long*)offsets, shapes, rects,
+                       tables, table_len, res, (unsigned long long*)counters);
+    DANET_CHECK_LAUNCH("seg_confusion_kernel");
+    return DANET_OK;
+}
+
+extern "C" int danet_rotmat_to_angle_axis(const float* R, int N, float* angle_axis, void* stream) {
+    DANET_ENTER();
+    DANET_CHECK_ARG(R && angle_axis && N > 0, "rotmat_to_angle_axis: bad arguments");
+    hipLaunchKernelGGL(rotmat_to_angle_axis_kernel, dim3(danet::cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, R, N, angle_axis);
+    DANET_CHECK_LAUNCH("rotmat_to_angle_axis_kernel");
+    return DANET_OK;
+}

@@ -14,6 +14,12 @@ def rot6d_to_rotmat(x):
     return ops.rot6d_to_rotmat(x)
 
 
+def rotmat_to_angle_axis(R):
+    """[N,3,3] -> [N,3], the inverse of batch_rodrigues with the angle in [0, pi] (HIP kernel; the rule is DESIGN.md's "axis-angle
+    rule" -- the reference calls torchgeometry's rotation_matrix_to_angle_axis on [N,3,4], eval.py:176-178)."""
+    return ops.rotmat_to_angle_axis(R)
+
+
 def perspective_projection(points, rotation, translation, focal_length, camera_center):
     """geometry.py:63-91.  rotation may be None (identity, as at every call site of the hot path)."""
     if rotation is not None:

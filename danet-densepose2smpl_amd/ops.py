@@ -286,3 +286,74 @@ class Rot6dFunction(torch.autograd.Function):
 def rot6d_to_rotmat(x):
     """/root/reference/utils/geometry.py:47-61."""
     return Rot6dFunction.apply(x)
+
+
+def rotmat_to_angle_axis(R):
+    """[..., 3, 3] rotation matrices -> [N, 3] axis-angle vectors with the angle in [0, pi] (DESIGN.md "axis-angle rule"): the inverse
+    of batch_rodrigues, where eval.py:175-178 calls tgm.rotation_matrix_to_angle_axis.  Forward only."""
+    L = _lib.lib()
+    Rc = _f32c(_dev_tensor(R, 'rotmat_to_angle_axis')).view(-1, 3, 3)
+    aa = torch.empty(Rc.shape[0], 3, device=Rc.device, dtype=torch.float32)
+    check(L.danet_rotmat_to_angle_axis(ptr(Rc), Rc.shape[0], ptr(aa), stream()), 'danet_rotmat_to_angle_axis')
+    return aa
+
+
+def pose_eval(pred_vertices, J_regressor, joint_mapper, gt_keypoints_3d=None, gt_vertices=None):
+    """metrics.pose_errors as ONE launch (csrc/eval_ops.hip): pred_vertices [B,V,3], J_regressor [17,V], joint_mapper 3..17 ints
+    (host), exactly one of gt_keypoints_3d [B,J,3] / gt_vertices [B,V,3] -> (mpjpe [B], recon_err [B], pred_joints17 [B,17,3]).
+    Allocates its three outputs and nothing else; capturable under torch.cuda.graph."""
+    import ctypes
+    L = _lib.lib()
+    if (gt_keypoints_3d is None) == (gt_vertices is None):
+        raise ValueError('pose_eval: give exactly one of gt_keypoints_3d / gt_vertices')
+    v = _f32c(_dev_tensor(pred_vertices, 'pose_eval'))
+    Jr = _f32c(_dev_tensor(J_regressor, 'pose_eval'))
+    B, V = v.shape[0], v.shape[1]
+    mapper = [int(m) for m in joint_mapper]
+    J = len(mapper)
+    if v.dim() != 3 or v.shape[2] != 3 or tuple(Jr.shape) != (17, V):
+        raise ValueError('pose_eval: vertices %s, J_regressor %s (expected [B,V,3], [17,V])' % (tuple(v.shape), tuple(Jr.shape)))
+    gk = gv = None
+    if gt_vertices is not None:
+        gv = _f32c(_dev_tensor(gt_vertices, 'pose_eval'))
+        if tuple(gv.shape) != (B, V, 3):
+            raise ValueError('pose_eval: gt_vertices %s, expected %s' % (tuple(gv.shape), (B, V, 3)))
+    else:
+        gk = _f32c(_dev_tensor(gt_keypoints_3d, 'pose_eval'))
+        if tuple(gk.shape) != (B, J, 3):
+            raise ValueError('pose_eval: gt_keypoints_3d %s, expected %s' % (tuple(gk.shape), (B, J, 3)))
+    e = torch.empty(B, device=v.device, dtype=torch.float32)
+    r = torch.empty(B, device=v.device, dtype=torch.float32)
+    j17 = torch.empty(B, 17, 3, device=v.device, dtype=torch.float32)
+    check(L.danet_pose_eval(ptr(v), ptr(Jr), (ctypes.c_int * J)(*mapper), J, ptr(gk), ptr(gv), B, V, ptr(e), ptr(r), ptr(j17), stream()),
+          'danet_pose_eval')
+    return e, r, j17
+
+
+SEG_COUNTERS = 32
+SEG = {'tp': 0, 'fp': 2, 'fn': 4, 'accuracy': 6, 'pixel_count': 7, 'parts_tp': 8, 'parts_fp': 15, 'parts_fn': 22,
+       'parts_accuracy': 29, 'parts_pixel_count': 30}              # include/danet_hip.h DANET_SEG_*
+
+
+def seg_confusion(mask, parts, gt_mask, gt_parts, offsets, shapes, rects, tables, max_pixels, counters):
+    """The LSP mask / part scoring of eval.py:222-266 for a batch in ONE launch, ADDED to `counters` (int64 [32] on the device, layout
+    SEG).  mask [B,R,R] f32 and parts [B,R,R] int64 as PartRenderer returns them; gt_mask / gt_parts packed uint8 label images (either
+    may be None); offsets int64 [B+1], shapes int32 [B,2], rects int32 [B,6], tables int32 [T]: evaluate.pack_labels builds them."""
+    L = _lib.lib()
+    m = _dev_tensor(mask, 'seg_confusion')
+    p = _dev_tensor(parts, 'seg_confusion')
+    B, R = m.shape[0], m.shape[-1]
+    if m.dtype != torch.float32 or p.dtype != torch.int64 or tuple(m.shape) != (B, R, R) or tuple(p.shape) != (B, R, R):
+        raise ValueError('seg_confusion: mask %s %s, parts %s %s (expected f32 / int64 [B,R,R])' % (m.dtype, tuple(m.shape), p.dtype, tuple(p.shape)))
+    labels = [t for t in (gt_mask, gt_parts) if t is not None]
+    if not labels or any(t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != labels[0].numel() for t in labels):
+        raise ValueError('seg_confusion: the label images come as packed uint8 buffers of one length')
+    for t, dt, shp, what in ((offsets, torch.int64, (B + 1,), 'offsets'), (shapes, torch.int32, (B, 2), 'shapes'), (rects, torch.int32, (B, 6), 'rects'),
+                             (counters, torch.int64, (SEG_COUNTERS,), 'counters')):
+        if t.dtype != dt or tuple(t.shape) != shp:
+            raise ValueError('seg_confusion: %s must be %s %s, got %s %s' % (what, dt, shp, t.dtype, tuple(t.shape)))
+    if tables.dtype != torch.int32 or tables.dim() != 1:
+        raise ValueError('seg_confusion: tables must be a flat int32 tensor')
+    check(L.danet_seg_confusion(ptr(m), ptr(p), ptr(gt_mask), ptr(gt_parts), labels[0].numel(), ptr(offsets), ptr(shapes), ptr(rects),
+                                ptr(tables), tables.numel(), B, R, int(max_pixels), ptr(counters), stream()), 'danet_seg_confusion')
+    return counters

@@ -704,6 +704,48 @@ int danet_mesh_shade_pixels(const void* ws, const float* cam, int B, int V, cons
 int danet_demo_compose(const float* images, const float* glob, const float* part, const float* riuv, const float* mesh,
                        const float* side, const float* side_alpha, int B, int S, int hm, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Scoring ops of the evaluation pipeline (csrc/eval_ops.hip; forward only, evaluate.py is the caller).
+ *
+ * pose_eval (eval.py:183-216, utils/pose_utils.py:10-58), ONE launch, one workgroup per sample: pred_vertices [B,V,3] f32,
+ * J_regressor [17,V] f32, joint_mapper a HOST array of J (3..17; the reference uses 14 or 17) indices into the 17 regressed
+ * joints, and exactly one of gt_keypoints_3d [B,J,3] f32 (already mapped and pelvis-centred) / gt_vertices [B,V,3] f32 (joints
+ * regressed, mapped and centred like the prediction's) -> mpjpe [B], recon_err [B] (Procrustes-aligned, solved in fp64),
+ * pred_joints17 [B,17,3] (not centred).  No workspace; capturable.
+ *
+ * seg_confusion (eval.py:222-266), ONE launch for a batch: mask [B,res,res] f32 and parts [B,res,res] i64 as
+ * PartRenderer.__call__ returns them; gt_mask / gt_parts (either may be NULL) the label images of the batch as packed u8 buffers
+ * of label_bytes bytes each, sample b at offsets[b] (i64 [B+1]) with shapes[b] = (rows, cols) (i32 [B,2]); rects i32 [B,6] =
+ * (y0, y1, x0, x1, row_table, col_table): label pixel (y, x) with y0 <= y < y1, x0 <= x < x1 shows rendered pixel
+ * (tables[row_table + y - y0], tables[col_table + x - x0]), every other label pixel shows 0 (`tables`: i32 [table_len]; the
+ * uncrop rule of DESIGN.md builds them on the host).  max_pixels = the largest rows * cols of the batch.  The counts are ADDED
+ * to counters (i64 [DANET_SEG_COUNTERS], caller-owned, zeroed by the caller before the first batch):
+ *   [TP + c], [FP + c], [FN + c], c = 0, 1 of the mask (label > 0 against mask > 0), [ACC] equal pixels, [PIXELS];
+ *   [PARTS_TP + c], [PARTS_FP + c], [PARTS_FN + c], c = 0..6, where label 255 never counts as predicted; [PARTS_ACC] equal
+ *   pixels after 255 -> 0 on both sides, [PARTS_PIXELS].
+ *
+ * rotmat_to_angle_axis: R [N,3,3] f32 -> angle_axis [N,3] f32, angle in [0, pi] (DESIGN.md "axis-angle rule"); the inverse of
+ * danet_batch_rodrigues.
+ */
+#define DANET_SEG_TP 0
+#define DANET_SEG_FP 2
+#define DANET_SEG_FN 4
+#define DANET_SEG_ACC 6
+#define DANET_SEG_PIXELS 7
+#define DANET_SEG_PARTS_TP 8
+#define DANET_SEG_PARTS_FP 15
+#define DANET_SEG_PARTS_FN 22
+#define DANET_SEG_PARTS_ACC 29
+#define DANET_SEG_PARTS_PIXELS 30
+#define DANET_SEG_COUNTERS 32
+int danet_pose_eval(const float* pred_vertices, const float* J_regressor, const int32_t* joint_mapper, int J,
+                    const float* gt_keypoints_3d, const float* gt_vertices, int B, int V,
+                    float* mpjpe, float* recon_err, float* pred_joints17, void* stream);
+int danet_seg_confusion(const float* mask, const int64_t* parts, const uint8_t* gt_mask, const uint8_t* gt_parts,
+                        int64_t label_bytes, const int64_t* offsets, const int32_t* shapes, const int32_t* rects,
+                        const int32_t* tables, int table_len, int B, int res, int max_pixels, int64_t* counters, void* stream);
+int danet_rotmat_to_angle_axis(const float* R, int N, float* angle_axis, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
