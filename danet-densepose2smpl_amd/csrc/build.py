@@ -51,6 +51,7 @@ UNITS = {
     'lstm_tree.hip': [],
     'vis_ops.hip': ['-ffp-contract=off'],     # the rotation and the bilinear weights are restated operation by operation in the tests
     'eval_ops.hip': [],
+    'input_ops.hip': ['-ffp-contract=off'],   # the crop's arithmetic is restated operation by operation in the tests
 }
 INCLUDES = {'norm_act_f32.hip': ['norm_act.hip']}
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-I' + os.path.join(ROOT, 'include'), '-I' + HERE,

@@ -13,6 +13,7 @@
 //                       block.  All sums are integers: the result does not depend on the order.
 //   rotmat_to_angle_axis  the inverse of batch_rodrigues under the rule of DESIGN.md ("axis-angle rule"), one lane per matrix.
 #include "common.h"
+#include "rotation.h"
 
 namespace {
 
@@ -288,31 +289,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_confusion_kernel(
 __global__ void rotmat_to_angle_axis_kernel(const float* __restrict__ Rm, int N, float* __restrict__ aa) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const float* R = Rm + (size_t)i * 9;
-    const float r00 = R[0], r01 = R[1], r02 = R[2], r10 = R[3], r11 = R[4], r12 = R[5], r20 = R[6], r21 = R[7], r22 = R[8];
-    // matrix -> quaternion, the case of the largest of (trace, r00, r11, r22): the square root is taken of a number >= 1
-    float w, x, y, z;
-    const float tr = r00 + r11 + r22;
-    if (tr > 0.0f) {
-        const float s = 2.0f * sqrtf(tr + 1.0f);
-        w = 0.25f * s; x = (r21 - r12) / s; y = (r02 - r20) / s; z = (r10 - r01) / s;
-    } else if (r00 >= r11 && r00 >= r22) {
-        const float s = 2.0f * sqrtf(1.0f + r00 - r11 - r22);
-        w = (r21 - r12) / s; x = 0.25f * s; y = (r01 + r10) / s; z = (r02 + r20) / s;
-    } else if (r11 >= r22) {
-        const float s = 2.0f * sqrtf(1.0f + r11 - r00 - r22);
-        w = (r02 - r20) / s; x = (r01 + r10) / s; y = 0.25f * s; z = (r12 + r21) / s;
-    } else {
-        const float s = 2.0f * sqrtf(1.0f + r22 - r00 - r11);
-        w = (r10 - r01) / s; x = (r02 + r20) / s; y = (r12 + r21) / s; z = 0.25f * s;
-    }
-    if (w < 0.0f) { w = -w; x = -x; y = -y; z = -z; }                        // the angle in [0, pi]
-    // quaternion -> axis-angle: angle = 2 atan2(|xyz|, w), axis = xyz / |xyz|; small angles: 2 xyz / w
-    const float sn = sqrtf(x * x + y * y + z * z);
-    const float k = sn < 1e-6f ? 2.0f / w : 2.0f * atan2f(sn, w) / sn;
-    aa[(size_t)i * 3 + 0] = x * k;
-    aa[(size_t)i * 3 + 1] = y * k;
-    aa[(size_t)i * 3 + 2] = z * k;
+    danet::rotmat_to_angle_axis<float>(Rm + (size_t)i * 9, aa + (size_t)i * 3);      // (rotation.h: shared with input_ops.hip)
 }
 
 }  // namespace

@@ -357,3 +357,64 @@ def seg_confusion(mask, parts, gt_mask, gt_parts, offsets, shapes, rects, tables
     check(L.danet_seg_confusion(ptr(m), ptr(p), ptr(gt_mask), ptr(gt_parts), labels[0].numel(), ptr(offsets), ptr(shapes), ptr(rects),
                                 ptr(tables), tables.numel(), B, R, int(max_pixels), ptr(counters), stream()), 'danet_seg_confusion')
     return counters
+
+
+def _typed(t, dtype, shape, what):
+    t = _dev_tensor(t, what)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous %s %s tensor, got %s %s' % (what, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+    return t
+
+
+def batch_crop(src, offsets, shapes, origin, params, res, out=None):
+    """augment.rgb_processing for a batch in ONE launch (csrc/input_ops.hip): src packed uint8 HWC pixels (flat), offsets int64 [B+1]
+    (bytes), shapes int32 [B,2] (rows, cols of what is packed per sample), origin int32 [B,2] (x0, y0 of that rectangle in its image),
+    params float64 [B,10] = (inverse crop transform: 6, flip, pn: 3) -> [B,3,res,res] f32 (`out`, or a new tensor -- the op's only
+    allocation).  datasets.crop_params builds the arguments."""
+    L = _lib.lib()
+    s = _dev_tensor(src, 'batch_crop')
+    if s.dtype != torch.uint8 or s.dim() != 1 or s.numel() == 0:
+        raise ValueError('batch_crop: the source pixels come as one packed, non-empty uint8 buffer')
+    B = offsets.numel() - 1
+    _typed(offsets, torch.int64, (B + 1,), 'batch_crop: offsets')
+    _typed(shapes, torch.int32, (B, 2), 'batch_crop: shapes')
+    _typed(origin, torch.int32, (B, 2), 'batch_crop: origin')
+    _typed(params, torch.float64, (B, 10), 'batch_crop: params')
+    res = int(res)
+    if out is None:
+        out = torch.empty(B, 3, res, res, device=s.device, dtype=torch.float32)
+    else:
+        _typed(out, torch.float32, (B, 3, res, res), 'batch_crop: out')
+    check(L.danet_batch_crop(ptr(s), s.numel(), ptr(offsets), ptr(shapes), ptr(origin), ptr(params), B, res, ptr(out), stream()), 'danet_batch_crop')
+    return out
+
+
+def label_augment(rot_flip, xform=None, keypoints=None, smpl_2dkps=None, pose_3d=None, pose=None, fits=None, res=224, inverse=False):
+    """The label transforms of a batch in ONE launch (csrc/input_ops.hip): rot_flip float64 [B,2] (degrees, flip), xform float64 [B,6]
+    (crop transform, for the 2D inputs), float64 keypoints [B,49,3] / smpl_2dkps [B,24,3] / pose_3d [B,24,4] / pose [B,72], float32 fits
+    [B,82].  -> dict of f32 tensors under the inputs' names; `fits` gives 'fits_pose' [B,72] and 'fits_betas' [B,10].  inverse: the pose
+    transforms undone (FitsDict.__setitem__)."""
+    L = _lib.lib()
+    B = rot_flip.shape[0]
+    rf = _typed(rot_flip, torch.float64, (B, 2), 'label_augment: rot_flip')
+    dev = rf.device
+    xf = None if xform is None else _typed(xform, torch.float64, (B, 6), 'label_augment: xform')
+    if (keypoints is not None or smpl_2dkps is not None) and xf is None:
+        raise ValueError('label_augment: 2D keypoints need the crop transform')
+    spec = (('keypoints', keypoints, torch.float64, (B, 49, 3)), ('smpl_2dkps', smpl_2dkps, torch.float64, (B, 24, 3)),
+            ('pose_3d', pose_3d, torch.float64, (B, 24, 4)), ('pose', pose, torch.float64, (B, 72)), ('fits', fits, torch.float32, (B, 82)))
+    ins, outs = [], {}
+    for name, t, dt, shp in spec:
+        ins.append(None if t is None else _typed(t, dt, shp, 'label_augment: ' + name))
+        if t is not None and name != 'fits':
+            outs[name] = torch.empty(shp, device=dev, dtype=torch.float32)
+    if fits is not None:
+        outs['fits_pose'] = torch.empty(B, 72, device=dev, dtype=torch.float32)
+        outs['fits_betas'] = torch.empty(B, 10, device=dev, dtype=torch.float32)
+    if not outs:
+        raise ValueError('label_augment: nothing to do')
+    o = lambda k: ptr(outs.get(k))           # noqa: E731
+    check(L.danet_label_augment(ptr(xf), ptr(rf), ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), ptr(ins[3]), ptr(ins[4]), B, int(res), int(bool(inverse)),
+                                o('keypoints'), o('smpl_2dkps'), o('pose_3d'), o('pose'), o('fits_pose'), o('fits_betas'), stream()),
+          'danet_label_augment')
+    return outs

@@ -2,8 +2,8 @@
 (/root/reference/train/trainer.py:117-244): ``train_step(in_dict) -> (output, losses)`` =
 forward, sum of the loss dict (trainer.py:217-220), backward, Adam step (lr 1e-4, trainer.py:42-44).
 The in_dict is the one the reference builds at trainer.py:184-212; `synthetic_in_dict` produces it
-from seeded random labels.  Data loading, FitsDict, TensorBoard and
-checkpoints are out of scope."""
+from seeded random labels.  `Trainer.fit` is the loop of base_trainer.py:53-106 over
+datasets.py / fits_dict.py; TensorBoard is out of scope."""
 import types
 
 import numpy as np
@@ -584,3 +584,83 @@ class Trainer(object):
         if self.step_count % self.ONEPASS_CHECK_EVERY == 0:
             self.check_onepass()
         return self._static_out
+
+    # ------------------------------------------------------------------------------------------
+    # The training loop: base_trainer.py:53-106 around the step prologue of train/trainer.py:134-212.  Steps run eagerly:
+    # `pretrain_mode` and `dp_active` are host switches that a captured graph would freeze.
+    def build_in_dict(self, host_batch, fits_dict, train_data='h36m_dp', pretrain_mode=False):
+        """A collated loader batch (datasets.collate) -> the in_dict of train_step, all on the step's own stream: upload + the two
+        input ops (datasets.to_device), the fits (fits_dict[...], one gather + the label op), valid_fit, prepare_batch."""
+        from . import datasets
+        with self._on_stream():
+            batch = datasets.to_device(host_batch, self.device, cfg.DANET.INIMG_SIZE)
+            opt_pose, opt_betas = fits_dict[(batch['dataset_name'], batch['sample_index'], batch['rot_angle'], batch['is_flipped'])]
+            has_smpl = batch['has_smpl'] > 0
+            if train_data == 'h36m_coco_itw':
+                batch['valid_fit'] = (fits_dict.get_vaild_state(batch['dataset_name'], batch['sample_index']) > 0) | has_smpl
+            else:
+                batch['valid_fit'] = has_smpl
+            batch['vis_on'] = False
+            batch['pretrain_mode'] = bool(pretrain_mode)
+            in_dict = self.prepare_batch(batch, opt_pose, opt_betas)
+            in_dict['dp_dict']['dp_active'] = bool(host_batch['dp_active'])
+        return in_dict
+
+    @staticmethod
+    def latest_checkpoint(checkpoint_dir):
+        names = sorted(n for n in os.listdir(checkpoint_dir) if n.startswith('step_') and n.endswith('.pt')) if os.path.isdir(checkpoint_dir) else []
+        return os.path.join(checkpoint_dir, names[-1]) if names else None
+
+    def fit(self, train_ds, fits_dict, options, on_step=None):
+        """Trains on `train_ds` (a datasets.MixedDataset / TrainDataset) with the pseudo-label store `fits_dict`.  options:
+        num_epochs, batch_size, checkpoint_steps, summary_steps, pretr_step, train_data, num_workers, time_to_run (seconds), seed,
+        shuffle_train, log_dir, checkpoint_dir, resume (a checkpoint file, or True: the newest of checkpoint_dir), pretrained_checkpoint.
+        Every summary_steps steps one JSON line with the losses goes to <log_dir>/train_log.jsonl; a checkpoint step_<n>.pt with
+        epoch, batch_idx and dataset_perm is written every checkpoint_steps steps and when time_to_run is over.
+        on_step(step_count, in_dict, losses), if given, is called after every step.  Returns the number of steps run."""
+        import json
+        import time
+        from . import checkpoint, datasets
+        opt = lambda k, d=None: d if getattr(options, k, None) is None else getattr(options, k)       # noqa: E731
+        bs, ckpt_dir, log_dir = int(options.batch_size), opt('checkpoint_dir', 'checkpoints'), opt('log_dir', 'logs')
+        endtime = time.time() + float(opt('time_to_run', np.inf))
+        book, epoch0 = None, 0
+        resume = opt('resume', None)
+        if resume:
+            path = resume if isinstance(resume, str) else self.latest_checkpoint(ckpt_dir)
+            if path is not None:
+                book = self.resume(path, trusted=True)
+                epoch0 = int(book.get('epoch') or 0)
+        elif opt('pretrained_checkpoint', None):
+            checkpoint.load_pretrained(self.model, options.pretrained_checkpoint)
+        os.makedirs(log_dir, exist_ok=True)
+        ran = 0
+
+        def save(epoch, batch_idx, perm):
+            return self.save(os.path.join(ckpt_dir, 'step_%08d.pt' % self.step_count), epoch=epoch, batch_idx=batch_idx, batch_size=bs, dataset_perm=perm)
+
+        with open(os.path.join(log_dir, 'train_log.jsonl'), 'a') as log:
+            for epoch in range(epoch0, int(options.num_epochs)):
+                loader = datasets.TrainLoader(train_ds, checkpoint=book, batch_size=bs, shuffle=bool(opt('shuffle_train', True)),
+                                              num_workers=int(opt('num_workers', 0)), seed=int(opt('seed', 0)), epoch=epoch, res=cfg.DANET.INIMG_SIZE)
+                for step, host in enumerate(loader, loader.checkpoint_batch_idx):
+                    if time.time() >= endtime:
+                        save(epoch, step, loader.sampler.dataset_perm)
+                        return ran
+                    count = self.step_count + 1                            # (base_trainer.py:70-74: the step about to run)
+                    in_dict = self.build_in_dict(host, fits_dict, opt('train_data', 'h36m_dp'), pretrain_mode=count <= int(opt('pretr_step', 0)))
+                    _, losses = self.train_step(in_dict)
+                    ran += 1
+                    if (self.step_count - 1) % int(opt('summary_steps', 100)) == 0:
+                        vals = {'loss_' + k: float(v.detach()) for k, v in losses.items()}      # ('loss_{}'.format(key), train/trainer.py:221)
+                        vals['loss_tatal'] = float(sum(vals.values()))
+                        log.write(json.dumps({'step': self.step_count, 'epoch': epoch, 'batch_idx': step, **vals}) + '\n')
+                        log.flush()
+                    if on_step is not None:
+                        on_step(self.step_count, in_dict, losses)
+                    if self.step_count % int(opt('checkpoint_steps', 10000)) == 0:
+                        save(epoch, step + 1, loader.sampler.dataset_perm)
+                book = None                                                # (a checkpoint positions the first epoch only)
+                if (epoch + 1) % 10 == 0:
+                    save(epoch + 1, 0, None)
+        return ran

@@ -746,6 +746,38 @@ int danet_seg_confusion(const float* mask, const int64_t* parts, const uint8_t* 
                         const int32_t* tables, int table_len, int B, int res, int max_pixels, int64_t* counters, void* stream);
 int danet_rotmat_to_angle_axis(const float* R, int N, float* angle_axis, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Input ops of the training pipeline (csrc/input_ops.hip; forward only, datasets.py and fits_dict.py are the callers).
+ * Both are ONE launch for a batch, need no workspace, enqueue only on `stream` and are capturable.
+ *
+ * batch_crop (datasets/base_dataset.py:144-158 + normalize_img; augment.rgb_processing): src is the batch's source pixels as one
+ * packed u8 buffer of src_bytes bytes, rows x cols x 3 (HWC, RGB) per sample, sample b at offsets[b] (i64 [B+1], in bytes) with
+ * shapes[b] = (rows, cols) (i32 [B,2]; 0 x 0 is allowed: nothing of the image is seen).  What is packed for a sample is a
+ * RECTANGLE of its image whose top-left pixel is image pixel origin[b] = (x0, y0) (i32 [B,2]; (0, 0) with the whole image packed).
+ * params f64 [B,10] per sample: the first two rows of the INVERSE of the crop transform (six numbers, row-major: output pixel
+ * (v, u) shows image point (p0 u + p1 v + p2, p3 u + p4 v + p5)), flip (0 / 1), pn[3] (the per-channel pixel noise).
+ * out [B,3,res,res] f32: bilinear on pixel coordinates, a tap outside the packed rectangle contributes zero; columns mirrored
+ * where flip; x pn[c], clamped to [0, 255], / 255, (x - mean[c]) / std[c] with the ImageNet constants (0.485, 0.456, 0.406) /
+ * (0.229, 0.224, 0.225).  The arithmetic is fp64 with one rounding to fp32 at the end; the origin is subtracted from the
+ * INTEGER tap coordinates, so a rectangle that holds every tap of the crop gives bit for bit what the whole image gives.
+ *
+ * label_augment (base_dataset.py:160-199,239-277; train/fits_dict.py:51-119): any of the five inputs may be NULL (its outputs
+ * are then not touched).  rot_flip f64 [B,2] = (rotation in degrees, flip 0 / 1); xform f64 [B,6] = the first two rows of the
+ * crop transform (needed by the two 2D inputs).  keypoints f64 [B,49,3] -> j2d_processing; smpl_2dkps f64 [B,24,3] ->
+ * j2d_processing without flip, rows of confidence 0 zeroed, then where flip the rows permuted by SMPL_JOINTS_FLIP_PERM and x
+ * negated; pose_3d f64 [B,24,4] -> j3d_processing; pose f64 [B,72] -> pose_processing; fits f32 [B,82] (72 pose, 10 betas) ->
+ * fits_pose_out [B,72] = flip_pose(rotate_pose(pose, rot), flip), fits_betas_out [B,10] copied.  inverse = 1 turns the two pose
+ * transforms into rotate_pose(flip_pose(pose, flip), -rot) (FitsDict.__setitem__).  All outputs f32; fp64 inside; the
+ * truncation of `transform` (imutils.py:38-46) included; the global orientation comes back under the axis-angle rule of
+ * danet_rotmat_to_angle_axis (the same device code).
+ */
+int danet_batch_crop(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int32_t* shapes, const int32_t* origin,
+                     const double* params, int B, int res, float* out, void* stream);
+int danet_label_augment(const double* xform, const double* rot_flip, const double* keypoints, const double* smpl_2dkps,
+                        const double* pose_3d, const double* pose, const float* fits, int B, int res, int inverse,
+                        float* keypoints_out, float* smpl_2dkps_out, float* pose_3d_out, float* pose_out,
+                        float* fits_pose_out, float* fits_betas_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
