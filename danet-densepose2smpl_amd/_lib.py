@@ -115,6 +115,9 @@ _SIGNATURES = {
     'danet_iuv_global_backward': (c_i, [c_f] * 4 + [c_i, c_i] + [c_f] * 6 + [c_i] * 4 + [c_f] * 5),
     'danet_softargmax_forward': (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_f]),
     'danet_softargmax_backward': (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_f, c_f]),
+    'danet_dp_point_losses_rows': (c_i, [c_i, c_i]),
+    'danet_dp_point_losses_forward': (c_i, [c_f] * 4 + [c_i, c_i] + [c_f] * 8 + [c_i] * 3 + [c_f, c_f]),
+    'danet_dp_point_losses_backward': (c_i, [c_f] * 4 + [c_i, c_i] + [c_f] * 9 + [c_i] * 3 + [c_f] * 5),
     'danet_pad_multi': (c_i, [c_f, c_f, c_f, c_f, c_i, c_f]),
     'danet_loss_finalize': (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_f]),
     'danet_smpl_joints_forward': (c_i, [c_f, c_f, c_f] + [c_i] * 4 + [c_f] * 4),

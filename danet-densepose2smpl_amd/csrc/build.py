@@ -40,6 +40,7 @@ UNITS = {
     'part_ops.hip': [],
     'part_gt.hip': [],
     'iuv_ops.hip': [],
+    'dp_losses.hip': ['-ffp-contract=off'],    # the sampling coordinates follow grid_sample's arithmetic operation by operation
     'loss_ops.hip': [],
     'adam.hip': [],
     'norm_act.hip': [],

@@ -323,7 +323,11 @@ class IUV_Estimator(nn.Module):
             # `torch.sum(has_dp) > 0` does, without a device sync inside the step.
             if uvia_dp_gt.get('dp_active', True):
                 dp = {k: v for k, v in uvia_dp_gt.items() if torch.is_tensor(v)}
-                lU, lV, lI, lA = self.dp_uvia_losses(u_pred, v_pred, index_pred, ann_pred, dp, has_dp, align)
+                if fused:
+                    # one launch per pass (csrc/dp_losses.hip); dp_uvia_losses states the same arithmetic in tensor ops
+                    lU, lV, lI, lA = iuv_ops.dp_point_losses(u_pred, v_pred, index_pred, ann_pred, dp, has_dp, align)
+                else:
+                    lU, lV, lI, lA = self.dp_uvia_losses(u_pred, v_pred, index_pred, ann_pred, dp, has_dp, align)
                 rd['losses'].update({'loss_Udp': lU, 'loss_Vdp': lV, 'loss_IndexUVdp': lI, 'loss_segAnndp': lA})
             else:
                 z = torch.zeros(1, device=data.device)

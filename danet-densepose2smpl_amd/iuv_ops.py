@@ -1,7 +1,8 @@
 """Global (25-class) IUV glue on HIP kernels (csrc/iuv_ops.hip): the estimator's `iuv_img2map` + `body_uv_losses`
 (/root/reference/models/danet/iuv_estimator.py:95-104,304-341, utils/iuvmap.py:103-147) and DaNet.forward's part drop +
 `iuvmap_clean` + concat (models/danet/danet.py:194-205,247, utils/iuvmap.py:6-38) as ONE op per pass, and the
-soft-argmax of the joint heat-maps (utils/keypoints.py:334-394).  GPU only; the tensor-op forms in iuvmap.py /
+soft-argmax of the joint heat-maps (utils/keypoints.py:334-394); and the DensePose-COCO point supervision
+(models/danet/iuv_estimator.py:343-419) as one launch per pass (csrc/dp_losses.hip).  GPU only; the tensor-op forms in iuvmap.py /
 geometry.py remain as the CPU-checkable statement of the same arithmetic (tests pin both against the reference's
 golden vectors)."""
 import torch
@@ -111,6 +112,18 @@ def iuv_global(u, v, ix, an, gt=None, w=None, keep=None, scales=None):
     return _pack(IuvGlobalFunction.apply(u, v, ix, an, gt, w, keep, scales), scales)
 
 
+def _padded_bases(u, v, ix, an):
+    """iuv_global's hand-over rule for dp_point_losses: -> the four `_padded_base` tensors when all four head outputs carry one that
+    qualifies (and gradients are being recorded), the tensors as they came otherwise."""
+    if PADDED_BASES and torch.is_grad_enabled():
+        bases = [getattr(t, '_padded_base', None) for t in (u, v, ix, an)]
+        ok = all(b is not None and b.dtype == torch.float32 and b.shape[0] == t.shape[0] and b.shape[2:] == t.shape[2:] and
+                 b.data_ptr() == t.data_ptr() and b.shape[1] == ld for b, t, ld in zip(bases, (u, v, ix, an), (32, 32, 32, 16)))
+        if ok and all(_rows(b, n, ld) is b for b, n, ld in zip(bases, (NP, NP, NP, NA), (32, 32, 32, 16))):
+            return bases
+    return u, v, ix, an
+
+
 def _pack(out, scales):
     """(sums, map, argmax), with `scales` the four finished losses as a tuple in place of the sum vector."""
     return out if scales is None else (tuple(out[:4]), out[4], out[5])
@@ -148,3 +161,70 @@ def softargmax(hm, scale=1.0):
     if not hm.is_cuda:
         raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % hm.device)
     return SoftArgmaxFunction.apply(hm, scale)
+
+
+NPT = 196          # DensePose point slots per sample (datasets/base_dataset.py:228-232)
+
+
+class DpPointLossesFunction(torch.autograd.Function):
+    """(u, v, index, ann, X, Y, I, U, V, point weights, ann labels, w [B] in {0, 1}, align, scales) -> the four finished losses
+    (csrc/dp_losses.hip + glue.loss_finalize); the gradients come back at the inputs' width (32 / 16 channels for padded bases)."""
+
+    @staticmethod
+    def forward(ctx, u, v, ix, an, X, Y, I, TU, TV, PW, labels, w, align, scales):
+        from .glue import loss_finalize
+        L = _lib.lib()
+        B, _, H, W = u.shape
+        if H != W:
+            raise RuntimeError('dp_point_losses: square maps expected, got %d x %d' % (H, W))
+        ctx.full = (u.shape[1] == 32, v.shape[1] == 32, ix.shape[1] == 32, an.shape[1] == 16)
+        u, v, ix = _rows(u, NP, 32), _rows(v, NP, 32), _rows(ix, NP, 32)
+        an = _rows(an, NA, 16)
+        rows = L.danet_dp_point_losses_rows(B, H)
+        partial = torch.empty(rows, 4, dtype=torch.float64, device=u.device)      # one row of double sums per workgroup, every row written
+        check(L.danet_dp_point_losses_forward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), 32, 16, ptr(X), ptr(Y), ptr(I), ptr(TU),
+                                              ptr(TV), ptr(PW), ptr(labels), ptr(w), B, H, int(bool(align)), ptr(partial), stream()),
+              'danet_dp_point_losses_forward')
+        ctx.save_for_backward(u, v, ix, an, X, Y, I, TU, TV, PW, labels, w)
+        ctx.align, ctx.scales = bool(align), scales
+        ctx.set_materialize_grads(False)
+        out = loss_finalize(4, scales, w, B, sums=partial, rows=rows)
+        return out[0:1], out[1:2], out[2:3], out[3:4]
+
+    @staticmethod
+    def backward(ctx, *g4):
+        from .glue import loss_finalize
+        L = _lib.lib()
+        u, v, ix, an, X, Y, I, TU, TV, PW, labels, w = ctx.saved_tensors
+        B, _, H, W = u.shape
+        if all(g is None for g in g4):
+            return (None,) * 14
+        coef = loss_finalize(4, ctx.scales, w, B, grads=list(g4))
+        du = torch.empty(B, H, W, 32, dtype=torch.float32, device=u.device)       # fully written by the kernel: no memset
+        dv, di = torch.empty_like(du), torch.empty_like(du)
+        da = torch.empty(B, H, W, 16, dtype=torch.float32, device=u.device)
+        check(L.danet_dp_point_losses_backward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), 32, 16, ptr(X), ptr(Y), ptr(I), ptr(TU),
+                                               ptr(TV), ptr(PW), ptr(labels), ptr(w), ptr(coef), B, H, int(ctx.align),
+                                               ptr(du), ptr(dv), ptr(di), ptr(da), stream()), 'danet_dp_point_losses_backward')
+        f = lambda t, n, full: t.permute(0, 3, 1, 2) if full else t.permute(0, 3, 1, 2)[:, :n]        # noqa: E731
+        fu = ctx.full
+        return (f(du, NP, fu[0]), f(dv, NP, fu[1]), f(di, NP, fu[2]), f(da, NA, fu[3])) + (None,) * 10
+
+
+def dp_point_losses(u, v, index, ann, dp, has_dp=None, align=True):
+    """IUV_Estimator.dp_uvia_losses (the CPU-checkable statement of this arithmetic) as one HIP launch per pass: the heads' [B,25|15,S,S]
+    outputs (or their zero-padded bases), the 9 DensePose blobs `dp` of a batch, has_dp [B] or None (= all labelled) ->
+    (loss_Udp, loss_Vdp, loss_IndexUVdp, loss_segAnndp), one-element tensors.  Every sample is evaluated and weighted by
+    has_dp > 0; an all-zero has_dp gives exact zeros.  The backward pass uses no floating-point atomics: two runs are bitwise equal."""
+    from .config import cfg
+    if not u.is_cuda:
+        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % u.device)
+    B, S = u.shape[0], u.shape[-1]
+    f32 = lambda k, n: dp[k].detach().reshape(B, n).to(torch.float32).contiguous()                   # noqa: E731
+    w = torch.ones(B, device=u.device) if has_dp is None else (has_dp.detach().reshape(B) > 0).to(torch.float32)
+    scales = ((cfg.DANET.POINT_REGRESSION_WEIGHTS, 0.), (cfg.DANET.POINT_REGRESSION_WEIGHTS, 0.),
+              (cfg.DANET.PART_WEIGHTS, float(NPT)), (cfg.DANET.INDEX_WEIGHTS, float(S * S)))
+    u, v, index, ann = _padded_bases(u, v, index, ann)
+    return DpPointLossesFunction.apply(u, v, index, ann, f32('body_uv_X_points', NPT), f32('body_uv_Y_points', NPT), f32('body_uv_I_points', NPT),
+                                       f32('body_uv_U_points', NP * NPT), f32('body_uv_V_points', NP * NPT), f32('body_uv_point_weights', NP * NPT),
+                                       dp['body_uv_ann_labels'].detach().reshape(B, S * S).to(torch.int32).contiguous(), w, align, scales)

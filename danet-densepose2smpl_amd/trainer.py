@@ -455,20 +455,22 @@ class Trainer(object):
     def _clone_batch(d):
         return {k: (v.clone() if torch.is_tensor(v) else Trainer._clone_batch(v) if isinstance(v, dict) else v) for k, v in d.items()}
 
-    def capture(self, in_dict, warmup=2):
+    def capture(self, in_dict, warmup=2, dp_active=True):
         """Capture the whole step -- forward, backward, the bucketed gradient all-reduces (N > 1) and Adam -- for batches
         shaped like `in_dict`.  The host-side switches of a batch are frozen into the graph: `pretrain_mode` / `vis_on`
         must not change between replays (checked by load_batch), and DensePose point supervision is captured as ACTIVE
         whenever the batch carries a `dp_dict` (its losses are masked by `has_dp` per sample, so batches without
-        DensePose labels simply contribute zeros).  If the communication library cannot be captured the all-reduces
-        and the optimizer run right after each replay instead."""
+        DensePose labels simply contribute zeros) -- unless dp_active is False: a run whose datasets hold no DensePose labels
+        captures the four zero losses and none of the work.  warmup: eager steps on `in_dict` before the capture (real optimizer
+        steps; 0 when the caller has just run eager steps of this kind itself, as Trainer.fit does).  If the communication
+        library cannot be captured the all-reduces and the optimizer run right after each replay instead."""
         from . import conv
         if self.device.type != 'cuda':
             raise RuntimeError('hipGraph capture needs a GPU')
         self.model.train()
         self._static = self._clone_batch(in_dict)
         if isinstance(self._static.get('dp_dict'), dict):
-            self._static['dp_dict']['dp_active'] = True
+            self._static['dp_dict']['dp_active'] = bool(dp_active)
         with self._on_stream():
             for _ in range(warmup):
                 self._core(self._static)
@@ -557,6 +559,14 @@ class Trainer(object):
         except Exception as e:          # noqa: BLE001 -- nothing more to try; the second capture will report the state it finds
             warnings.warn('trainer: could not end the stray capture (%r)' % (e,))
 
+    def drop_graph(self):
+        """Forget the captured step: the graph with its memory pool, the static batch and the static outputs (tensors handed out by
+        train_step_graphed die with them), and the packed-weight cache, whose entries may point into that pool."""
+        self._graph = None
+        self._static = None
+        self._static_out = None
+        _conv._PACK_CACHE.clear()
+
     def load_batch(self, in_dict):
         """Copy a new batch into the captured graph's static input tensors (nested dictionaries included)."""
         def rec(dst, src, path):
@@ -586,8 +596,9 @@ class Trainer(object):
         return self._static_out
 
     # ------------------------------------------------------------------------------------------
-    # The training loop: base_trainer.py:53-106 around the step prologue of train/trainer.py:134-212.  Steps run eagerly:
-    # `pretrain_mode` and `dp_active` are host switches that a captured graph would freeze.
+    # The training loop: base_trainer.py:53-106 around the step prologue of train/trainer.py:134-212.  Steps run eagerly unless
+    # options.graph asks for captured steps: `pretrain_mode` and `dp_active` are host switches that a captured graph freezes, so a
+    # graphed run holds one graph per pretrain_mode phase and decides dp_active once, from the datasets of the run (_fit_step).
     def build_in_dict(self, host_batch, fits_dict, train_data='h36m_dp', pretrain_mode=False):
         """A collated loader batch (datasets.collate) -> the in_dict of train_step, all on the step's own stream: upload + the two
         input ops (datasets.to_device), the fits (fits_dict[...], one gather + the label op), valid_fit, prepare_batch."""
@@ -606,6 +617,30 @@ class Trainer(object):
             in_dict['dp_dict']['dp_active'] = bool(host_batch['dp_active'])
         return in_dict
 
+    def _fit_step(self, in_dict):
+        """One step of a graphed fit (see fit): eager for the first two steps of a pretrain_mode phase, a capture before the third,
+        replays from there on.  -> the step's losses."""
+        phase, done, dp_captured = self._fit_phase
+        if phase != in_dict['pretrain_mode']:
+            # a new phase runs other modules: drop the old graph, static batch and pool FIRST, and let the two eager steps record and
+            # build the weight bank again (the bank of a pretrain-mode step holds none of the regressor's weights)
+            self.drop_graph()
+            self.bank = None
+            if isinstance(_conv.RECORDER, _conv.WeightBank):
+                _conv.RECORDER = None
+            phase, done = in_dict['pretrain_mode'], 0
+        if done < 2:
+            _, losses = self.train_step(in_dict)
+            self.fit_stats['eager_steps'] += 1
+        else:
+            if self._graph is None:
+                self.capture(in_dict, warmup=0, dp_active=dp_captured)
+                self.fit_stats['captures'] += 1
+            _, losses = self.train_step_graphed(in_dict)
+            self.fit_stats['replayed_steps'] += 1
+        self._fit_phase = (phase, done + 1, dp_captured)
+        return losses
+
     @staticmethod
     def latest_checkpoint(checkpoint_dir):
         names = sorted(n for n in os.listdir(checkpoint_dir) if n.startswith('step_') and n.endswith('.pt')) if os.path.isdir(checkpoint_dir) else []
@@ -617,7 +652,15 @@ class Trainer(object):
         shuffle_train, log_dir, checkpoint_dir, resume (a checkpoint file, or True: the newest of checkpoint_dir), pretrained_checkpoint.
         Every summary_steps steps one JSON line with the losses goes to <log_dir>/train_log.jsonl; a checkpoint step_<n>.pt with
         epoch, batch_idx and dataset_perm is written every checkpoint_steps steps and when time_to_run is over.
-        on_step(step_count, in_dict, losses), if given, is called after every step.  Returns the number of steps run."""
+        on_step(step_count, in_dict, losses), if given, is called after every step.  Returns the number of steps run.
+        options.graph (default off): steps run as hipGraph replays.  A phase is a value of pretrain_mode; its first two steps run
+        eagerly on their own batches (they build the weight bank and the allocator's state the capture needs, and they are real
+        optimizer steps), the third step's in_dict is captured (no warm-up steps of the capture's own) and that step and every later
+        one of the phase is a replay; when the phase changes the graph, its static batch and its pool are dropped first.  DensePose
+        point supervision is captured as active iff 'dp_coco' is one of the run's datasets (TRAIN_SETS[train_data]), decided once per
+        run.  A batch of another shape than the captured one raises (load_batch).  The `losses` of a replayed step are the graph's
+        static output tensors: valid until the next step, which overwrites them -- copy what must outlive it.
+        self.fit_stats = {'eager_steps', 'replayed_steps', 'captures'} counts this call's steps."""
         import json
         import time
         from . import checkpoint, datasets
@@ -635,6 +678,14 @@ class Trainer(object):
             checkpoint.load_pretrained(self.model, options.pretrained_checkpoint)
         os.makedirs(log_dir, exist_ok=True)
         ran = 0
+        self.fit_stats = {'eager_steps': 0, 'replayed_steps': 0, 'captures': 0}
+        graphed = bool(opt('graph', False))
+        train_data = opt('train_data', 'h36m_dp')
+        if graphed:
+            if self.device.type != 'cuda':
+                raise RuntimeError('options.graph needs a GPU')
+            self.drop_graph()                                              # (a graph of an earlier run: its phase is unknown here)
+            self._fit_phase = (None, 0, 'dp_coco' in datasets.TRAIN_SETS.get(train_data, ()))
 
         def save(epoch, batch_idx, perm):
             return self.save(os.path.join(ckpt_dir, 'step_%08d.pt' % self.step_count), epoch=epoch, batch_idx=batch_idx, batch_size=bs, dataset_perm=perm)
@@ -648,8 +699,12 @@ class Trainer(object):
                         save(epoch, step, loader.sampler.dataset_perm)
                         return ran
                     count = self.step_count + 1                            # (base_trainer.py:70-74: the step about to run)
-                    in_dict = self.build_in_dict(host, fits_dict, opt('train_data', 'h36m_dp'), pretrain_mode=count <= int(opt('pretr_step', 0)))
-                    _, losses = self.train_step(in_dict)
+                    in_dict = self.build_in_dict(host, fits_dict, train_data, pretrain_mode=count <= int(opt('pretr_step', 0)))
+                    if graphed:
+                        losses = self._fit_step(in_dict)
+                    else:
+                        _, losses = self.train_step(in_dict)
+                        self.fit_stats['eager_steps'] += 1
                     ran += 1
                     if (self.step_count - 1) % int(opt('summary_steps', 100)) == 0:
                         vals = {'loss_' + k: float(v.detach()) for k, v in losses.items()}      # ('loss_{}'.format(key), train/trainer.py:221)

@@ -206,6 +206,26 @@ int danet_softargmax_backward(const float* hm, int ld, int B, int J, int H, int 
                               const float* gout, float* dhm, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * DensePose-COCO point supervision (csrc/dp_losses.hip).  Replaces models/danet/iuv_estimator.py:343-419 (dp_uvia_losses) in
+ * masked-weight form: every sample is evaluated, samples with has_dp <= 0 contribute exact zeros.
+ *  u, v, ix: fp32 [B*S*S][ld = 32] (25 valid channels); an: [B*S*S][lda = 16] (15 valid); X, Y, I: [B,196] point coordinates (pixels of
+ *  the S x S map) and patch labels (floats holding 0..24); TU, TV, PW: [B,25,196] targets and point weights; ann_labels: int32 [B,S*S]
+ *  (0..14); has_dp: [B] floats; align: grid_sample's align_corners.
+ *  forward: partial[rows][4] DOUBLES, rows = danet_dp_point_losses_rows(B, S), every row written (no memset, no atomics): the sums of
+ *  (smooth-L1 U, smooth-L1 V with inside = outside = PW; cross-entropy of the pooled index logits over all 196 slots; cross-entropy of
+ *  the Ann logits over all pixels) of one workgroup -- danet_loss_finalize adds the rows in order and applies weights and divisors.
+ *  backward: coef[4] = dL/dsums (device); du, dv, di ([..][32]) and da ([..][16]) are fully written (pad channels, untouched pixels and
+ *  unlabelled samples as zeros), without floating-point atomics: two runs are bitwise equal.  S <= 128. */
+int danet_dp_point_losses_rows(int B, int S);
+int danet_dp_point_losses_forward(const float* u, const float* v, const float* ix, const float* an, int ld, int lda,
+                                  const float* X, const float* Y, const float* I, const float* TU, const float* TV, const float* PW,
+                                  const int* ann_labels, const float* has_dp, int B, int S, int align, double* partial, void* stream);
+int danet_dp_point_losses_backward(const float* u, const float* v, const float* ix, const float* an, int ld, int lda,
+                                   const float* X, const float* Y, const float* I, const float* TU, const float* TV, const float* PW,
+                                   const int* ann_labels, const float* has_dp, const float* coef, int B, int S, int align,
+                                   float* du, float* dv, float* di, float* da, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Launch-count glue (csrc/glue.hip).
  * danet_pad_multi: n (<= 16) zero-pad / crop copies of small dense fp32 tensors (<= 4-d, shapes given with leading ones) in one
  *   launch: dst[i] = src[i] inside the source's shape, 0 elsewhere.  Replaces F.pad on the parameters of layers whose widths are no

@@ -2,11 +2,12 @@
 
   python tools/train.py --name RUN [--data_root DIR] [--train_data h36m_dp|h36m_coco_itw] [--num_epochs N] [--batch_size B]
                         [--checkpoint_steps K] [--summary_steps K] [--pretr_step K] [--resume] [--pretrained_checkpoint FILE]
-                        [--num_workers W] [--ignore_3d] [--time_to_run SECONDS] [--cfg YAML] [--log_dir DIR]
+                        [--num_workers W] [--ignore_3d] [--time_to_run SECONDS] [--cfg YAML] [--log_dir DIR] [--graph]
 
 --data_root holds, for every dataset <ds> of --train_data, <ds>_train.npz (the reference's annotation layout), the image folder <ds>/
 and the fits folders final_fits/ and static_fits/.  Without it a small synthetic 'h36m_dp' set is written to a scratch directory and
-trained on, so the tool runs on a machine with no data.  Logs (train_log.jsonl) and checkpoints go to <log_dir>/<name>/.
+trained on, so the tool runs on a machine with no data.  --graph runs the steps as hipGraph replays (Trainer.fit: two eager steps and
+one capture per pretrain_mode phase).  Logs (train_log.jsonl) and checkpoints go to <log_dir>/<name>/.
 Last line: one JSON object (steps run, last losses)."""
 import argparse
 import json
@@ -36,6 +37,7 @@ def main(argv=None):
     ap.add_argument('--cfg', dest='cfg_file', default=None)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--num_synthetic', type=int, default=32)
+    ap.add_argument('--graph', action='store_true', help='replay captured steps (one hipGraph per pretrain_mode phase)')
     a = ap.parse_args(argv)
 
     import torch
@@ -70,8 +72,9 @@ def main(argv=None):
 
     def on_step(step, in_dict, losses):
         last.clear()
-        last.update(step=step, **{k: float(v.detach()) for k, v in losses.items()})
+        last.update(step=step, **losses)         # (tensors: read once, after the last step -- no host read per step)
     steps = trainer.fit(train_ds, fits, a, on_step=on_step)
+    last = {k: (float(v.detach()) if torch.is_tensor(v) else v) for k, v in last.items()}
     fits.save()
     print(json.dumps({'steps': steps, 'last': last}), flush=True)
     if tmp is not None:
