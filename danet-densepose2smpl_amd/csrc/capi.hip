@@ -28,6 +28,29 @@ hipError_t zero_async(void* p, size_t bytes, hipStream_t stream) {
     hipLaunchKernelGGL(zero_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (unsigned*)p, n4, tail0, n);
     return hipGetLastError();
 }
+
+int raise_dynamic_lds(LdsOptIn& st, const void* kernel, size_t bytes, const char* name) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(DANET_ERR_HIP, "%s: hipGetDevice, before raising dynamic LDS to %zu bytes: %s", name, bytes, hipGetErrorString(e)); }
+    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
+    if (st.devices.load(std::memory_order_acquire) & bit) return DANET_OK;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);     // (two threads racing here both raise: harmless)
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(DANET_ERR_HIP, "%s: raising dynamic LDS to %zu bytes on device %d: %s", name, bytes, dev, hipGetErrorString(e)); }
+    st.devices.fetch_or(bit, std::memory_order_release);
+    return DANET_OK;
+}
+
+int compute_units() {
+    static std::atomic<int> seen[64];                    // 0 = not asked yet
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) { (void)hipGetLastError(); return 256; }
+    const bool keyed = dev < 64;
+    if (keyed && (cus = seen[dev].load(std::memory_order_relaxed)) > 0) return cus;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+    if (keyed) seen[dev].store(cus, std::memory_order_relaxed);
+    return cus;
+}
 }  // namespace danet
 
 extern "C" int danet_version(void) { return 100; }

@@ -501,13 +501,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_one_kernel(C3Launch L)
 }
 
 template <int MT, int NT, int KW>
-void launch_one(const C3Launch& L, int grid, size_t lds, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_one_kernel<MT, NT, KW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+int launch_one(const C3Launch& L, int grid, size_t lds, hipStream_t st) {
+    if (int e = danet::raise_dynamic_lds<&conv3x3_one_kernel<MT, NT, KW>>(160 * 1024, "conv3x3_one_kernel")) return e;
     hipLaunchKernelGGL((conv3x3_one_kernel<MT, NT, KW>), dim3((unsigned)grid), dim3(256), lds, st, L);
+    return 0;
 }
 
 // run-time knobs (A-B timing, tests): defaults from the environment, settable through danet_knob (DANET_KNOB_C3_*)
@@ -627,13 +624,14 @@ int conv3x3_config(const ConvP& p, bool vec8, int nprob) {
     return plan(p, q, nprob) > 0 ? q.cfg : 0;
 }
 
-// Launches n (<= 4) problems in one launch.  0 on launch, -1 when the set cannot run on this kernel (nothing is
-// launched then); dry = true only answers that question.
+// Launches n (<= 4) problems in one launch.  0 on launch, -1 when the set cannot run on this kernel, DANET_ERR_HIP (-2) when a
+// HIP call failed (nothing is launched in either case); dry = true only answers that question.
 bool conv3x3_stream_first() { return g_c3_on && g_force.mt == 0; }      // conv3x3_launch offers the problem set to the streamed kernel first
 
 int conv3x3_launch(const ConvP* ps, int n, void* stream, bool dry) {
     if (n < 1 || n > C3_MAXP) return -1;
-    if (g_c3_on && g_force.mt == 0 && conv3x3s_launch(ps, n, stream, dry) == 0) return 0;      // the streamed kernel takes what it can (no forced tiling)
+    const int e = conv3x3_stream_first() ? conv3x3s_launch(ps, n, stream, dry) : -1;      // the streamed kernel takes what it can (no forced tiling)
+    if (e == 0 || e == DANET_ERR_HIP) return e;
     C3Launch L{};
     L.n = n;
     int lds_max = 0, tile0 = 0;
@@ -665,7 +663,7 @@ int conv3x3_launch(const ConvP* ps, int n, void* stream, bool dry) {
     hipStream_t st = (hipStream_t)stream;
     if (n == 1) {
         switch (L.p[0].cfg) {
-#define C3_CASE(M_, N_, K_) case M_ * 100 + N_ * 10 + K_: launch_one<M_, N_, K_>(L, grid, (size_t)lds_max, st); return 0;
+#define C3_CASE(M_, N_, K_) case M_ * 100 + N_ * 10 + K_: return launch_one<M_, N_, K_>(L, grid, (size_t)lds_max, st);
             C3_CASE(8, 3, 1) C3_CASE(8, 3, 2) C3_CASE(8, 3, 4)
             C3_CASE(4, 3, 1) C3_CASE(4, 3, 2) C3_CASE(4, 3, 4)
             C3_CASE(4, 4, 1) C3_CASE(4, 4, 2) C3_CASE(4, 4, 4)
@@ -675,11 +673,7 @@ int conv3x3_launch(const ConvP* ps, int n, void* stream, bool dry) {
             default: return -1;
         }
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ONE);
-        attr_set = true;
-    }
+    if (int e = danet::raise_dynamic_lds<&conv3x3_tile_kernel>(LDS_ONE, "conv3x3_tile_kernel")) return e;
     hipLaunchKernelGGL(conv3x3_tile_kernel, dim3((unsigned)grid), dim3(256), (size_t)lds_max, st, L);
     return 0;
 }

@@ -378,15 +378,9 @@ bool g_c3a_on = getenv("DANET_NO_CONV3X3A") == nullptr;
 
 template <int TW, bool EPI>
 int c3a_launch(const C3aP& p, hipStream_t st) {
-    static bool attr_set = false;
-    static int cus = 0;
-    const void* const fn = EPI ? reinterpret_cast<const void*>(&conv3x3a_bias_kernel<TW>) : reinterpret_cast<const void*>(&conv3x3a_kernel<TW>);
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<TW>::LDS);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        attr_set = true;
-    }
+    if (int e = EPI ? danet::raise_dynamic_lds<&conv3x3a_bias_kernel<TW>>(Geo<TW>::LDS, "conv3x3a_bias_kernel")
+                    : danet::raise_dynamic_lds<&conv3x3a_kernel<TW>>(Geo<TW>::LDS, "conv3x3a_kernel")) return e;
+    const int cus = danet::compute_units();
     const int grid = p.ntiles < cus ? p.ntiles : cus;
     if (EPI) hipLaunchKernelGGL(conv3x3a_bias_kernel<TW>, dim3((unsigned)grid), dim3(256), (size_t)Geo<TW>::LDS, st, p);
     else hipLaunchKernelGGL(conv3x3a_kernel<TW>, dim3((unsigned)grid), dim3(256), (size_t)Geo<TW>::LDS, st, p);
@@ -425,8 +419,8 @@ extern "C" int danet_conv3x3a(const void* x, const void* wp, void* y, int B, int
     p.addend = (const bf16_t*)addend;
     p.B = B; p.H = H; p.W = W; p.mirrored = transposed ? 1 : 0;
     p.bytes = (int)((long)B * H * W * 128);
-    if (W == 16) { p.strips = H / 16; p.ntiles = B * p.strips; c3a_launch<16, false>(p, (hipStream_t)stream); }
-    else { p.strips = H / 4; p.ntiles = B * p.strips; c3a_launch<64, false>(p, (hipStream_t)stream); }
+    p.strips = W == 16 ? H / 16 : H / 4; p.ntiles = B * p.strips;
+    if (int e = W == 16 ? c3a_launch<16, false>(p, (hipStream_t)stream) : c3a_launch<64, false>(p, (hipStream_t)stream)) return e;
     DANET_CHECK_LAUNCH("conv3x3a_kernel");
     return DANET_OK;
 }
@@ -445,8 +439,8 @@ extern "C" int danet_conv3x3a_forward_epi(const void* x, const void* wp, const f
     p.addend = (const bf16_t*)addend; p.bias = bias; p.relu = relu ? 1 : 0;
     p.B = B; p.H = H; p.W = W; p.mirrored = 0;
     p.bytes = (int)((long)B * H * W * 128);
-    if (W == 16) { p.strips = H / 16; p.ntiles = B * p.strips; c3a_launch<16, true>(p, (hipStream_t)stream); }
-    else { p.strips = H / 4; p.ntiles = B * p.strips; c3a_launch<64, true>(p, (hipStream_t)stream); }
+    p.strips = W == 16 ? H / 16 : H / 4; p.ntiles = B * p.strips;
+    if (int e = W == 16 ? c3a_launch<16, true>(p, (hipStream_t)stream) : c3a_launch<64, true>(p, (hipStream_t)stream)) return e;
     DANET_CHECK_LAUNCH("conv3x3a_bias_kernel");
     return DANET_OK;
 }

@@ -1197,29 +1197,23 @@ void s3_assign(S3Launch& L, int grid) {
 }
 
 template <int NT>
-void s3_launch_nt(const S3Launch& L, int grid, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_stream_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, S3_LDS);
-        attr_set = true;
-    }
+int s3_launch_nt(const S3Launch& L, int grid, hipStream_t st) {
+    if (int e = danet::raise_dynamic_lds<&conv3x3_stream_kernel<NT>>(S3_LDS, "conv3x3_stream_kernel")) return e;
     hipLaunchKernelGGL((conv3x3_stream_kernel<NT>), dim3((unsigned)grid), dim3(S3_THREADS), (size_t)S3_LDS, st, L);
+    return 0;
 }
 template <int NT>
-void s3_launch_nt(const S3LaunchBn& L, int grid, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_stream_bn_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, S3_LDS);
-        attr_set = true;
-    }
+int s3_launch_nt(const S3LaunchBn& L, int grid, hipStream_t st) {
+    if (int e = danet::raise_dynamic_lds<&conv3x3_stream_bn_kernel<NT>>(S3_LDS, "conv3x3_stream_bn_kernel")) return e;
     hipLaunchKernelGGL((conv3x3_stream_bn_kernel<NT>), dim3((unsigned)grid), dim3(S3_THREADS), (size_t)S3_LDS, st, L);
+    return 0;
 }
 template <typename LaunchT>
 int s3_launch_any(int NT, const LaunchT& L, int grid, hipStream_t st) {
     switch (NT) {
-        case 1: s3_launch_nt<1>(L, grid, st); return 0;
-        case 2: s3_launch_nt<2>(L, grid, st); return 0;
-        case 3: s3_launch_nt<3>(L, grid, st); return 0;
+        case 1: return s3_launch_nt<1>(L, grid, st);
+        case 2: return s3_launch_nt<2>(L, grid, st);
+        case 3: return s3_launch_nt<3>(L, grid, st);
         default: return -1;
     }
 }
@@ -1228,8 +1222,8 @@ int s3_launch_any(int NT, const LaunchT& L, int grid, hipStream_t st) {
 
 namespace danet_conv {
 
-// n (<= 4) problems in one launch of the streamed kernel.  0 on launch, -1 when the set cannot run here (nothing is
-// launched then); dry = true only answers that question.
+// n (<= 4) problems in one launch of the streamed kernel.  0 on launch, -1 when the set cannot run here, DANET_ERR_HIP (-2) when a
+// HIP call failed (nothing is launched in either case); dry = true only answers that question.
 int conv3x3s_launch(const ConvP* ps, int n, void* stream, bool dry) {
     if (n < 1 || n > S3_MAXP) return -1;
     S3Launch L{};

@@ -423,7 +423,7 @@ bool supported(const ConvF& p) {
 }
 
 template <int MT, int NT>
-void launch(const ConvF& p, hipStream_t st) {
+int launch(const ConvF& p, hipStream_t st) {
     long mblk = p.M;
     int nz = p.groups;
     if (p.parity) {
@@ -432,11 +432,10 @@ void launch(const ConvF& p, hipStream_t st) {
     }
     const dim3 grid((unsigned)((mblk + 64 * MT - 1) / (64 * MT)), (unsigned)(p.Cout_pad / (16 * NT)), (unsigned)nz);
     const size_t lds = (size_t)(p.Kp / 4) * sizeof(i32x2);
-    if (lds > 60 * 1024) {                                   // once per instantiation: the 160 KB of a gfx950 compute unit are opt-in above 64 KB
-        static bool raised = false;
-        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f32m_kernel<MT, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); raised = true; }
-    }
+    if (lds > 60 * 1024)                                     // the 160 KB of a gfx950 compute unit are opt-in above 64 KB
+        if (int e = danet::raise_dynamic_lds<&conv_f32m_kernel<MT, NT>>(128 * 1024, "conv_f32m_kernel")) return e;
     hipLaunchKernelGGL((conv_f32m_kernel<MT, NT>), grid, dim3(256), lds, st, p);
+    return 0;
 }
 
 bool wg_plan(WgF& p, int B, int H, int W, int Cin, int OH, int OW, int Cout, int R, int S, int stride, int pad, int dil, int groups,
@@ -532,7 +531,7 @@ extern "C" int danet_conv_f32m_forward(const float* x, const float* wp, const fl
     const long mblk = p.parity ? (long)p.B * ((p.OH + p.stride - 1) / p.stride) * ((p.OW + p.stride - 1) / p.stride) : p.M;
     const int mt = f32m_mt(mblk, p.Cout_pad / (16 * nt), p.groups * (p.parity ? p.stride * p.stride : 1));
     hipStream_t st = (hipStream_t)stream;
-#define F32M_CASE(M_, N_) if (mt == M_ && nt == N_) { launch<M_, N_>(p, st); } else
+#define F32M_CASE(M_, N_) if (mt == M_ && nt == N_) { if (int e = launch<M_, N_>(p, st)) return e; } else
     F32M_CASE(1, 1) F32M_CASE(2, 1) F32M_CASE(4, 1) F32M_CASE(1, 2) F32M_CASE(2, 2) F32M_CASE(4, 2)
     F32M_CASE(1, 3) F32M_CASE(2, 3) F32M_CASE(4, 3) F32M_CASE(1, 4) F32M_CASE(2, 4) F32M_CASE(4, 4)
     return danet::fail(DANET_ERR_ARG, "conv_f32m_forward: no kernel for tiles %dx%d", mt, nt);

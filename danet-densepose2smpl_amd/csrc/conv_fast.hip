@@ -383,7 +383,7 @@ __global__ __launch_bounds__(256) void conv_fast_multi_kernel(ConvMulti m)
 }
 
 template <int MT, int NT>
-void launch_fast(const ConvP& p, hipStream_t st) {
+int launch_fast(const ConvP& p, hipStream_t st) {
     long mblk = p.M;
     int nz = p.groups;
     if (p.parity) {
@@ -392,14 +392,10 @@ void launch_fast(const ConvP& p, hipStream_t st) {
     }
     const dim3 grid((unsigned)((mblk + 64 * MT - 1) / (64 * MT)), (unsigned)(p.Cout_pad / (16 * NT)), (unsigned)nz);
     const size_t lds = (size_t)(p.Kp / 8) * sizeof(i32x2) + (MT == 1 ? (size_t)2 * 8 * NT * 1024 : 0);
-    if (MT == 1) {
-        static bool attr_set = false;          // more than the default 64 KB of dynamic LDS
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_fast_kernel<MT, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            attr_set = true;
-        }
-    }
+    if (MT == 1)                               // more than the default 64 KB of dynamic LDS
+        if (int e = danet::raise_dynamic_lds<&conv_fast_kernel<MT, NT>>(96 * 1024, "conv_fast_kernel")) return e;
     hipLaunchKernelGGL((conv_fast_kernel<MT, NT>), grid, dim3(256), lds, st, p);
+    return 0;
 }
 
 const bool g_no_fast = getenv("DANET_CONV_NO_FAST") != nullptr;     // A-B timing knob
@@ -423,14 +419,14 @@ bool conv_fast_ok(const ConvP& p, bool vec8, int mt) {
 
 int conv_fast_launch(const ConvP& p, int mt, int nt, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-#define FAST_CASE(M_, N_) if (mt == M_ && nt == N_) { launch_fast<M_, N_>(p, st); return 0; }
+#define FAST_CASE(M_, N_) if (mt == M_ && nt == N_) return launch_fast<M_, N_>(p, st);
     FAST_CASE(1, 1) FAST_CASE(2, 1) FAST_CASE(4, 1) FAST_CASE(1, 2) FAST_CASE(2, 2) FAST_CASE(4, 2)
     FAST_CASE(1, 3) FAST_CASE(2, 3) FAST_CASE(4, 3) FAST_CASE(1, 4) FAST_CASE(2, 4) FAST_CASE(4, 4)
 #undef FAST_CASE
     return -1;
 }
 
-// All problems must pass conv_fast_ok and share NT.  Returns 0 on launch, -1 if the set is not supported.
+// All problems must pass conv_fast_ok and share NT.  Returns 0 on launch, -1 if the set is not supported, DANET_ERR_HIP (-2) when a HIP call failed.
 int conv_fast_launch_multi(const ConvP* ps, const int* mts, int n, int nt, void* stream) {
     if (n < 1 || n > NCM) return -1;
     ConvMulti m;
@@ -461,8 +457,7 @@ int conv_fast_launch_multi(const ConvP* ps, const int* mts, int n, int nt, void*
     }
     hipStream_t st = (hipStream_t)stream;
 #define MULTI_CASE(N_) if (nt == N_) { \
-        static bool attr_set = false; \
-        if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_fast_multi_kernel<N_>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr_set = true; } \
+        if (int e = danet::raise_dynamic_lds<&conv_fast_multi_kernel<N_>>(96 * 1024, "conv_fast_multi_kernel")) return e; \
         hipLaunchKernelGGL((conv_fast_multi_kernel<N_>), dim3((unsigned)m.start[n]), dim3(256), lds, st, m); return 0; }
     MULTI_CASE(1) MULTI_CASE(2) MULTI_CASE(3) MULTI_CASE(4)
 #undef MULTI_CASE

@@ -160,8 +160,7 @@ int g3_launch(const ConvP& p, void* stream)
     using C = G3Cfg<CIN>;
     const int nband = (p.H + C::TH - 1) / C::TH;
     const size_t lds = (size_t)(C::TH + 2) * (p.W + 2) * C::PS + 16;
-    static bool raised = false;
-    if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_g3_kernel<CIN, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); raised = true; }
+    if (int e = danet::raise_dynamic_lds<&conv_g3_kernel<CIN, MT>>(80 * 1024, "conv_g3_kernel")) return e;
     hipLaunchKernelGGL((conv_g3_kernel<CIN, MT>), dim3((unsigned)(p.B * p.groups * nband)), dim3(256), lds, (hipStream_t)stream, p);
     return 0;
 }

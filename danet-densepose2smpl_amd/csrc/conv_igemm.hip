@@ -688,27 +688,28 @@ extern "C" int danet_conv_forward(const void* x, const void* wp, const float* bi
     hipStream_t st = (hipStream_t)stream;
     if (conv_g3_ok(p, vec8)) {
         // the 24-group partial-IUV head and its data gradient (csrc/conv_g3.hip): one (image, group, row band) per workgroup
-        if (conv_g3_launch(p, stream) != 0) return danet::fail(DANET_ERR_ARG, "conv_forward: no narrow-group instantiation");
+        DANET_CHECK_LAUNCHER(conv_g3_launch(p, stream), "conv_forward: no narrow-group instantiation");
         DANET_CHECK_LAUNCH("conv_g3_kernel");
         return DANET_OK;
     }
     if (c3) {
-        if (conv3x3_launch(&p, 1, stream) != 0) return danet::fail(DANET_ERR_ARG, "conv_forward: no 3x3 tiling");
+        DANET_CHECK_LAUNCHER(conv3x3_launch(&p, 1, stream), "conv_forward: no 3x3 tiling");
         DANET_CHECK_LAUNCH("conv3x3_tile_kernel");
         return DANET_OK;
     }
     if (pw) {
-        if (conv_pw_launch(p, stream) != 0) return danet::fail(DANET_ERR_ARG, "conv_forward: no pointwise instantiation");
+        DANET_CHECK_LAUNCHER(conv_pw_launch(p, stream), "conv_forward: no pointwise instantiation");
         DANET_CHECK_LAUNCH("conv_pw_kernel");
         return DANET_OK;
     }
-    if (p.groups > 1 && vec8 && !p.bn_red && conv3x3_stream_first() && conv3x3s_launch(&p, 1, stream, false) == 0) {
+    if (p.groups > 1 && vec8 && !p.bn_red && conv3x3_stream_first()) {
         // grouped 3x3 / stride-1 layers (the 24-group partial-IUV head): one group's channels of a pixel tile per tile of the streamed kernel
-        DANET_CHECK_LAUNCH("conv3x3_stream_kernel");
-        return DANET_OK;
+        const int e = conv3x3s_launch(&p, 1, stream, false);
+        if (e == 0) DANET_CHECK_LAUNCH("conv3x3_stream_kernel");
+        if (e == 0 || e == DANET_ERR_HIP) return e;
     }
     if (conv_fast_ok(p, vec8, mt)) {
-        if (conv_fast_launch(p, mt, nt, stream) != 0) return danet::fail(DANET_ERR_ARG, "conv_forward: no fast kernel for tiles %dx%d", mt, nt);
+        DANET_CHECK_LAUNCHER(conv_fast_launch(p, mt, nt, stream), "conv_forward: no fast kernel for tiles %dx%d", mt, nt);
         DANET_CHECK_LAUNCH("conv_fast_kernel");
         return DANET_OK;
     }
@@ -830,7 +831,9 @@ extern "C" int danet_conv_bn_forward_multi(const void* jobs, int n, const void* 
     if (fused) *fused = 0;
     if (conv_bn_fusable((const ConvJob*)jobs, n, (const BnFwdJobC*)bn_jobs, ps, ba, momentum, eps, bar) > 0) {
         for (int i = 0; i < n; ++i) DANET_CHECK_ARG(ps[i].x && ps[i].w && ps[i].y, "conv_bn_forward_multi: job %d: null pointer", i);
-        if (conv3x3s_launch(ps, n, stream, false) == 0) {              // (-1: e.g. a tap table that is new while the stream captures)
+        const int e = conv3x3s_launch(ps, n, stream, false);            // (-1: e.g. a tap table that is new while the stream captures)
+        if (e == DANET_ERR_HIP) return e;
+        if (e == 0) {
             DANET_CHECK_LAUNCH("conv3x3_stream_bn_kernel");
             if (fused) *fused = 1;
             return DANET_OK;
@@ -852,11 +855,11 @@ extern "C" int danet_conv_forward_multi(const void* jobs, int n, void* stream)
         DANET_CHECK_ARG(!ps[i].bn_red || (ps[i].bn_x && ps[i].bn_saved), "conv_forward_multi: job %d: incomplete BatchNorm-backward arguments", i);
     }
     if (all3) {
-        DANET_CHECK_ARG(conv3x3_launch(ps, n, stream) == 0, "conv_forward_multi: no 3x3 tiling");
+        DANET_CHECK_LAUNCHER(conv3x3_launch(ps, n, stream), "conv_forward_multi: no 3x3 tiling");
         DANET_CHECK_LAUNCH("conv3x3_tile_kernel");
         return DANET_OK;
     }
-    DANET_CHECK_ARG(conv_fast_launch_multi(ps, mts, n, nt, stream) == 0, "conv_forward_multi: no kernel for %d tiles per block", nt);
+    DANET_CHECK_LAUNCHER(conv_fast_launch_multi(ps, mts, n, nt, stream), "conv_forward_multi: no kernel for %d tiles per block", nt);
     DANET_CHECK_LAUNCH("conv_fast_multi_kernel");
     return DANET_OK;
 }
@@ -896,11 +899,11 @@ extern "C" int danet_conv_forward_multi_epi(const void* jobs, int n, void* strea
     DANET_CHECK_ARG(conv_multi_prepare_epi(jobs, n, ps, mts, &nt, &all3) == 0, "conv_forward_multi_epi: unsupported set (see danet_conv_forward_multi_epi_ok)");
     for (int i = 0; i < n; ++i) DANET_CHECK_ARG(ps[i].x && ps[i].w && ps[i].y, "conv_forward_multi_epi: job %d: null pointer", i);
     if (all3) {
-        DANET_CHECK_ARG(conv3x3_launch(ps, n, stream) == 0, "conv_forward_multi_epi: no 3x3 tiling");
+        DANET_CHECK_LAUNCHER(conv3x3_launch(ps, n, stream), "conv_forward_multi_epi: no 3x3 tiling");
         DANET_CHECK_LAUNCH("conv3x3_tile_kernel");
         return DANET_OK;
     }
-    DANET_CHECK_ARG(conv_fast_launch_multi(ps, mts, n, nt, stream) == 0, "conv_forward_multi_epi: no kernel for %d tiles per block", nt);
+    DANET_CHECK_LAUNCHER(conv_fast_launch_multi(ps, mts, n, nt, stream), "conv_forward_multi_epi: no kernel for %d tiles per block", nt);
     DANET_CHECK_LAUNCH("conv_fast_multi_kernel");
     return DANET_OK;
 }

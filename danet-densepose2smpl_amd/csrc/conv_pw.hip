@@ -257,16 +257,9 @@ bool pw_plan(const ConvP& p, PwPlan& pl) {
 
 // Workgroups: persistent, as many as are resident at once (registers and the layer's LDS footprint decide: 2 .. 8 per compute unit)
 template <int NKS, int NTB>
-void pw_launch_t(const PwP& q, size_t lds, hipStream_t st) {
-    static bool attr_set = false;
+int pw_launch_t(const PwP& q, size_t lds, hipStream_t st) {
     static int per_cu[3] = {0, 0, 0};                 // by LDS class: <= 16 KB, <= 32 KB, more
-    static int cus = 0;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pw_kernel<NKS, NTB>), hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS_MAX + 4096);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        attr_set = true;
-    }
+    if (int e = danet::raise_dynamic_lds<&conv_pw_kernel<NKS, NTB>>(PW_LDS_MAX + 4096, "conv_pw_kernel")) return e;
     const int cls = lds <= 16 * 1024 ? 0 : (lds <= 32 * 1024 ? 1 : 2);
     if (per_cu[cls] == 0) {
         int n = 0;
@@ -274,8 +267,9 @@ void pw_launch_t(const PwP& q, size_t lds, hipStream_t st) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&conv_pw_kernel<NKS, NTB>), 256, probe) != hipSuccess || n < 1) { (void)hipGetLastError(); n = 2; }
         per_cu[cls] = n > 8 ? 8 : n;
     }
-    const int cap = cus * per_cu[cls];
+    const int cap = danet::compute_units() * per_cu[cls];
     hipLaunchKernelGGL((conv_pw_kernel<NKS, NTB>), dim3((unsigned)(q.niter < cap ? q.niter : cap)), dim3(256), lds, st, q);
+    return 0;
 }
 
 }  // namespace
@@ -313,7 +307,7 @@ int conv_pw_launch(const ConvP& p, void* stream) {
     q.x_bytes = (int)p.x_bytes; q.y_bytes = (int)p.y_bytes;
     const size_t lds = (size_t)q.NB * q.nks * 1024 + 4 * 2 * 4 * 16 * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-#define PW_CASE(K_, N_) if (pl.nks_t == K_ && pl.ntb == N_) { pw_launch_t<K_, N_>(q, lds, st); return 0; }
+#define PW_CASE(K_, N_) if (pl.nks_t == K_ && pl.ntb == N_) { return pw_launch_t<K_, N_>(q, lds, st); }
     PW_CASE(2, 1) PW_CASE(2, 2) PW_CASE(2, 3) PW_CASE(2, 4)
     PW_CASE(4, 1) PW_CASE(4, 2) PW_CASE(4, 3) PW_CASE(4, 4)
     PW_CASE(8, 1) PW_CASE(8, 2) PW_CASE(8, 3) PW_CASE(8, 4)

@@ -301,7 +301,7 @@ size_t conv_pw_wgrad_ws_floats(const WgJob* jobs, const int* idx, int cnt, long 
 }
 
 // Launches the problems idx[0..cnt) (all conv_pw_wgrad_ok) in groups that share an instantiation; ws: scratch of
-// conv_pw_wgrad_ws_floats floats (need not be zeroed).  0 on success.
+// conv_pw_wgrad_ws_floats floats (need not be zeroed).  0 on success, -1 without an instantiation, DANET_ERR_HIP (-2) when a HIP call failed.
 int conv_pw_wgrad_launch(const WgJob* jobs, const int* idx, int cnt, float* ws, float beta, long target, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     long total_px = 0;
@@ -341,8 +341,7 @@ int conv_pw_wgrad_launch(const WgJob* jobs, const int* idx, int cnt, float* ws, 
         }
         const dim3 grid((unsigned)mp.start[mp.n]);
 #define PWG_CASE(A_, B_, C_) if (pl0.nbw_t == A_ && pl0.kbw_t == B_ && pl0.nkc == C_) { \
-            static bool attr_set = false; \
-            if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pw_wgrad_kernel<A_, B_, C_>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr_set = true; } \
+            if (int e = danet::raise_dynamic_lds<&conv_pw_wgrad_kernel<A_, B_, C_>>(96 * 1024, "conv_pw_wgrad_kernel")) return e; \
             hipLaunchKernelGGL((conv_pw_wgrad_kernel<A_, B_, C_>), grid, dim3(256), lds, st, mp); } else
         PWG_CASE(1, 1, 2) PWG_CASE(1, 2, 2) PWG_CASE(1, 4, 2) PWG_CASE(1, 8, 2)
         PWG_CASE(2, 1, 2) PWG_CASE(2, 2, 2) PWG_CASE(2, 4, 2)
@@ -351,9 +350,9 @@ int conv_pw_wgrad_launch(const WgJob* jobs, const int* idx, int cnt, float* ws, 
         PWG_CASE(2, 1, 1) PWG_CASE(2, 2, 1) PWG_CASE(2, 4, 1) PWG_CASE(2, 8, 1) PWG_CASE(4, 1, 1) PWG_CASE(4, 2, 1) PWG_CASE(4, 4, 1)
         return -1;
 #undef PWG_CASE
-        if (hipGetLastError() != hipSuccess) return -2;
+        DANET_CHECK_LAUNCH("conv_pw_wgrad_kernel");
         hipLaunchKernelGGL(conv_pw_wgrad_reduce_kernel, dim3((unsigned)danet::cdiv(rp.start[rp.n] * 8, 256)), dim3(256), 0, st, rp);
-        if (hipGetLastError() != hipSuccess) return -2;
+        DANET_CHECK_LAUNCH("conv_pw_wgrad_reduce_kernel");
     }
     return 0;
 }

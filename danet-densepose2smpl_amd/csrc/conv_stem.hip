@@ -416,14 +416,8 @@ extern "C" int danet_conv_stem_forward(const void* x, const void* wp, void* y, i
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.OH = OH;
     p.nslab = Cin / 16; p.strips = OH / ST_TH; p.ntiles = B * p.strips;
     p.x_bytes = (int)((long)B * H * W * Cin * 2); p.y_bytes = (int)((long)B * OH * OW * Cout * 2);
-    static bool attr_set = false;
-    static int cus = 0;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_stem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        attr_set = true;
-    }
+    if (int e = danet::raise_dynamic_lds<&conv_stem_kernel>(ST_LDS, "conv_stem_kernel")) return e;
+    const int cus = danet::compute_units();
     const int grid = p.ntiles < cus ? p.ntiles : cus;
     hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)grid), dim3(256), (size_t)ST_LDS, (hipStream_t)stream, p);
     DANET_CHECK_LAUNCH("conv_stem_kernel");
@@ -444,14 +438,8 @@ extern "C" int danet_conv_stem_forward_epi(const void* x, const void* wp, const 
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.OH = OH;
     p.nslab = Cin / 16; p.strips = OH / ST_TH; p.ntiles = B * p.strips;
     p.x_bytes = (int)((long)B * H * W * Cin * 2); p.y_bytes = (int)((long)B * OH * OW * Cout * 2);
-    static bool attr_set = false;
-    static int cus = 0;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_stem_bias_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        attr_set = true;
-    }
+    if (int e = danet::raise_dynamic_lds<&conv_stem_bias_kernel>(ST_LDS, "conv_stem_bias_kernel")) return e;
+    const int cus = danet::compute_units();
     const int grid = p.ntiles < cus ? p.ntiles : cus;
     hipLaunchKernelGGL(conv_stem_bias_kernel, dim3((unsigned)grid), dim3(256), (size_t)ST_LDS, (hipStream_t)stream, p, bias, relu ? 1 : 0);
     DANET_CHECK_LAUNCH("conv_stem_bias_kernel");

@@ -370,14 +370,8 @@ extern "C" int danet_conv_stem_dgrad(const void* dy, const void* wp, void* dx, i
     p.B = B; p.H = H; p.W = W; p.OH = OH;
     p.strips = OH / SD_TH; p.ntiles = B * p.strips;
     p.dy_bytes = (int)((long)B * OH * OW * Cout * 2); p.dx_bytes = (int)((long)B * H * W * Cin * 2);
-    static bool attr_set = false;
-    static int cus = 0;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_stem_dgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SD_LDS);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        attr_set = true;
-    }
+    if (int e = danet::raise_dynamic_lds<&conv_stem_dgrad_kernel>(SD_LDS, "conv_stem_dgrad_kernel")) return e;
+    const int cus = danet::compute_units();
     const int grid = p.ntiles < cus ? p.ntiles : cus;
     hipLaunchKernelGGL(conv_stem_dgrad_kernel, dim3((unsigned)grid), dim3(256), (size_t)SD_LDS, (hipStream_t)stream, p);
     DANET_CHECK_LAUNCH("conv_stem_dgrad_kernel");

@@ -336,7 +336,7 @@ extern "C" int danet_conv_wgrad(const void* x, const void* dy, float* dw, float*
         const int one = 0;
         if (conv_pw_wgrad_ok(job) && conv_pw_wgrad_ws_floats(&job, &one, 1, PW_WGRAD_BLOCKS) <= ws_floats) {
             // (a workspace sized by danet_conv_wgrad_ws_floats_for: the pointwise kernel's partial sums; need not be zeroed)
-            if (conv_pw_wgrad_launch(&job, &one, 1, ws, beta, PW_WGRAD_BLOCKS, stream) != 0) return danet::fail(DANET_ERR_HIP, "conv_wgrad: pointwise launch failed");
+            DANET_CHECK_LAUNCHER(conv_pw_wgrad_launch(&job, &one, 1, ws, beta, PW_WGRAD_BLOCKS, stream), "conv_wgrad: no pointwise instantiation");
             return DANET_OK;
         }
     }
@@ -416,7 +416,7 @@ static int wg_multi(const WgJob* jobs, int n, float* ws, size_t ws_floats, float
             const size_t need = conv_pw_wgrad_ws_floats(jobs, idx, cnt, PW_WGRAD_BLOCKS);
             if (ws) {
                 if (need > ws_floats) return danet::fail(DANET_ERR_WORKSPACE, "conv_wgrad_multi: workspace too small");
-                if (conv_pw_wgrad_launch(jobs, idx, cnt, ws, beta, PW_WGRAD_BLOCKS, st) != 0) return danet::fail(DANET_ERR_HIP, "conv_wgrad_multi: pointwise launch failed");
+                DANET_CHECK_LAUNCHER(conv_pw_wgrad_launch(jobs, idx, cnt, ws, beta, PW_WGRAD_BLOCKS, st), "conv_wgrad_multi: no pointwise instantiation");
             }
             used += need;
         }

@@ -704,8 +704,7 @@ extern "C" int danet_gcn_tail_forward(const void* args, void* stream)
     const TailArgs* a = (const TailArgs*)args;
     if (int e = tail_check(a, "gcn_tail_forward")) return e;
     DANET_CHECK_ARG(a->jr0 && a->jp0 && a->jp1 && a->pose, "gcn_tail_forward: missing outputs");
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gcn_tail_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SM_FLOATS * 4); attr = true; }
+    if (int e = danet::raise_dynamic_lds<&gcn_tail_fwd_kernel>(SM_FLOATS * 4, "gcn_tail_fwd_kernel")) return e;
     hipLaunchKernelGGL(gcn_tail_fwd_kernel, dim3(NJ), dim3(NT), SM_FLOATS * 4, (hipStream_t)stream, *a);
     DANET_CHECK_LAUNCH("gcn_tail_fwd_kernel");
     return DANET_OK;
@@ -721,8 +720,7 @@ extern "C" int danet_gcn_tail_backward(const void* args, void* stream)
         DANET_CHECK_ARG(a->gW[l] && a->gb[l] && a->ggamma[l] && a->gbeta[l], "gcn_tail_backward: layer %d lacks a gradient buffer", l);
     for (int i = 0; i < 2; ++i)
         DANET_CHECK_ARG(a->gWp[i] && a->gbp[i] && a->gWc[i] && a->gbc[i], "gcn_tail_backward: head %d lacks a gradient buffer", i);
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gcn_tail_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SM_FLOATS_BWD * 4); attr = true; }
+    if (int e = danet::raise_dynamic_lds<&gcn_tail_bwd_kernel>(SM_FLOATS_BWD * 4, "gcn_tail_bwd_kernel")) return e;
     hipLaunchKernelGGL(gcn_tail_bwd_kernel, dim3(NJ), dim3(NT), SM_FLOATS_BWD * 4, (hipStream_t)stream, *a);
     DANET_CHECK_LAUNCH("gcn_tail_bwd_kernel");
     return DANET_OK;

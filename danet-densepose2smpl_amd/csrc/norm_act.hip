@@ -1370,12 +1370,8 @@ extern "C" int danet_bn_backward_onepass(const void* jobs, int n, void* bar, int
 {
     DANET_ENTER();
     BnOnePass ms[NBM];
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bn_bwd_onepass_kernel<OP_NV>), hipFuncAttributeMaxDynamicSharedMemorySize, OP_NL * 256 * 17);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bn_bwd_onepass_kernel<OP_NV_BIG>), hipFuncAttributeMaxDynamicSharedMemorySize, OP_NL * 256 * 17);
-        attr_set = true;
-    }
+    if (int e = danet::raise_dynamic_lds<&bn_bwd_onepass_kernel<OP_NV>>(OP_NL * 256 * 17, "bn_bwd_onepass_kernel<OP_NV>")) return e;
+    if (int e = danet::raise_dynamic_lds<&bn_bwd_onepass_kernel<OP_NV_BIG>>(OP_NL * 256 * 17, "bn_bwd_onepass_kernel<OP_NV_BIG>")) return e;
     const int nl = onepass_plan((const BnBwdJob*)jobs, n, ms, max_blocks);
     DANET_CHECK_ARG(bar && nl > 0, "bn_backward_onepass: the job set does not qualify (see danet_bn_backward_onepass_ok)");
     for (int l = 0; l < nl; ++l) {

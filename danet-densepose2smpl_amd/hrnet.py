@@ -14,7 +14,7 @@ from . import segments
 from .config import cfg
 from .nn import fan_out, fan_out_multi, sum_relu, sum_relu_multi, multi_batch_norm, multi_conv_bn
 from .resnet import BasicBlock, Bottleneck, ConvBN, IUV_predict_layer, make_res_layer, BN_MOMENTUM
-from .nn import Conv2d, BatchNorm2d
+from .nn import Conv2d, BatchNorm2d, SideBranch, side_streams
 from .conv import multi_conv, ResLink
 
 blocks_dict = {'BASIC': BasicBlock, 'BOTTLENECK': Bottleneck}
@@ -40,15 +40,6 @@ FUSE_GROUP = int(os.environ.get('DANET_FUSE_GROUP', '12'))    # exchange paths p
 FUSE_SPLIT_RELU = bool(int(os.environ.get('DANET_FUSE_SPLIT_RELU', '0')))       # A-B knob: 1 = ReLU and non-ReLU exchange stages in separate launches (rounds 2-4)
 SUM_MULTI = bool(int(os.environ.get('DANET_SUM_MULTI', '1')))       # a module's fuse sums (and their gradients) in one launch each
 BRANCH_STREAMS = False      # run the low-resolution branches on side streams (set by the trainer's hipGraph capture)
-_SIDE = {}
-
-
-def _side_streams(device, n):
-    key = (device.index, torch.cuda.current_stream(device).stream_id)
-    pool = _SIDE.setdefault(key, [])
-    while len(pool) < n:
-        pool.append(torch.cuda.Stream(device=device))
-    return pool[:n]
 
 
 class HighResolutionModule(nn.Module):
@@ -121,16 +112,14 @@ class HighResolutionModule(nn.Module):
         chip-filling one) stays on the current stream, the low-resolution branches -- whose kernels
         launch far fewer workgroups than there are CUs -- run beside it on side streams.  Autograd
         replays each branch's backward on the stream its forward ran on."""
-        cur = torch.cuda.current_stream(x[0].device)
-        side = _side_streams(x[0].device, self.num_branches - 1)
+        side = [SideBranch(s) for s in side_streams(x[0].device, self.num_branches - 1)]
         out = [None] * self.num_branches
         for i in range(1, self.num_branches):
-            side[i - 1].wait_stream(cur)
-            with torch.cuda.stream(side[i - 1]):
+            with side[i - 1].fork():
                 out[i] = self.branches[i](x[i])
         out[0] = self.branches[0](x[0])
-        for i in range(1, self.num_branches):
-            cur.wait_stream(side[i - 1])
+        for br in side:
+            br.join()
         return out
 
     def forward(self, x):

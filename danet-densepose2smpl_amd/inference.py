@@ -477,12 +477,11 @@ class InferenceEngine(object):
 
     def _capture(self, image, warmup=2):
         self._static_in = image.detach().clone()
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
+        side = _nn.SideBranch(torch.cuda.Stream(device=self.device))
+        with side.fork():
             for _ in range(warmup):
                 self._forward(self._static_in)
-        torch.cuda.current_stream(self.device).wait_stream(side)
+        side.join()
         torch.cuda.synchronize(self.device)
         self._pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()

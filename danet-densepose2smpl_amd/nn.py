@@ -1,5 +1,6 @@
 """Layer modules on the HIP kernels, with nn.Module parameter/buffer names identical to the
 reference's torch modules (state-dict compatible)."""
+import contextlib
 import ctypes
 
 import os
@@ -32,7 +33,7 @@ ONEPASS_STREAM = None
 # could wait for ever (include/danet_hip.h, danet_bn_backward_onepass).
 ONEPASS_MAX_BLOCKS = 0
 # > 0 while another stream of the step may be running kernels beside the one-pass stream (the regressor's body_net branch between its fork
-# and its join, in the forward and in the backward pass: smpl_regressor.SideWindow).  A one-pass launch of more than ONE workgroup per
+# and its join, in the forward and in the backward pass: SideBranch(window=True) below).  A one-pass launch of more than ONE workgroup per
 # compute unit is then not safe: each workgroup takes 78 KB of a compute unit's 160 KB of LDS, and a block of LDS that a workgroup of the
 # other stream held while the first one-pass workgroup was placed can leave the remaining space in two pieces that are each too small
 # for the second -- for as long as the first one spins at the barrier, i.e. until the barrier's spin bound (round 6: a 492-workgroup
@@ -133,16 +134,106 @@ def onepass_recover(device=None, force=False):
     takes over); returns True when there was an error to recover from.  Steps computed since the time-out are garbage:
     the caller decides what to redo (trainer.Trainer re-captures its graph and raises).  force: another data-parallel rank
     reported the time-out (the all-reduced poison word): switch this rank over as well, so that all replicas keep running
-    the same kernels."""
-    global ONEPASS
+    the same kernels.  Also closes the side-stream window (SIDE_LIVE = 0): a backward pass that raised inside it cannot be
+    bracketed from the forward -- besides Trainer._core this is the only place that resets the counter."""
+    global ONEPASS, SIDE_LIVE
     if not (onepass_error(device) or force):
         return False
     torch.cuda.synchronize()
+    SIDE_LIVE = 0
     for d, b in _ONEPASS_BAR.items():
         if _on_device(d, device):
             b.zero_()
     ONEPASS = False
     return True
+
+
+_SIDE = {}
+
+
+def side_streams(device, n):
+    """n side streams of the pool that belongs to (device, the current stream)."""
+    key = (device.index, torch.cuda.current_stream(device).stream_id)
+    pool = _SIDE.setdefault(key, [])
+    while len(pool) < n:
+        pool.append(torch.cuda.Stream(device=device))
+    return pool[:n]
+
+
+class _SideWindowOpen(torch.autograd.Function):
+    """Identity on the joined result of the two branches: its backward is the FIRST node of their backward pass and opens the
+    side-stream window (SIDE_LIVE) -- from here on the side branch's backward kernels run beside the main one's."""
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        global SIDE_LIVE
+        SIDE_LIVE += 1
+        return g
+
+
+class _SideWindowClose(torch.autograd.Function):
+    """Identity on the two branches' inputs: its backward runs when BOTH branches have delivered their input gradients and closes the
+    window."""
+    @staticmethod
+    def forward(ctx, a, b):
+        return a.view_as(a), b.view_as(b)
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        global SIDE_LIVE
+        SIDE_LIVE = max(0, SIDE_LIVE - 1)
+        return ga, gb
+
+
+class SideBranch:
+    """Run something on `side` beside the current stream: `with br.fork(): ...` (the side stream first waits for the current one), then
+    whatever belongs on the current stream, then `br.join(*tensors)` (the current stream waits for the side stream and takes over the
+    tensors made there).  Autograd replays each part's backward on the stream its forward ran on.  side = None: all on one stream.
+    window=True keeps the grid-barrier budget at one workgroup per compute unit (SIDE_LIVE) while the two streams share the chip, in
+    the forward and in the backward pass: `a, b = br.bracket(a, b)` on the two branches' inputs before the fork, `br.seal(t)` on the
+    joined result, and the whole region inside `with br:` -- if it raises between fork and join, SIDE_LIVE is put back."""
+
+    def __init__(self, side, window=False):
+        self.side, self.window = side, window and side is not None
+        self.cur = None if side is None else torch.cuda.current_stream(side.device)
+
+    def __enter__(self):
+        self._live = SIDE_LIVE
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        global SIDE_LIVE
+        if exc_type is not None:
+            SIDE_LIVE = self._live
+
+    def bracket(self, a, b):
+        global SIDE_LIVE
+        if self.window:
+            a, b = _SideWindowClose.apply(a, b)
+            SIDE_LIVE += 1
+        return a, b
+
+    def fork(self):
+        if self.side is None:
+            return contextlib.nullcontext()
+        self.side.wait_stream(self.cur)
+        return torch.cuda.stream(self.side)
+
+    def join(self, *tensors):
+        global SIDE_LIVE
+        if self.side is None:
+            return
+        self.cur.wait_stream(self.side)
+        for t in tensors:
+            t.record_stream(self.cur)
+        if self.window:
+            SIDE_LIVE = max(0, SIDE_LIVE - 1)
+
+    def seal(self, t):
+        return _SideWindowOpen.apply(t) if self.window else t
 
 
 class BatchNormActFunction(torch.autograd.Function):

@@ -151,16 +151,12 @@ class IUV_predict_layer(nn.Module):
         if HEAD_STREAM and x.is_cuda and self.training and torch.is_grad_enabled():
             # the four global heads are independent of the heat-map head's chain of ten narrow (12 / 16-channel) layers, whose launches
             # are bound by their latency: side by side on two streams (round 6; autograd replays each on its own stream)
-            from .hrnet import _side_streams
-            cur = torch.cuda.current_stream(x.device)
-            side = _side_streams(x.device, 2)[1]
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
+            from .nn import SideBranch, side_streams
+            side = SideBranch(side_streams(x.device, 2)[1])
+            with side.fork():
                 heads = [self.predict_u(xs[0]), self.predict_v(xs[1]), self.predict_uv_index(xs[2]), self.predict_ann_index(xs[3])]
             hm = self.predict_hm(xs[4])
-            cur.wait_stream(side)
-            for h in heads:
-                h.record_stream(cur)
+            side.join(*heads)
             return {'predict_u': heads[0], 'predict_v': heads[1], 'predict_uv_index': heads[2], 'predict_ann_index': heads[3],
                     'predict_hm': hm, 'xd': xs[5]}
         return {'predict_u': self.predict_u(xs[0]), 'predict_v': self.predict_v(xs[1]),

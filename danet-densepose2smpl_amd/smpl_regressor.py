@@ -19,7 +19,7 @@ from .gcn import GCN, adjacency, normalize_digraph, normalize_undigraph
 from .geometry import perspective_projection, rot6d_to_rotmat
 from .iuv_estimator import SMPL_PARENTS, SMPL_CHILDREN, DP2SMPL_MAPPING
 from .lstm_tree import CHAINS as LSTM_CHAINS, LimbLSTM, lstm_tree
-from .nn import Conv2d, BatchNorm2d
+from .nn import Conv2d, BatchNorm2d, SideBranch, side_streams
 from .resnet import SmplResNet, LimbResLayers
 from .smpl import SMPL
 
@@ -76,36 +76,6 @@ def _pool_conv1x1_grouped(cin, cout, groups):
     Inputs are already [B, C, 1, 1]; the grouped 1x1 conv is a batched matmul (tiny, torch op)."""
     seq = nn.Sequential(nn.AdaptiveAvgPool2d(1), nn.Conv2d(cin, cout, kernel_size=1, groups=groups))
     return seq
-
-
-class _SideWindowOpen(torch.autograd.Function):
-    """Identity on the joined result of the two branches: its backward is the FIRST node of the regressor's backward pass and opens the
-    side-stream window (nn.SIDE_LIVE) -- from here on body_net's backward kernels run beside limb_net's."""
-
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        from . import nn as _nn
-        _nn.SIDE_LIVE += 1
-        return g
-
-
-class _SideWindowClose(torch.autograd.Function):
-    """Identity on the two branches' inputs: its backward runs when BOTH branches have delivered their input gradients and closes the
-    window."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        return a.view_as(a), b.view_as(b)
-
-    @staticmethod
-    def backward(ctx, ga, gb):
-        from . import nn as _nn
-        _nn.SIDE_LIVE = max(0, _nn.SIDE_LIVE - 1)
-        return ga, gb
 
 
 FUSED_SMPL_LOSSES = True    # SMPL-side losses through csrc/loss_ops.hip (False: the tensor-op formulation below)
@@ -435,60 +405,13 @@ class DecomposedPredictor(nn.Module):
         y = torch.einsum('bjc,joc->bjo', feats, W)
         return y + conv.bias.view(1, 24, out_g)
 
-    def forward(self, body_iuv, limb_iuv):
-        rd = {'visualization': {}, 'losses': {}}
-        # body_net (32 images, tensors of <= 16 MB, most launches a handful of workgroups) is independent of limb_net (the 768 part
-        # crops: chip-filling launches) until `para` is assembled: on a side stream its latency-bound launches run beside the limb
-        # net's (round 6; autograd replays its backward on the same stream; its BatchNorms take the two-kernel backward there, the
-        # one-pass kernel being confined to the step's own stream, nn.ONEPASS_STREAM)
-        side = None
-        window = False
-        pad = getattr(limb_iuv, '_nhwc_padded', None)
-        # (only when both inputs carry gradients -- as in a train step --: the backward window below is bracketed by their gradient nodes)
-        if BODY_STREAM and body_iuv.is_cuda and self.training and torch.is_grad_enabled() and body_iuv.requires_grad and \
-                (pad if pad is not None else limb_iuv).requires_grad:
-            from .hrnet import _side_streams
-            from . import nn as _nn
-            cur = torch.cuda.current_stream(body_iuv.device)
-            side = _side_streams(body_iuv.device, 1)[0]
-            # between this fork and the join below (and between their mirror images in the backward pass) kernels of two streams share
-            # the compute units: barrier kernels are held to one workgroup per compute unit meanwhile (nn.SIDE_LIVE)
-            if pad is not None:
-                body_iuv, pad = _SideWindowClose.apply(body_iuv, pad)          # (the padded operand is what limb_net reads, see below)
-            else:
-                body_iuv, limb_iuv = _SideWindowClose.apply(body_iuv, limb_iuv)
-            window = True
-            _nn.SIDE_LIVE += 1
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                global_para, _ = self.body_net(body_iuv)
-                global_para = global_para + self.mean_cam_shape
-        else:
-            global_para, _ = self.body_net(body_iuv)
-            global_para = global_para + self.mean_cam_shape
-        nbs, S = limb_iuv.size(0), limb_iuv.size(-1)
-        # the fused part_clean op hands over the zero-padded 24-channel NHWC bf16 operand of the stem conv
-        stacked = pad
-        if stacked is None:
-            stacked = limb_iuv.reshape(nbs * 24, -1, S, S)
-        _, lf = self.limb_net(stacked)
-        lf = lf['x4']
-        lf = self.limb_reslayer(_glue.regroup_parts(lf, nbs) if REGROUP_PARTS else lf.reshape(nbs, -1, lf.size(-2), lf.size(-1)))      # [B,24*128,1,1]
-        rot_feats = lf.reshape(nbs, 24, -1).float()                                   # [B,24,128]
-
+    def _refine(self, rot_feats, rd):
+        """rot_feats [B,24,128] -> the joint rotations [B,216] behind `para`; the intermediate heads' outputs go into rd."""
         rd['joint_rotation'] = []
         if self.refine_strategy != 'gcn':
             if self.refine_strategy == 'lstm':
                 rd['joint_position'] = []
-            smpl_pose = self._lstm_refine(rot_feats, rd)
-            if side is not None:
-                cur.wait_stream(side)
-                global_para.record_stream(cur)
-                _nn.SIDE_LIVE = max(0, _nn.SIDE_LIVE - 1)
-            rd['para'] = torch.cat([global_para, smpl_pose], dim=1)
-            if window:
-                rd['para'] = _SideWindowOpen.apply(rd['para'])
-            return rd
+            return self._lstm_refine(rot_feats, rd)
         rd['joint_position'] = []
         # the whole graph tail below as ONE launch per direction when the configuration is the trained default (csrc/gcn_tail.hip, round 6)
         fused = _gcn_tail.fused_tail(self, rot_feats)
@@ -496,14 +419,8 @@ class DecomposedPredictor(nn.Module):
             jr0, jp0, jp1, smpl_pose = fused
             rd['joint_rotation'].append(jr0)
             rd['joint_position'] += [jp0, jp1]
-            if side is not None:
-                cur.wait_stream(side)
-                global_para.record_stream(cur)
-                _nn.SIDE_LIVE = max(0, _nn.SIDE_LIVE - 1)
-            rd['para'] = torch.cat([global_para, smpl_pose], dim=1)
-            if window:
-                rd['para'] = _SideWindowOpen.apply(rd['para'])
-            return rd
+            return smpl_pose
+        nbs = rot_feats.size(0)
         if self.training:
             p0 = self._grouped_head(self.pose_regressors[0], rot_feats).reshape(nbs, -1) + self.mean_pose
             rd['joint_rotation'].append(rot6d_to_rotmat(p0).reshape(nbs, -1))
@@ -521,12 +438,34 @@ class DecomposedPredictor(nn.Module):
             pos_ref = pos_init
         rot_ref = self.p2r_gcn(pos_ref, self.p2r_A[0])
         pose6 = self._grouped_head(self.pose_regressors[-1], rot_ref).reshape(nbs, -1) + self.mean_pose
-        smpl_pose = rot6d_to_rotmat(pose6).reshape(nbs, -1)
-        if side is not None:
-            cur.wait_stream(side)
-            global_para.record_stream(cur)
-            _nn.SIDE_LIVE = max(0, _nn.SIDE_LIVE - 1)
-        rd['para'] = torch.cat([global_para, smpl_pose], dim=1)
-        if window:
-            rd['para'] = _SideWindowOpen.apply(rd['para'])
+        return rot6d_to_rotmat(pose6).reshape(nbs, -1)
+
+    def forward(self, body_iuv, limb_iuv):
+        rd = {'visualization': {}, 'losses': {}}
+        # body_net (32 images, tensors of <= 16 MB, most launches a handful of workgroups) is independent of limb_net (the 768 part
+        # crops: chip-filling launches) until `para` is assembled: on a side stream its latency-bound launches run beside the limb
+        # net's (round 6; autograd replays its backward on the same stream; its BatchNorms take the two-kernel backward there, the
+        # one-pass kernel being confined to the step's own stream, nn.ONEPASS_STREAM)
+        pad = getattr(limb_iuv, '_nhwc_padded', None)
+        # (only when both inputs carry gradients -- as in a train step --: the backward window is bracketed by their gradient nodes)
+        beside = BODY_STREAM and body_iuv.is_cuda and self.training and torch.is_grad_enabled() and body_iuv.requires_grad and \
+            (pad if pad is not None else limb_iuv).requires_grad
+        # between the fork and the join (and between their mirror images in the backward pass) kernels of two streams share the compute
+        # units: barrier kernels are held to one workgroup per compute unit meanwhile (nn.SIDE_LIVE)
+        side = SideBranch(side_streams(body_iuv.device, 1)[0] if beside else None, window=True)
+        with side:
+            if pad is not None:
+                body_iuv, pad = side.bracket(body_iuv, pad)          # (the padded operand is what limb_net reads, see below)
+            else:
+                body_iuv, limb_iuv = side.bracket(body_iuv, limb_iuv)
+            with side.fork():
+                global_para, _ = self.body_net(body_iuv)
+                global_para = global_para + self.mean_cam_shape
+            nbs, S = limb_iuv.size(0), limb_iuv.size(-1)
+            # the fused part_clean op hands over the zero-padded 24-channel NHWC bf16 operand of the stem conv
+            lf = self.limb_net(pad if pad is not None else limb_iuv.reshape(nbs * 24, -1, S, S))[1]['x4']
+            lf = self.limb_reslayer(_glue.regroup_parts(lf, nbs) if REGROUP_PARTS else lf.reshape(nbs, -1, lf.size(-2), lf.size(-1)))      # [B,24*128,1,1]
+            smpl_pose = self._refine(lf.reshape(nbs, 24, -1).float(), rd)                 # [B,24,128] -> [B,216]
+            side.join(global_para)
+        rd['para'] = side.seal(torch.cat([global_para, smpl_pose], dim=1))
         return rd

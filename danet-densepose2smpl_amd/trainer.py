@@ -16,7 +16,7 @@ from . import ops
 from .config import cfg
 from .danet import DaNet
 from .distributed import GradStore
-from .nn import BatchNorm2d, bump_batch_counters
+from .nn import BatchNorm2d, SideBranch, bump_batch_counters
 from . import conv as _conv
 from .geometry import perspective_projection, label_prologue
 
@@ -306,14 +306,10 @@ class Trainer(object):
 
     @contextlib.contextmanager
     def _on_stream(self):
-        if self.stream is None:
+        side = SideBranch(self.stream)                  # (None on the CPU: everything stays where it is)
+        with side.fork():
             yield
-            return
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            yield
-        cur.wait_stream(self.stream)
+        side.join()
 
     def _core(self, batch, reduce=True, with_optimizer=True):
         """One optimisation step on the current stream: forward; backward with the weight gradients queued -- in segments
