@@ -154,6 +154,8 @@ _SIGNATURES = {
     'danet_pose_eval': (c_i, [c_f, c_f, ctypes.POINTER(c_i), c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f]),
     'danet_seg_confusion': (c_i, [c_f] * 4 + [ctypes.c_int64] + [c_f] * 4 + [c_i] * 4 + [c_f, c_f]),
     'danet_rotmat_to_angle_axis': (c_i, [c_f, c_i, c_f, c_f]),
+    'danet_coco_keypoints': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_fl, c_f, c_f]),
+    'danet_coco_oks_match': (c_i, [c_f, c_f, c_f, ctypes.c_int64, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_int64, c_i, c_i, c_f, c_f, c_f, c_f]),
     'danet_batch_crop': (c_i, [c_f, ctypes.c_int64, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f]),
     'danet_label_augment': (c_i, [c_f] * 7 + [c_i] * 3 + [c_f] * 7),
 }

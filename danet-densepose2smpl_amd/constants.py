@@ -13,6 +13,10 @@ JOINT_MAP_49 = [
 J24_TO_J17 = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 18, 14, 16, 17]
 J24_TO_J14 = J24_TO_J17[:14]
 J24_TO_J19 = J24_TO_J17[:14] + [19, 20, 21, 22, 23]
+# The 17 COCO keypoints (nose, eyes, ears, shoulders, elbows, wrists, hips, knees, ankles) out of the 24 ground-truth joints, and the
+# per-keypoint sigmas of the COCO keypoint evaluation (object keypoint similarity; csrc/coco_ops.hip holds the same two tables)
+J24_TO_JCOCO = [19, 20, 21, 22, 23, 9, 8, 10, 7, 11, 6, 3, 2, 4, 1, 5, 0]
+COCO_SIGMAS = [s / 10.0 for s in (.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89)]
 
 # Left/right permutations of the augmentation flips (values restated from /root/reference/constants.py:98-131)
 H36M_TO_J17 = [6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10, 0, 7, 9]

@@ -52,6 +52,7 @@ UNITS = {
     'lstm_tree.hip': [],
     'vis_ops.hip': ['-ffp-contract=off'],     # the rotation and the bilinear weights are restated operation by operation in the tests
     'eval_ops.hip': [],
+    'coco_ops.hip': [],
     'input_ops.hip': ['-ffp-contract=off'],   # the crop's arithmetic is restated operation by operation in the tests
 }
 INCLUDES = {'norm_act_f32.hip': ['norm_act.hip']}

@@ -359,6 +359,66 @@ def seg_confusion(mask, parts, gt_mask, gt_parts, offsets, shapes, rects, tables
     return counters
 
 
+COCO_MAX_DETS, COCO_MAX_GT = 20, 256                                   # include/danet_hip.h DANET_COCO_*
+
+
+def coco_keypoints(joints, camera, center, scale, img_res=224, focal_length=5000., out=None):
+    """eval_coco.py:114-145 for a batch in ONE launch (csrc/coco_ops.hip): joints [B,49,3] as the SMPL layer returns them, camera
+    [B,3] = (s, tx, ty), center [B,2] and scale [B] of the crop -> the 17 COCO keypoints [B,17,2] f32 in pixels of the original
+    image (`out`, or a new tensor -- the op's only allocation).  Capturable under torch.cuda.graph."""
+    L = _lib.lib()
+    j = _f32c(_dev_tensor(joints, 'coco_keypoints'))
+    cam, c, s = (_f32c(_dev_tensor(t, 'coco_keypoints')) for t in (camera, center, scale))
+    B = j.shape[0]
+    if tuple(j.shape) != (B, 49, 3) or tuple(cam.shape) != (B, 3) or tuple(c.shape) != (B, 2) or s.numel() != B:
+        raise ValueError('coco_keypoints: joints %s, camera %s, center %s, scale %s (expected [B,49,3], [B,3], [B,2], [B])'
+                         % (tuple(j.shape), tuple(cam.shape), tuple(c.shape), tuple(s.shape)))
+    if out is None:
+        out = torch.empty(B, 17, 2, device=j.device, dtype=torch.float32)
+    else:
+        _typed(out, torch.float32, (B, 17, 2), 'coco_keypoints: out')
+    check(L.danet_coco_keypoints(ptr(j), ptr(cam), ptr(c), ptr(s), B, int(img_res), float(focal_length), ptr(out), stream()),
+          'danet_coco_keypoints')
+    return out
+
+
+def coco_oks_match(dt_kpts, dt_area, dt_offsets, gt_kpts, gt_area, gt_bbox, gt_ignore, gt_iscrowd, gt_offsets):
+    """The per-image part of the COCO keypoint rule for a whole dataset in ONE launch, one workgroup per image
+    (csrc/coco_ops.hip).  Detections packed by image in evaluation order: dt_kpts [N,17,2] f32, dt_area [N] f64, dt_offsets int64
+    [I+1]; ground truth packed by image: gt_kpts [M,17,3] f64, gt_area [M] f64, gt_bbox [M,4] f64, gt_ignore / gt_iscrowd [M] uint8,
+    gt_offsets int64 [I+1].  -> (dt_match [N,3], dt_ignore [N,3]) as int32 holding the kernel's 16-bit words (bit t = threshold
+    0.5 + 0.05 t; columns = area ranges all, medium, large) and gt_count [I,3] int32.  The offsets are read back and checked on the
+    host (this op belongs to summary(), which copies to the host anyway); more than COCO_MAX_GT ground truths in an image is an error."""
+    L = _lib.lib()
+    dk = _dev_tensor(dt_kpts, 'coco_oks_match')
+    N, I = dk.shape[0], dt_offsets.numel() - 1
+    _typed(dk, torch.float32, (N, 17, 2), 'coco_oks_match: dt_kpts')
+    _typed(dt_area, torch.float64, (N,), 'coco_oks_match: dt_area')
+    M = gt_kpts.shape[0]
+    _typed(gt_kpts, torch.float64, (M, 17, 3), 'coco_oks_match: gt_kpts')
+    _typed(gt_area, torch.float64, (M,), 'coco_oks_match: gt_area')
+    _typed(gt_bbox, torch.float64, (M, 4), 'coco_oks_match: gt_bbox')
+    _typed(gt_ignore, torch.uint8, (M,), 'coco_oks_match: gt_ignore')
+    _typed(gt_iscrowd, torch.uint8, (M,), 'coco_oks_match: gt_iscrowd')
+    _typed(dt_offsets, torch.int64, (I + 1,), 'coco_oks_match: dt_offsets')
+    _typed(gt_offsets, torch.int64, (I + 1,), 'coco_oks_match: gt_offsets')
+    if I < 1:
+        raise ValueError('coco_oks_match: no images')
+    host = {}
+    for off, n, what in ((dt_offsets, N, 'dt_offsets'), (gt_offsets, M, 'gt_offsets')):
+        o = host[what] = off.cpu()
+        if int(o[0]) != 0 or int(o[-1]) != n or bool((o[1:] < o[:-1]).any()):
+            raise ValueError('coco_oks_match: %s must ascend from 0 to %d' % (what, n))
+    max_gt = int((host['gt_offsets'][1:] - host['gt_offsets'][:-1]).max())
+    # the kernel stores 16-bit words; torch has no arithmetic on uint16, so the buffers are int16 and widened after the launch
+    dm = torch.empty(N, 3, device=dk.device, dtype=torch.int16)
+    di = torch.empty(N, 3, device=dk.device, dtype=torch.int16)
+    gc = torch.empty(I, 3, device=dk.device, dtype=torch.int32)
+    check(L.danet_coco_oks_match(ptr(dk), ptr(dt_area), ptr(dt_offsets), N, ptr(gt_kpts), ptr(gt_area), ptr(gt_bbox), ptr(gt_ignore),
+                                 ptr(gt_iscrowd), ptr(gt_offsets), M, I, max_gt, ptr(dm), ptr(di), ptr(gc), stream()), 'danet_coco_oks_match')
+    return dm.int() & 0xffff, di.int() & 0xffff, gc
+
+
 def _typed(t, dtype, shape, what):
     t = _dev_tensor(t, what)
     if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():

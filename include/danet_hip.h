@@ -767,6 +767,36 @@ int danet_seg_confusion(const float* mask, const int64_t* parts, const uint8_t* 
 int danet_rotmat_to_angle_axis(const float* R, int N, float* angle_axis, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * COCO keypoint evaluation ops (csrc/coco_ops.hip; forward only, evaluate_coco.py is the caller).  Both are ONE launch, need no
+ * workspace, enqueue only on `stream` and are capturable.
+ *
+ * coco_keypoints (eval_coco.py:114-145): joints [B,49,3] f32 as the SMPL layer returns them (the last 24 are picked through
+ * J24_TO_JCOCO), camera [B,3] f32 = (s, tx, ty), center [B,2] f32 and scale [B] f32 of the crop -> preds [B,17,2] f32 in pixels
+ * of the original image: t = (tx, ty, 2 focal_length / (img_res s + 1e-9)), pinhole projection with identity rotation and a zero
+ * principal point, + img_res / 2, then the inverse crop affine, which without rotation is x -> center + (x - img_res / 2) * 200
+ * scale / img_res.  fp64 inside, one rounding to f32.
+ *
+ * coco_oks_match (the per-image part of the COCO keypoint rule of DESIGN.md 4c), one workgroup per image, ONE launch for the
+ * dataset.  Detections packed by image in evaluation order: dt_kpts [N,17,2] f32, dt_area [N] f64, dt_offsets i64
+ * [num_images + 1].  Ground truth packed by image: gt_kpts [M,17,3] f64 (x, y, v), gt_area [M] f64, gt_bbox [M,4] f64 (x, y, w,
+ * h), gt_ignore [M] u8 (iscrowd or num_keypoints == 0), gt_iscrowd [M] u8, gt_offsets i64 [num_images + 1].  The areas, boxes and
+ * ground-truth keypoints are f64 because the annotation file holds them so and a rounding could move one across 32^2 or 96^2.
+ * max_gt is the largest ground-truth count of an image as the HOST knows it: above DANET_COCO_MAX_GT the call returns
+ * DANET_ERR_ARG and launches nothing (a workgroup that finds offsets on the device that contradict N, M or that limit writes
+ * nothing).  -> dt_match [N,3] and dt_ignore [N,3] u16: bit t = threshold numpy.linspace(0.5, 0.95, 10)[t], one column per area
+ * range (all, medium, large); a detection past the first DANET_COCO_MAX_DETS of its image gets match 0 and ignore 0x3ff;
+ * gt_count [num_images,3] i32 = the ground truths not ignored in that range.
+ */
+#define DANET_COCO_MAX_DETS 20
+#define DANET_COCO_MAX_GT 256
+int danet_coco_keypoints(const float* joints, const float* camera, const float* center, const float* scale, int B,
+                         int img_res, float focal_length, float* preds, void* stream);
+int danet_coco_oks_match(const float* dt_kpts, const double* dt_area, const int64_t* dt_offsets, int64_t N,
+                         const double* gt_kpts, const double* gt_area, const double* gt_bbox, const uint8_t* gt_ignore,
+                         const uint8_t* gt_iscrowd, const int64_t* gt_offsets, int64_t M, int num_images, int max_gt,
+                         uint16_t* dt_match, uint16_t* dt_ignore, int32_t* gt_count, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input ops of the training pipeline (csrc/input_ops.hip; forward only, datasets.py and fits_dict.py are the callers).
  * Both are ONE launch for a batch, need no workspace, enqueue only on `stream` and are capturable.
  *
