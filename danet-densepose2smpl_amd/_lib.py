@@ -158,6 +158,8 @@ _SIGNATURES = {
     'danet_coco_oks_match': (c_i, [c_f, c_f, c_f, ctypes.c_int64, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_int64, c_i, c_i, c_f, c_f, c_f, c_f]),
     'danet_batch_crop': (c_i, [c_f, ctypes.c_int64, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f]),
     'danet_label_augment': (c_i, [c_f] * 7 + [c_i] * 3 + [c_f] * 7),
+    'danet_vis_grid': (c_i, [c_f, c_f, ctypes.POINTER(ctypes.c_int64)] + [c_i] * 7 + [c_fl, c_i, c_f, c_i, c_i, c_f, c_f, c_f]),
+    'danet_vis_joints': (c_i, [c_f, c_i, c_i, c_f, ctypes.POINTER(ctypes.c_int64), c_f, ctypes.POINTER(ctypes.c_int64)] + [c_i] * 6 + [c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations

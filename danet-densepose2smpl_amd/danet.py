@@ -154,8 +154,10 @@ class DaNet(nn.Module):
             iuv_map = torch.cat([u_cl, v_cl, i_cl], dim=1)
         if in_dict.get('vis_on', False):
             rd['visualization']['gt_uv'] = uv_image_gt
-            if 'stn_kps_pred' in uv:
-                rd['visualization']['stn_kps_pred'] = uv['stn_kps_pred']
+            # (what Trainer.visualize turns into sheets, danet.py:214-235: references to tensors the estimator made anyway)
+            for key in ('stn_kps_pred', 'skps_hm_pred', 'part_iuv_gt'):
+                if key in uv:
+                    rd['visualization'][key] = uv[key].detach()
 
         smpl_rd = None
         if not in_dict.get('pretrain_mode', False):

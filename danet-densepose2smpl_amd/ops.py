@@ -243,6 +243,71 @@ def demo_compose(images, glob, part, riuv, mesh=None, side=None, side_alpha=None
     return out
 
 
+def vis_grid_size(N, H, W, nrow, padding):
+    """The sheet rule's size for N tiles of H x W -> (Hs, Ws)."""
+    xmaps = min(int(nrow), int(N))
+    ymaps = -(-int(N) // xmaps)
+    return ymaps * (H + padding) + padding, xmaps * (W + padding) + padding
+
+
+def vis_grid(a, b=None, nrow=8, padding=2, pad_value=0., denormalize=False, overlay=None, lohi=None):
+    """The sheet rule (csrc/train_vis.hip), one launch: a [B,C,H,W] fp32 / bf16 with any strides (C = 1 or 3), b a
+    second source of the same shape whose tiles are interleaved with a's, overlay [B,3,h,w] laid over the tiles where > 0, lohi a
+    2-float device buffer (min, max) that switches the normalisation on.  -> [3,Hs,Ws] f32."""
+    import ctypes
+    L = _lib.lib()
+    ts = [_dev_tensor(a, 'vis_grid')] + ([] if b is None else [_dev_tensor(b, 'vis_grid')])
+    dt = ts[0].dtype
+    if dt not in (torch.float32, torch.bfloat16) or any(t.dtype != dt for t in ts):
+        ts = [t.to(torch.float32) for t in ts]
+        dt = torch.float32
+    if ts[0].dim() != 4 or any(t.shape != ts[0].shape for t in ts):
+        raise ValueError('vis_grid: [B,C,H,W] sources of one shape expected, got %s' % [tuple(t.shape) for t in ts])
+    B, C, H, W = ts[0].shape
+    ov, oh, ow = None, 0, 0
+    if overlay is not None:
+        ov = _f32c(_dev_tensor(overlay, 'vis_grid'))
+        if ov.dim() != 4 or ov.shape[0] != B or ov.shape[1] != 3:
+            raise ValueError('vis_grid: overlay %s for %d tiles (expected [B,3,h,w])' % (tuple(ov.shape), B))
+        oh, ow = ov.shape[2], ov.shape[3]
+    lh = None
+    if lohi is not None:
+        lh = _f32c(_dev_tensor(lohi, 'vis_grid')).reshape(-1)
+        if lh.numel() != 2:
+            raise ValueError('vis_grid: lohi holds (min, max), got %d values' % lh.numel())
+    flags = (1 if denormalize else 0) | (2 if lh is not None else 0)
+    Hs, Ws = vis_grid_size(B * len(ts), H, W, nrow, padding)
+    strides = (ctypes.c_int64 * 8)(*([st for t in ts for st in t.stride()] + [0] * (8 - 4 * len(ts))))
+    out = torch.empty(3, Hs, Ws, device=ts[0].device, dtype=torch.float32)
+    check(L.danet_vis_grid(ts[0].data_ptr(), None if b is None else ts[1].data_ptr(), strides, 0 if dt == torch.float32 else 1,
+                           B, C, H, W, int(nrow), int(padding), float(pad_value), flags, ptr(ov), oh, ow, ptr(lh), ptr(out), stream()),
+          'danet_vis_grid')
+    return out
+
+
+def vis_joints(sheet, joints, vis, B, H, W, nrow=8, padding=2):
+    """The marker rule (csrc/train_vis.hip), one launch, IN PLACE on sheet [3,Hs,Ws] f32 (contiguous) as vis_grid made
+    it from B tiles of H x W: joints [B,J,>=2] f32 (x, y relative to the tile), vis [B,J] / [B,J,1] f32 or None (all visible)."""
+    import ctypes
+    L = _lib.lib()
+    sh = _dev_tensor(sheet, 'vis_joints')
+    if sh.dtype != torch.float32 or sh.dim() != 3 or sh.shape[0] != 3 or not sh.is_contiguous():
+        raise ValueError('vis_joints: a contiguous [3,Hs,Ws] f32 sheet expected, got %s %s' % (sh.dtype, tuple(sh.shape)))
+    j = _dev_tensor(joints, 'vis_joints').to(torch.float32)
+    if j.dim() != 3 or j.shape[0] != B or j.shape[2] < 2:
+        raise ValueError('vis_joints: joints %s for %d tiles (expected [B,J,>=2])' % (tuple(j.shape), B))
+    J = j.shape[1]
+    v, vs = None, None
+    if vis is not None:
+        v = _dev_tensor(vis, 'vis_joints').to(torch.float32).reshape(vis.shape[0], -1)
+        if tuple(v.shape) != (B, J):
+            raise ValueError('vis_joints: visibility %s for joints %s' % (tuple(vis.shape), tuple(j.shape)))
+        vs = (ctypes.c_int64 * 2)(*v.stride())
+    check(L.danet_vis_joints(sh.data_ptr(), sh.shape[1], sh.shape[2], j.data_ptr(), (ctypes.c_int64 * 3)(*j.stride()),
+                             None if v is None else v.data_ptr(), vs, B, J, H, W, int(nrow), int(padding), stream()), 'danet_vis_joints')
+    return sheet
+
+
 def _rodrigues(theta, which):
     L = _lib.lib()
     if theta.requires_grad:

@@ -3,7 +3,7 @@
 forward, sum of the loss dict (trainer.py:217-220), backward, Adam step (lr 1e-4, trainer.py:42-44).
 The in_dict is the one the reference builds at trainer.py:184-212; `synthetic_in_dict` produces it
 from seeded random labels.  `Trainer.fit` is the loop of base_trainer.py:53-106 over
-datasets.py / fits_dict.py; TensorBoard is out of scope."""
+datasets.py / fits_dict.py; TensorBoard's image summaries are PNG sheets here (Trainer.visualize, train_vis.py), its event files are out of scope."""
 import types
 
 import numpy as np
@@ -595,9 +595,10 @@ class Trainer(object):
     # The training loop: base_trainer.py:53-106 around the step prologue of train/trainer.py:134-212.  Steps run eagerly unless
     # options.graph asks for captured steps: `pretrain_mode` and `dp_active` are host switches that a captured graph freezes, so a
     # graphed run holds one graph per pretrain_mode phase and decides dp_active once, from the datasets of the run (_fit_step).
-    def build_in_dict(self, host_batch, fits_dict, train_data='h36m_dp', pretrain_mode=False):
+    def build_in_dict(self, host_batch, fits_dict, train_data='h36m_dp', pretrain_mode=False, vis_on=False):
         """A collated loader batch (datasets.collate) -> the in_dict of train_step, all on the step's own stream: upload + the two
-        input ops (datasets.to_device), the fits (fits_dict[...], one gather + the label op), valid_fit, prepare_batch."""
+        input ops (datasets.to_device), the fits (fits_dict[...], one gather + the label op), valid_fit, prepare_batch.  vis_on: the
+        step's output will be looked at (base_trainer.py:73; fit sets it on visualisation steps)."""
         from . import datasets
         with self._on_stream():
             batch = datasets.to_device(host_batch, self.device, cfg.DANET.INIMG_SIZE)
@@ -607,7 +608,7 @@ class Trainer(object):
                 batch['valid_fit'] = (fits_dict.get_vaild_state(batch['dataset_name'], batch['sample_index']) > 0) | has_smpl
             else:
                 batch['valid_fit'] = has_smpl
-            batch['vis_on'] = False
+            batch['vis_on'] = bool(vis_on)
             batch['pretrain_mode'] = bool(pretrain_mode)
             in_dict = self.prepare_batch(batch, opt_pose, opt_betas)
             in_dict['dp_dict']['dp_active'] = bool(host_batch['dp_active'])
@@ -615,7 +616,7 @@ class Trainer(object):
 
     def _fit_step(self, in_dict):
         """One step of a graphed fit (see fit): eager for the first two steps of a pretrain_mode phase, a capture before the third,
-        replays from there on.  -> the step's losses."""
+        replays from there on.  -> (output, losses, in_dict as the step saw it): of a replayed step the graph's static tensors."""
         phase, done, dp_captured = self._fit_phase
         if phase != in_dict['pretrain_mode']:
             # a new phase runs other modules: drop the old graph, static batch and pool FIRST, and let the two eager steps record and
@@ -626,16 +627,99 @@ class Trainer(object):
                 _conv.RECORDER = None
             phase, done = in_dict['pretrain_mode'], 0
         if done < 2:
-            _, losses = self.train_step(in_dict)
+            out, losses = self.train_step(in_dict)
             self.fit_stats['eager_steps'] += 1
         else:
             if self._graph is None:
                 self.capture(in_dict, warmup=0, dp_active=dp_captured)
                 self.fit_stats['captures'] += 1
-            _, losses = self.train_step_graphed(in_dict)
+            out, losses = self.train_step_graphed(in_dict)
+            in_dict = self._static
             self.fit_stats['replayed_steps'] += 1
         self._fit_phase = (phase, done + 1, dp_captured)
-        return losses
+        return out, losses, in_dict
+
+    # ------------------------------------------------------------------------------------------
+    # Training visualisation (train/trainer.py:250-305, models/danet/danet.py:210-235,334-350): image sheets as uint8 device
+    # tensors, built by the two kernels of csrc/train_vis.hip from ops the demo already has.
+    VIS_SCALARS = ('index_fg', 'p_index_fg')
+
+    def _mesh_renderer(self, res):
+        from .renderer import MeshRenderer
+        cache = self.__dict__.setdefault('_mesh_renderers', {})
+        if res not in cache:
+            cache[res] = MeshRenderer(self.smpl.faces, img_res=res)
+        return cache[res]
+
+    @torch.no_grad()
+    def visualize(self, in_dict, output, losses=None):
+        """The sheets of a step that ran with `vis_on`, under the reference's tags -> {tag: uint8 [3,Hs,Ws] device tensor}, a sheet
+        only where its source is present: opt_shape, pred_shape (label / predicted mesh beside the input, train_vis.pair_grid),
+        pred_uv, gt_uv (decoded IUV over the input, overlay_grid), part_uvi_pred (sample 0's 24 decoded partial maps), part_uvi_gt
+        (where the estimator materialises part_iuv_gt: not on the fused path), skps_hm_pred (max over the 24 heat-maps, clamped to
+        1), skps_hm_pred_soft (sum of their spatial softmaxes), stn_centers_gt, stn_centers_pred (the STN centres marked on the
+        input, joints_grid; all joints visible).  Plus the foreground fractions of the cleaned index maps (danet.py:218,336) as
+        0-dim f32 device tensors: index_fg, and p_index_fg when the regressor ran.  Runs eagerly on the step's stream; reads its
+        arguments only (target_smpl_kps and stn_kps_pred are not scaled in place, unlike trainer.py:281-282,293-294).  `losses` is
+        accepted for the reference's signature and not used."""
+        from . import iuvmap, train_vis as tv
+        from .iuv_estimator import DP2SMPL_MAPPING
+        vis = output.get('visualization', {})
+        pred = output.get('prediction', {})
+        pretrain = bool(in_dict.get('pretrain_mode', False))
+        img = in_dict['img']
+        S = img.shape[-1]
+        sheets = {}
+        with self._on_stream():
+            if 'target_verts' in in_dict and 'target_cam' in in_dict and S == cfg.DANET.INIMG_SIZE:
+                images = tv.denormalized(img)                          # (the renderer's background; the sheets de-normalise in their own launch)
+                render = self._mesh_renderer(S)
+                sheets['opt_shape'] = tv.pair_grid(images, render(in_dict['target_verts'].detach(), in_dict['target_cam'].detach(), images)[0])
+                if not pretrain and 'vertices' in pred and 'cam' in pred:
+                    sheets['pred_shape'] = tv.pair_grid(images, render(pred['vertices'].detach(), pred['cam'].detach(), images)[0])
+            if 'iuv_pred' in vis:
+                sheets['pred_uv'] = tv.overlay_grid(img, iuvmap.iuv_map2img(*vis['iuv_pred']))
+                index = vis['iuv_pred'][2]
+                sheets['index_fg'] = index[:, 1:].sum(dtype=torch.float32) / index[:, 0].numel()
+            if 'gt_uv' in vis:
+                sheets['gt_uv'] = tv.overlay_grid(img, vis['gt_uv'])
+            if not pretrain and vis.get('part_iuv_pred') is not None:
+                part = vis['part_iuv_pred']
+                sheets['part_uvi_pred'] = tv.make_grid(iuvmap.part_iuv_map2img(part[:1], DP2SMPL_MAPPING)[0], padding=1, pad_value=1)
+                sheets['p_index_fg'] = part[:, :, 2, 1:].sum(dtype=torch.float32) / part[:, :, 2, 0].numel()
+            if vis.get('part_iuv_gt') is not None:
+                sheets['part_uvi_gt'] = tv.make_grid(iuvmap.part_iuv_map2img(vis['part_iuv_gt'][:1], DP2SMPL_MAPPING)[0], padding=1, pad_value=1)
+            if 'skps_hm_pred' in vis:
+                hm = vis['skps_hm_pred'].to(torch.float32)
+                sheets['skps_hm_pred'] = tv.make_grid(hm.amax(dim=1, keepdim=True).clamp(max=1.), padding=1, pad_value=1)
+                soft = torch.softmax(hm.flatten(2), dim=2).reshape(hm.shape).sum(dim=1, keepdim=True)
+                sheets['skps_hm_pred_soft'] = tv.make_grid(soft, padding=1, pad_value=1)
+            for tag, kps in (('stn_centers_gt', in_dict.get('target_smpl_kps')), ('stn_centers_pred', vis.get('stn_kps_pred'))):
+                if kps is not None:
+                    sheets[tag] = tv.joints_grid(img, kps[:, :, :2].to(torch.float32) * (S / 2.) + S / 2.)
+            for tag in sheets:
+                if tag not in self.VIS_SCALARS:
+                    sheets[tag] = tv.to_uint8(sheets[tag])
+        return sheets
+
+    def write_sheets(self, folder, sheets):
+        """What visualize returned -> one <tag>.png per sheet under `folder` (ONE device-to-host copy for all of them) and the
+        scalars as {name: float}."""
+        from . import train_vis as tv
+        tags = [t for t in sheets if t not in self.VIS_SCALARS]
+        os.makedirs(folder, exist_ok=True)
+        if tags:
+            with self._on_stream():
+                flat = torch.cat([sheets[t].reshape(-1) for t in tags] +
+                                 [sheets[t].reshape(1).view(torch.uint8) for t in self.VIS_SCALARS if t in sheets])
+            host = flat.cpu().numpy()
+            at = 0
+            for t in tags:
+                n = sheets[t].numel()
+                tv.write_png(os.path.join(folder, t + '.png'), host[at:at + n].reshape(tuple(sheets[t].shape)).transpose(1, 2, 0))
+                at += n
+            return {t: float(v) for t, v in zip([t for t in self.VIS_SCALARS if t in sheets], host[at:].view(np.float32))}
+        return {t: float(sheets[t]) for t in self.VIS_SCALARS if t in sheets}
 
     @staticmethod
     def latest_checkpoint(checkpoint_dir):
@@ -656,10 +740,15 @@ class Trainer(object):
         point supervision is captured as active iff 'dp_coco' is one of the run's datasets (TRAIN_SETS[train_data]), decided once per
         run.  A batch of another shape than the captured one raises (load_batch).  The `losses` of a replayed step are the graph's
         static output tensors: valid until the next step, which overwrites them -- copy what must outlive it.
-        self.fit_stats = {'eager_steps', 'replayed_steps', 'captures'} counts this call's steps."""
+        self.fit_stats = {'eager_steps', 'replayed_steps', 'captures'} counts this call's steps.
+        options.vis_interval (absent, None or 0: off): a step with (step_count - 1) % vis_interval == 0 is followed by visualize();
+        its sheets go to <log_dir>/vis/step_%08d/<tag>.png and index_fg / p_index_fg into the step's JSON line (a line of its own
+        where the summary schedule has none).  Eager runs set `vis_on` on exactly those steps (base_trainer.py:73); a graphed run
+        sets it on EVERY step, since the capture freezes the switch, and a replayed visualisation step reads the graph's static
+        outputs before the next replay overwrites them.  visualize itself always runs eagerly, outside the graph."""
         import json
         import time
-        from . import checkpoint, datasets
+        from . import checkpoint, datasets, train_vis
         opt = lambda k, d=None: d if getattr(options, k, None) is None else getattr(options, k)       # noqa: E731
         bs, ckpt_dir, log_dir = int(options.batch_size), opt('checkpoint_dir', 'checkpoints'), opt('log_dir', 'logs')
         endtime = time.time() + float(opt('time_to_run', np.inf))
@@ -677,6 +766,7 @@ class Trainer(object):
         self.fit_stats = {'eager_steps': 0, 'replayed_steps': 0, 'captures': 0}
         graphed = bool(opt('graph', False))
         train_data = opt('train_data', 'h36m_dp')
+        vis_interval = int(opt('vis_interval', 0))
         if graphed:
             if self.device.type != 'cuda':
                 raise RuntimeError('options.graph needs a GPU')
@@ -695,17 +785,25 @@ class Trainer(object):
                         save(epoch, step, loader.sampler.dataset_perm)
                         return ran
                     count = self.step_count + 1                            # (base_trainer.py:70-74: the step about to run)
-                    in_dict = self.build_in_dict(host, fits_dict, train_data, pretrain_mode=count <= int(opt('pretr_step', 0)))
+                    vis_on = vis_interval > 0 if graphed else train_vis.vis_due(count, vis_interval)
+                    in_dict = self.build_in_dict(host, fits_dict, train_data, pretrain_mode=count <= int(opt('pretr_step', 0)), vis_on=vis_on)
                     if graphed:
-                        losses = self._fit_step(in_dict)
+                        output, losses, seen = self._fit_step(in_dict)
                     else:
-                        _, losses = self.train_step(in_dict)
+                        output, losses = self.train_step(in_dict)
+                        seen = in_dict
                         self.fit_stats['eager_steps'] += 1
                     ran += 1
+                    line = None
                     if (self.step_count - 1) % int(opt('summary_steps', 100)) == 0:
                         vals = {'loss_' + k: float(v.detach()) for k, v in losses.items()}      # ('loss_{}'.format(key), train/trainer.py:221)
                         vals['loss_tatal'] = float(sum(vals.values()))
-                        log.write(json.dumps({'step': self.step_count, 'epoch': epoch, 'batch_idx': step, **vals}) + '\n')
+                        line = {'step': self.step_count, 'epoch': epoch, 'batch_idx': step, **vals}
+                    if train_vis.vis_due(self.step_count, vis_interval):
+                        line = line or {'step': self.step_count, 'epoch': epoch, 'batch_idx': step}
+                        line.update(self.write_sheets(os.path.join(log_dir, 'vis', 'step_%08d' % self.step_count), self.visualize(seen, output, losses)))
+                    if line is not None:
+                        log.write(json.dumps(line) + '\n')
                         log.flush()
                     if on_step is not None:
                         on_step(self.step_count, in_dict, losses)

@@ -828,6 +828,36 @@ int danet_label_augment(const double* xform, const double* rot_flip, const doubl
                         float* keypoints_out, float* smpl_2dkps_out, float* pose_3d_out, float* pose_out,
                         float* fits_pose_out, float* fits_betas_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Sheet kernels of the training visualisation (csrc/train_vis.hip; forward only, train_vis.py is the caller; the two rules are
+ * DESIGN.md 4e).  Both are ONE launch, need no workspace, enqueue only on `stream` and are capturable.
+ *
+ * vis_grid, the sheet rule (torchvision's make_grid; utils/renderer.py:39-50, train/trainer.py:250-277, utils/vis.py:367): a
+ * [B,C,H,W] (C = 1 or 3; dtype 0 = fp32, 1 = bf16 bits) with element strides strides[0..3], and optionally a second source b of the
+ * same shape and dtype with strides[4..7] whose tiles are interleaved a0, b0, a1, b1, ... (N = 2 B tiles; N = B otherwise).
+ * xmaps = min(nrow, N), ymaps = ceil(N / xmaps); out [3, ymaps (H + padding) + padding, xmaps (W + padding) + padding] f32; tile k
+ * at row (k / xmaps) (H + padding) + padding, column (k % xmaps) (W + padding) + padding; every other element is pad_value; C = 1
+ * is replicated to the three planes.  Per element of a tile, in this order: flags & DANET_VIS_DENORM: x * std[c] + mean[c] with the
+ * ImageNet constants (C = 3); overlay [B,3,oh,ow] f32 contiguous (may be NULL; not with b): o = overlay[n, c, y / f, x / f], f =
+ * H / oh = W / ow an integer (anything else is DANET_ERR_ARG), and the element becomes o where o > 0 -- per channel, not per pixel;
+ * flags & DANET_VIS_NORMALIZE: (x - lo) / (hi - lo + 1e-5) clamped to [0, 1], (lo, hi) = lohi[0..1] on the device.
+ *
+ * vis_joints, the marker rule (utils/vis.py:359-405 without the joint numbers): sheet [3,Hs,Ws] f32 as vis_grid made it from B
+ * tiles of H x W with this nrow and padding (Hs, Ws are checked against the sheet rule); joints f32 with element strides
+ * joint_strides = (sample, joint, coordinate), x then y, relative to the tile; vis f32 with strides (sample, joint) or NULL = all
+ * visible.  Joint j of tile k marks the 5 pixels |dx| + |dy| <= 1 around (int(ox + x), int(oy + y)), (ox, oy) the tile's corner on
+ * the sheet, the sum in f32 and int() truncating toward zero: (0, 1, 0) for even j, (1, 0, 0) for odd j.  Pixels outside the sheet
+ * are clipped, a joint with a non-finite position or visibility 0 is skipped, and where markers overlap the later one in
+ * (tile, joint) order wins.  In place; no element that is not a marker pixel is written.
+ */
+#define DANET_VIS_DENORM 1
+#define DANET_VIS_NORMALIZE 2
+int danet_vis_grid(const void* a, const void* b, const int64_t* strides, int dtype, int B, int C, int H, int W, int nrow,
+                   int padding, float pad_value, int flags, const float* overlay, int oh, int ow, const float* lohi, float* out,
+                   void* stream);
+int danet_vis_joints(float* sheet, int Hs, int Ws, const float* joints, const int64_t* joint_strides, const float* vis,
+                     const int64_t* vis_strides, int B, int J, int H, int W, int nrow, int padding, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

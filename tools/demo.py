@@ -6,34 +6,19 @@ shaded mesh turned by 90 degrees.
 
 Images: .npy arrays always ([S,S,3] or [3,S,S], uint8 or float in [0,1]); .jpg / .png if PIL is installed.  They must be square
 at DANET.INIMG_SIZE (cropping is augment.py's job).  Without --checkpoint the model has seeded random weights and the synthetic
-SMPL / DensePose tables, so the tool runs on a clean checkout.  The PNG files are written by write_png below (zlib + struct).
+SMPL / DensePose tables, so the tool runs on a clean checkout.  The PNG files are written by train_vis.write_png (zlib + struct).
 Last line: one JSON object with the milliseconds per image of the panel stage (demo.result_panels, HIP) beside the same panels
 assembled from tensor ops (panels_torch below), 20 alternating repetitions, median and p10..p90."""
 import argparse
 import json
 import os
-import struct
 import sys
-import zlib
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-
-def write_png(path, arr):
-    """uint8 [H,W,3] (RGB) or [H,W,4] (RGBA) -> an 8-bit, non-interlaced PNG file (filter type 0 on every line)."""
-    arr = np.ascontiguousarray(arr)
-    if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] not in (3, 4):
-        raise ValueError('write_png: uint8 [H,W,3|4] expected, got %s %s' % (arr.dtype, arr.shape))
-    H, W, C = arr.shape
-    raw = np.concatenate([np.zeros((H, 1), np.uint8), arr.reshape(H, W * C)], 1).tobytes()
-
-    def chunk(typ, body):
-        return struct.pack('>I', len(body)) + typ + body + struct.pack('>I', zlib.crc32(typ + body) & 0xffffffff)
-    with open(path, 'wb') as f:
-        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', W, H, 8, 2 if C == 3 else 6, 0, 0, 0)) +
-                chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b''))
+from danet_densepose2smpl_amd.train_vis import write_png       # noqa: E402  (the writer the training sheets share)
 
 
 def to_uint8(x):

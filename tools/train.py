@@ -3,11 +3,13 @@
   python tools/train.py --name RUN [--data_root DIR] [--train_data h36m_dp|h36m_coco_itw] [--num_epochs N] [--batch_size B]
                         [--checkpoint_steps K] [--summary_steps K] [--pretr_step K] [--resume] [--pretrained_checkpoint FILE]
                         [--num_workers W] [--ignore_3d] [--time_to_run SECONDS] [--cfg YAML] [--log_dir DIR] [--graph]
+                        [--vis_interval K]
 
 --data_root holds, for every dataset <ds> of --train_data, <ds>_train.npz (the reference's annotation layout), the image folder <ds>/
 and the fits folders final_fits/ and static_fits/.  Without it a small synthetic 'h36m_dp' set is written to a scratch directory and
 trained on, so the tool runs on a machine with no data.  --graph runs the steps as hipGraph replays (Trainer.fit: two eager steps and
-one capture per pretrain_mode phase).  Logs (train_log.jsonl) and checkpoints go to <log_dir>/<name>/.
+one capture per pretrain_mode phase).  --vis_interval K (default 0 = off; the reference's default is 1000) writes the image sheets of
+Trainer.visualize to <log_dir>/<name>/vis/step_<n>/<tag>.png after every K-th step.  Logs (train_log.jsonl) and checkpoints go to <log_dir>/<name>/.
 Last line: one JSON object (steps run, last losses)."""
 import argparse
 import json
@@ -38,6 +40,7 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--num_synthetic', type=int, default=32)
     ap.add_argument('--graph', action='store_true', help='replay captured steps (one hipGraph per pretrain_mode phase)')
+    ap.add_argument('--vis_interval', type=int, default=0, help='steps between image sheets under <log_dir>/<name>/vis (0: none)')
     a = ap.parse_args(argv)
 
     import torch
