@@ -194,7 +194,8 @@ __global__ __launch_bounds__(1024) void stn_bwd_kernel(const T* __restrict__ dy,
                 const float wy = sWy[p * OH + oh];
                 if (wy == 0.0f) continue;                           // (uniform: the same row for every lane)
                 const T* const drow = dy + (((size_t)b * OH + oh) * OW) * PCs + (size_t)p * C + cv * 8;
-                // four candidates at a time, their loads in flight together (a window is 2 / scale + 1 columns: mostly ONE group);
+                // four candidates at a time, their loads in flight together (ix advances by scale * W / OW pixels per output column, so a
+                // window is 2 * OW / (scale * W) + 1 columns -- 2 / scale + 1 when the output has the input's size: mostly ONE group);
                 // a slot past the window reads the window's last column with weight 0 (adds an exact zero)
                 for (int ow = ow0; ow <= ow1; ow += 4) {
                     V8 g[4];

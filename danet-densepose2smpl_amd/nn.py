@@ -824,7 +824,14 @@ def relu(x):
 
 class StnGatherFunction(torch.autograd.Function):
     """x [B,C,H,W], theta [B,P,2,3] -> [B,P*C,OH,OW]; gradient to x only (theta is detached in the
-    reference, iuv_estimator.py:197)."""
+    reference, iuv_estimator.py:197).
+
+    Contract of the backward: AXIS-ALIGNED thetas only, [[sx, 0, cx], [0, sy, cy]] (any sign of sx / sy, zero included).  The
+    forward honours the shear terms theta[..., 0, 1] and theta[..., 1, 0]; the backward (csrc/stn.hip, a gather over separable
+    windows) ignores them, so with a sheared theta the gradient would silently belong to another forward.  affine_para, the only
+    producer of these thetas, never builds shear.  The values live on the device and are not checked here (a check would cost a
+    synchronisation per step): a caller with general affine maps must not take this gradient.  tests/test_gpu_stn.py holds both
+    kernels to the float64 oracle on axis-aligned thetas and the forward alone on sheared ones."""
 
     @staticmethod
     def forward(ctx, x, theta, out_hw, align_corners):
