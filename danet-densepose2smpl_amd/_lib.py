@@ -152,6 +152,7 @@ _SIGNATURES = {
     'danet_mesh_shade_pixels': (c_i, [c_f, c_f, c_i, c_i, c_f, c_i, c_f, c_f, c_fl, c_fl, c_i, c_f, c_f, c_f]),
     'danet_demo_compose': (c_i, [c_f] * 7 + [c_i] * 3 + [c_f, c_f]),
     'danet_pose_eval': (c_i, [c_f, c_f, ctypes.POINTER(c_i), c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f]),
+    'danet_vertex_eval': (c_i, [c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f]),
     'danet_seg_confusion': (c_i, [c_f] * 4 + [ctypes.c_int64] + [c_f] * 4 + [c_i] * 4 + [c_f, c_f]),
     'danet_rotmat_to_angle_axis': (c_i, [c_f, c_i, c_f, c_f]),
     'danet_coco_keypoints': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_fl, c_f, c_f]),

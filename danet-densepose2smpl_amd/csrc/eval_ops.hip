@@ -6,6 +6,10 @@
 //                       then one lane centres, maps, takes the MPJPE and solves the Procrustes problem in fp64: Jacobi on the
 //                       symmetric K^T K gives V and the order of the singular values, U follows from K V, and the last singular
 //                       pair takes the sign that makes det R = +1 (the reference's Z).  HBM / latency bound, no MFMA.
+//   vertex_eval         the PVE rule of DESIGN.md 4c as one launch, one workgroup per sample: three passes over the two meshes (they
+//                       stay in L2: 2 x 82.7 KB at V = 6890), every sum in fp64 through the block sum pose_eval uses -- pelvis dot
+//                       products and centroids; K, var1 and the pelvis-centred distance (PVE); one lane solves the Procrustes problem
+//                       with pose_eval's solver and publishes s R and t through LDS; the aligned distance (PA-PVE).
 //   seg_confusion       eval.py:222-266 for a batch as one launch: one lane per label pixel looks its predicted value up through
 //                       the paste rectangle and the two nearest-neighbour index tables of the uncrop rule, so no
 //                       uncropped image exists.  Counts are wave ballots + popcounts kept in wave-uniform registers over the
@@ -22,11 +26,30 @@ constexpr int kPoseThreads = 256;
 
 struct Mapper { int idx[kNJ]; };
 
-// sum over the 256 lanes of a block; the result is valid in lane 0 of wave 0.  `red` holds 4 doubles per value.
+// sum over the 64 lanes of a wave; the result is valid in lane 0
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
+}
+
+// sums of N values per lane over the block, in fp64: every lane reads them from out[0..N) afterwards.  `red` holds 4 x N doubles
+// and may be reused by the next call (the closing barrier orders its reads before the next writes).
+template <int N, typename Acc, typename Out>
+__device__ __forceinline__ void block_sum(const Acc* __restrict__ acc, double* __restrict__ red, Out* __restrict__ out) {
+    static_assert(N <= kPoseThreads, "one lane per sum adds the four waves' partial sums");
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double s = wave_sum((double)acc[k]);
+        if (lane == 0) red[wave * N + k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const int k = threadIdx.x;
+        out[k] = (Out)(red[k] + red[N + k] + red[2 * N + k] + red[3 * N + k]);
+    }
+    __syncthreads();
 }
 
 __device__ void regress17(const float* __restrict__ verts, const float* __restrict__ Jr, int V, double* __restrict__ red /* [4][51] */,
@@ -45,18 +68,7 @@ __device__ void regress17(const float* __restrict__ verts, const float* __restri
             acc[j * 3 + 2] += w * z;
         }
     }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < kNJ * 3; ++k) {
-        const double s = wave_sum((double)acc[k]);
-        if (lane == 0) red[wave * (kNJ * 3) + k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kNJ * 3) {
-        const int k = threadIdx.x;
-        out[k] = (float)(red[k] + red[kNJ * 3 + k] + red[2 * kNJ * 3 + k] + red[3 * kNJ * 3 + k]);
-    }
-    __syncthreads();
+    block_sum<kNJ * 3>(acc, red, out);
 }
 
 // eigenvectors of the symmetric 3 x 3 matrix A (destroyed) by cyclic Jacobi rotations: A -> diagonal, E -> columns
@@ -114,6 +126,41 @@ __device__ __forceinline__ void any_orthogonal(const double* a, double* o) {
     normalize3(o);
 }
 
+// steps 4-6 of pose_utils.py:10-58 on one lane: from K = X1 X2^T, var1 = sum |X1|^2 and the two centroids the rotation R with
+// det R = +1, the translation t and (returned) the scale of the best similarity transform of set 1 onto set 2
+__device__ double similarity_solve(const double K[3][3], double var1, const double* mu1, const double* mu2, double R[3][3], double* t) {
+    // K = U S V^T: V and S^2 from K^T K
+    double A[3][3], E[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) A[a][b] = K[0][a] * K[0][b] + K[1][a] * K[1][b] + K[2][a] * K[2][b];
+    jacobi3(A, E);
+    int o0 = 0, o1 = 1, o2 = 2;                                             // descending eigenvalues
+    if (A[o0][o0] < A[o1][o1]) { const int s = o0; o0 = o1; o1 = s; }
+    if (A[o0][o0] < A[o2][o2]) { const int s = o0; o0 = o2; o2 = s; }
+    if (A[o1][o1] < A[o2][o2]) { const int s = o1; o1 = o2; o2 = s; }
+    double v0[3] = {E[0][o0], E[1][o0], E[2][o0]}, v1[3] = {E[0][o1], E[1][o1], E[2][o1]}, v2[3];
+    cross3(v0, v1, v2);
+    double u0[3], u1[3], u2[3];
+    for (int a = 0; a < 3; ++a) {
+        u0[a] = K[a][0] * v0[0] + K[a][1] * v0[1] + K[a][2] * v0[2];
+        u1[a] = K[a][0] * v1[0] + K[a][1] * v1[1] + K[a][2] * v1[2];
+    }
+    if (!normalize3(u0)) { u0[0] = 1.0; u0[1] = 0.0; u0[2] = 0.0; }          // K = 0: any rotation is optimal
+    const double d = u0[0] * u1[0] + u0[1] * u1[1] + u0[2] * u1[2];
+    for (int a = 0; a < 3; ++a) u1[a] -= d * u0[a];
+    if (!normalize3(u1)) any_orthogonal(u0, u1);                            // rank one
+    cross3(u0, u1, u2);
+    // R = V Z U^T with det R = +1: both triples are right-handed, so the third pair carries the sign of Z
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) R[a][b] = v0[a] * u0[b] + v1[a] * u1[b] + v2[a] * u2[b];
+    double tr = 0.0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) tr += R[a][b] * K[b][a];                // trace(R K)
+    const double scale = tr / var1;
+    for (int a = 0; a < 3; ++a) t[a] = mu2[a] - scale * (R[a][0] * mu1[0] + R[a][1] * mu1[1] + R[a][2] * mu1[2]);
+    return scale;
+}
+
 // pose_utils.py:10-58 for S1, S2 [J][3] fp32 (J <= 17): the mean distance between S2 and S1 under the best similarity transform
 __device__ double procrustes_error(const float* __restrict__ S1, const float* __restrict__ S2, int J) {
     double mu1[3] = {0, 0, 0}, mu2[3] = {0, 0, 0};
@@ -129,37 +176,8 @@ __device__ double procrustes_error(const float* __restrict__ S1, const float* __
             for (int b = 0; b < 3; ++b) K[a][b] += x1[a] * x2[b];          // K = X1 X2^T
         }
     }
-    // K = U S V^T: V and S^2 from K^T K
-    double A[3][3], E[3][3];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) A[a][b] = K[0][a] * K[0][b] + K[1][a] * K[1][b] + K[2][a] * K[2][b];
-    jacobi3(A, E);
-    int o0 = 0, o1 = 1, o2 = 2;                                             // descending eigenvalues
-    if (A[o0][o0] < A[o1][o1]) { const int t = o0; o0 = o1; o1 = t; }
-    if (A[o0][o0] < A[o2][o2]) { const int t = o0; o0 = o2; o2 = t; }
-    if (A[o1][o1] < A[o2][o2]) { const int t = o1; o1 = o2; o2 = t; }
-    double v0[3] = {E[0][o0], E[1][o0], E[2][o0]}, v1[3] = {E[0][o1], E[1][o1], E[2][o1]}, v2[3];
-    cross3(v0, v1, v2);
-    double u0[3], u1[3], u2[3];
-    for (int a = 0; a < 3; ++a) {
-        u0[a] = K[a][0] * v0[0] + K[a][1] * v0[1] + K[a][2] * v0[2];
-        u1[a] = K[a][0] * v1[0] + K[a][1] * v1[1] + K[a][2] * v1[2];
-    }
-    if (!normalize3(u0)) { u0[0] = 1.0; u0[1] = 0.0; u0[2] = 0.0; }          // K = 0: any rotation is optimal
-    const double d = u0[0] * u1[0] + u0[1] * u1[1] + u0[2] * u1[2];
-    for (int a = 0; a < 3; ++a) u1[a] -= d * u0[a];
-    if (!normalize3(u1)) any_orthogonal(u0, u1);                            // rank one
-    cross3(u0, u1, u2);
-    // R = V Z U^T with det R = +1: both triples are right-handed, so the third pair carries the sign of Z
-    double R[3][3];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) R[a][b] = v0[a] * u0[b] + v1[a] * u1[b] + v2[a] * u2[b];
-    double tr = 0.0;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) tr += R[a][b] * K[b][a];                // trace(R K)
-    const double scale = tr / var1;
-    double t[3];
-    for (int a = 0; a < 3; ++a) t[a] = mu2[a] - scale * (R[a][0] * mu1[0] + R[a][1] * mu1[1] + R[a][2] * mu1[2]);
+    double R[3][3], t[3];
+    const double scale = similarity_solve(K, var1, mu1, mu2, R, t);
     double err = 0.0;
     for (int j = 0; j < J; ++j) {
         double e2 = 0.0;
@@ -202,6 +220,90 @@ __global__ __launch_bounds__(kPoseThreads) void pose_eval_kernel(
         mpjpe[b] = (float)(e / J);
         recon[b] = (float)procrustes_error(s1, s2, J);
     }
+}
+
+// The PVE rule.  P, G: the sample's two meshes, pel: row 0 of the H36M regressor.
+__global__ __launch_bounds__(kPoseThreads) void vertex_eval_kernel(
+    const float* __restrict__ pred_vertices, const float* __restrict__ gt_vertices, const float* __restrict__ pel, int V,
+    float* __restrict__ pve, float* __restrict__ pa_pve)
+{
+    __shared__ double red[4 * 12];
+    __shared__ double s1[12], s2[11], s3[1];
+    __shared__ double xf[12];                                                // s R (row-major), then t
+    const int b = blockIdx.x;
+    const float* __restrict__ P = pred_vertices + (size_t)b * V * 3;
+    const float* __restrict__ G = gt_vertices + (size_t)b * V * 3;
+    // pass 1: pel . P, pel . G, sum P, sum G
+    double a1[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) a1[k] = 0.0;
+    for (int v = threadIdx.x; v < V; v += kPoseThreads) {
+        const double w = (double)pel[v];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double p = (double)P[v * 3 + k], g = (double)G[v * 3 + k];
+            a1[k] += w * p;
+            a1[3 + k] += w * g;
+            a1[6 + k] += p;
+            a1[9 + k] += g;
+        }
+    }
+    block_sum<12>(a1, red, s1);
+    double pp[3], gp[3], mu1[3], mu2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { pp[k] = s1[k]; gp[k] = s1[3 + k]; mu1[k] = s1[6 + k] / V; mu2[k] = s1[9 + k] / V; }
+    // pass 2: K = sum (p - mu1)(g - mu2)^T, var1 = sum |p - mu1|^2, and the distance of the pelvis-centred meshes
+    double a2[11];
+#pragma unroll
+    for (int k = 0; k < 11; ++k) a2[k] = 0.0;
+    for (int v = threadIdx.x; v < V; v += kPoseThreads) {
+        double x1[3], x2[3], e2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double p = (double)P[v * 3 + k], g = (double)G[v * 3 + k];
+            x1[k] = p - mu1[k];
+            x2[k] = g - mu2[k];
+            const double df = (p - pp[k]) - (g - gp[k]);
+            e2 += df * df;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            a2[9] += x1[i] * x1[i];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) a2[i * 3 + j] += x1[i] * x2[j];
+        }
+        a2[10] += sqrt(e2);
+    }
+    block_sum<11>(a2, red, s2);
+    if (threadIdx.x == 0) {
+        pve[b] = (float)(s2[10] / V);
+        double K[3][3], R[3][3], t[3];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) K[i][j] = s2[i * 3 + j];
+        const double scale = similarity_solve(K, s2[9], mu1, mu2, R, t);
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) xf[i * 3 + j] = scale * R[i][j];
+            xf[9 + i] = t[i];
+        }
+    }
+    __syncthreads();
+    // pass 3: the distance after the alignment
+    double m[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) m[k] = xf[k];
+    double a3[1] = {0.0};
+    for (int v = threadIdx.x; v < V; v += kPoseThreads) {
+        const double x = (double)P[v * 3 + 0], y = (double)P[v * 3 + 1], z = (double)P[v * 3 + 2];
+        double e2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double df = (m[i * 3 + 0] * x + m[i * 3 + 1] * y + m[i * 3 + 2] * z + m[9 + i]) - (double)G[v * 3 + i];
+            e2 += df * df;
+        }
+        a3[0] += sqrt(e2);
+    }
+    block_sum<1>(a3, red, s3);
+    if (threadIdx.x == 0) pa_pve[b] = (float)(s3[0] / V);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -312,6 +414,18 @@ extern "C" int danet_pose_eval(const float* pred_vertices, const float* J_regres
     hipLaunchKernelGGL(pose_eval_kernel, dim3(B), dim3(kPoseThreads), 0, (hipStream_t)stream, pred_vertices, J_regressor, m, J,
                        gt_keypoints_3d, gt_vertices, V, mpjpe, recon_err, pred_joints17);
     DANET_CHECK_LAUNCH("pose_eval_kernel");
+    return DANET_OK;
+}
+
+extern "C" int danet_vertex_eval(const float* pred_vertices, const float* gt_vertices, const float* pelvis_row, int B, int V,
+                                 float* pve, float* pa_pve, void* stream)
+{
+    DANET_ENTER();
+    DANET_CHECK_ARG(B > 0 && B < (1 << 24) && V > 0 && V < (1 << 24), "vertex_eval: bad sizes B=%d V=%d", B, V);
+    DANET_CHECK_ARG(pred_vertices && gt_vertices && pelvis_row && pve && pa_pve, "vertex_eval: null pointer");
+    hipLaunchKernelGGL(vertex_eval_kernel, dim3(B), dim3(kPoseThreads), 0, (hipStream_t)stream, pred_vertices, gt_vertices, pelvis_row, V,
+                       pve, pa_pve);
+    DANET_CHECK_LAUNCH("vertex_eval_kernel");
     return DANET_OK;
 }
 

@@ -1,8 +1,9 @@
 """The evaluation pipeline of the reference's eval.py: MPJPE / reconstruction error (Human3.6M P1 / P2, 3DPW, MPI-INF-3DHP) and
 the LSP mask / part accuracy and F1, with the scoring on the device (csrc/eval_ops.hip).
 
-  Evaluator        per-batch scoring: SMPL forward, ops.pose_eval (one launch), for 'lsp' PartRenderer + ops.seg_confusion (one
-                   launch).  Errors and counters stay on the device; summary() makes the one host copy.
+  Evaluator        per-batch scoring: SMPL forward, ops.pose_eval (one launch), with eval_pve ops.vertex_eval (one launch: the PVE rule
+                   of DESIGN.md 4c), for 'lsp' PartRenderer + ops.seg_confusion (one launch).  Errors and counters stay on the
+                   device; summary() makes the one host copy.
   run_evaluation   the reference's loop and signature around a DaNet (infer_net) or an InferenceEngine.
   EvalDataset      an annotation .npz of the reference's layout (datasets/base_dataset.py, is_train=False) + image files.
   uncrop_geometry  the host side of the uncrop rule: paste rectangle and nearest-neighbour index tables that replace
@@ -142,12 +143,17 @@ def _f1(tp, fp, fn):
 class Evaluator(object):
     """Scores batches of predictions for one evaluation dataset.
 
-    Evaluator(dataset_name, J_regressor [17,V], smpl_neutral, smpl_male=None, smpl_female=None, part_renderer=None)
+    Evaluator(dataset_name, J_regressor [17,V], smpl_neutral, smpl_male=None, smpl_female=None, part_renderer=None, eval_pve=False)
     update(batch, para) -- batch: the dict run_evaluation's loader yields (device tensors 'pose', 'betas', 'gender', 'pose_3d',
     'center', 'scale'; for 'lsp' the host lists 'gt_mask' / 'gt_parts'; 'imgname'), para [B,229] = (camera 3, betas 10, 24 rotation
-    matrices).  Enqueues only; nothing is read back.  summary() -> dict with the quantities eval.py prints."""
+    matrices).  Enqueues only; nothing is read back.  summary() -> dict with the quantities eval.py prints.
+    eval_pve (the reference's dead --eval_pve; 'lsp' ignores it): the per-vertex error PVE and its Procrustes-aligned form PA-PVE
+     against the ground-truth mesh -- for '3dpw' the gendered mesh pose_eval is scored against, else the neutral
+    model's mesh of the batch's pose and betas (eval.py:146), where a sample counts iff batch['has_smpl'] is 1 (absent: all).
+    summary() then carries pve / pa_pve (mm, float64 means over the counted samples), pve_per_sample / pa_pve_per_sample and
+    pve_num_samples; with no counted sample the four metric keys are absent."""
 
-    def __init__(self, dataset_name, J_regressor, smpl_neutral, smpl_male=None, smpl_female=None, part_renderer=None):
+    def __init__(self, dataset_name, J_regressor, smpl_neutral, smpl_male=None, smpl_female=None, part_renderer=None, eval_pve=False):
         self.dataset_name = dataset_name
         self.plan = dataset_plan(dataset_name)
         self.smpl_neutral, self.smpl_male, self.smpl_female = smpl_neutral, smpl_male, smpl_female
@@ -162,6 +168,8 @@ class Evaluator(object):
         self.J_regressor = torch.as_tensor(J_regressor).float().contiguous().to(self.device)
         self.counters = torch.zeros(ops.SEG_COUNTERS, dtype=torch.int64, device=self.device)
         self._mpjpe, self._recon, self._j17, self._pose, self._betas, self._cam, self._names = [], [], [], [], [], [], []
+        self.eval_pve = bool(eval_pve) and self.plan['eval_pose']
+        self._pve, self._pa_pve, self._pve_on = [], [], []
 
     def update(self, batch, para):
         if not para.is_cuda:
@@ -180,12 +188,23 @@ class Evaluator(object):
                 if self.plan['gt_source'] == 'joints':
                     gt = batch['pose_3d'].to(self.device)[:, self.plan['joint_mapper_gt'], :-1].contiguous()
                     e, r, j17 = ops.pose_eval(verts, self.J_regressor, self.plan['joint_mapper_h36m'], gt_keypoints_3d=gt)
+                    if self.eval_pve:
+                        gp, gb = batch['pose'].to(self.device), batch['betas'].to(self.device)
+                        gv = self.smpl_neutral(global_orient=gp[:, :3], body_pose=gp[:, 3:], betas=gb).vertices        # eval.py:146
+                        has = batch.get('has_smpl')
+                        counted = torch.ones(B, dtype=torch.bool, device=self.device) if has is None else torch.as_tensor(has).to(self.device).view(B) > 0
                 else:
                     gp, gb = batch['pose'].to(self.device), batch['betas'].to(self.device)
                     vm = self.smpl_male(global_orient=gp[:, :3], body_pose=gp[:, 3:], betas=gb).vertices
                     vf = self.smpl_female(global_orient=gp[:, :3], body_pose=gp[:, 3:], betas=gb).vertices
                     gv = torch.where((batch['gender'].to(self.device) == 1).view(B, 1, 1), vf, vm)
                     e, r, j17 = ops.pose_eval(verts, self.J_regressor, self.plan['joint_mapper_h36m'], gt_vertices=gv)
+                    counted = torch.ones(B, dtype=torch.bool, device=self.device)
+                if self.eval_pve:
+                    pve, pa = ops.vertex_eval(verts, gv, self.J_regressor[0])
+                    self._pve.append(pve)
+                    self._pa_pve.append(pa)
+                    self._pve_on.append(counted)
                 self._mpjpe.append(e)
                 self._recon.append(r)
                 self._j17.append(j17)
@@ -213,6 +232,12 @@ class Evaluator(object):
                 for i, n in enumerate(self._names):
                     acts.setdefault(h36m_action(n), []).append(i)
                 out['actions'] = {a: {'mpjpe': float(mp[ix].mean() * 1000.), 'recon_err': float(re[ix].mean() * 1000.)} for a, ix in acts.items()}
+            if self.eval_pve:
+                on = torch.cat(self._pve_on).cpu().numpy() if self._pve_on else np.zeros(0, bool)
+                out['pve_num_samples'] = int(on.sum())
+                if on.any():
+                    pv, pa = cat(self._pve, (0,))[on], cat(self._pa_pve, (0,))[on]
+                    out.update(pve=float(1000 * pv.mean()), pa_pve=float(1000 * pa.mean()), pve_per_sample=pv, pa_pve_per_sample=pa)
         if self.plan['eval_masks']:
             S = ops.SEG
             tp, fp, fn = (c[S[k]:S[k] + 2].astype(np.float64) for k in ('tp', 'fp', 'fn'))
@@ -237,6 +262,9 @@ def print_summary(s, header='*** Final Results ***'):
     if 'mpjpe' in s:
         print('MPJPE: ' + str(s['mpjpe']))
         print('Reconstruction Error: ' + str(s['recon_err']))
+        if 'pve' in s:
+            print('PVE: ' + str(s['pve']))
+            print('PA-PVE: ' + str(s['pa_pve']))
         print()
     if 'accuracy' in s:
         print('Accuracy: ', s['accuracy'])
@@ -280,6 +308,7 @@ class EvalDataset(object):
         self.betas = np.asarray(d['shape'], np.float64) if has('pose') and has('shape') else np.zeros((n, 10))
         self.pose_3d = np.asarray(d['S'], np.float64) if has('S') else np.zeros((n, 24, 4))
         self.gender = (np.array([0 if str(g) == 'm' else 1 for g in d['gender']], np.int32) if has('gender') else -np.ones(n, np.int32))
+        self.has_smpl = np.asarray(d['has_smpl'], np.float32).reshape(n) if has('has_smpl') else np.ones(n, np.float32)
         self.maskname = [str(m) for m in d['maskname']] if has('maskname') else None
         self.partname = [str(m) for m in d['partname']] if has('partname') else None
 
@@ -293,7 +322,7 @@ class EvalDataset(object):
         item = {'img_raw': np.ascontiguousarray(img[:, :, :3]), 'orig_shape': np.array(img.shape[:2]), 'imgname': os.path.join(self.img_dir, self.imgname[i]),
                 'center': self.center[i].astype(np.float32), 'scale': float(self.scale[i]), 'pose': self.pose[i].astype(np.float32),
                 'betas': self.betas[i].astype(np.float32), 'pose_3d': self.pose_3d[i].astype(np.float32), 'gender': self.gender[i],
-                'sample_index': i, 'maskname': self.maskname[i] if self.maskname else '', 'partname': self.partname[i] if self.partname else ''}
+                'has_smpl': self.has_smpl[i], 'sample_index': i, 'maskname': self.maskname[i] if self.maskname else '', 'partname': self.partname[i] if self.partname else ''}
         if self.dataset == 'lsp':
             item['gt_mask'] = np.ascontiguousarray(read_array(os.path.join(self.label_dir, item['maskname']), gray=True), dtype=np.uint8)
             item['gt_parts'] = np.ascontiguousarray(read_array(os.path.join(self.label_dir, item['partname']), gray=True), dtype=np.uint8)
@@ -311,6 +340,8 @@ def collate(items):
     batch = {'img_raw': raw}
     for k in ('center', 'scale', 'pose', 'betas', 'pose_3d', 'gender', 'orig_shape', 'sample_index'):
         batch[k] = np.stack([np.asarray(it[k]) for it in items])
+    if 'has_smpl' in items[0]:
+        batch['has_smpl'] = np.stack([np.asarray(it['has_smpl'], np.float32) for it in items])
     for k in ('imgname', 'maskname', 'partname'):
         batch[k] = [it[k] for it in items]
     if 'gt_mask' in items[0]:
@@ -322,7 +353,7 @@ def to_device(batch, device, img_res=constants.IMG_RES):
     """Uploads a collated batch and crops its images: adds 'img' [B,3,res,res] (normalised, base_dataset.py:248-251 with no
     augmentation) and, for 'lsp', 'labels' (pack_labels)."""
     out = dict(batch)
-    for k in ('center', 'scale', 'pose', 'betas', 'pose_3d', 'gender'):
+    for k in ('center', 'scale', 'pose', 'betas', 'pose_3d', 'gender') + (('has_smpl',) if 'has_smpl' in batch else ()):
         out[k] = torch.from_numpy(np.ascontiguousarray(batch[k])).to(device, non_blocking=True)
     raw = torch.from_numpy(batch['img_raw']).to(device, non_blocking=True).permute(0, 3, 1, 2).float()
     B = raw.shape[0]
@@ -427,12 +458,18 @@ def _model_parts(model):
     raise TypeError('run_evaluation: model must be a DaNet or an InferenceEngine, got %s' % type(model).__name__)
 
 
+def val_due(step_count, test_steps):
+    """base_trainer.py:89-91: validation follows the steps with step_count % test_steps == 0; never for test_steps 0 / None."""
+    return bool(test_steps) and int(test_steps) > 0 and int(step_count) > 0 and int(step_count) % int(test_steps) == 0
+
+
 def run_evaluation(model, dataset_name, dataset, result_file, batch_size=32, img_res=224, num_workers=32, shuffle=False, log_freq=50,
-                   options=None):
+                   options=None, verbose=True):
     """eval.py:57-316.  `model`: a DaNet in eval mode (infer_net is called) or an InferenceEngine.  `options` may carry what the
     reference reads from its path_config: J_regressor ([17,6890] array or .npy path), smpl_male / smpl_female (SMPL modules),
     part_renderer; what is missing is a seeded synthetic stand-in (the male / female models fall back to the neutral one).
-    Prints the reference's lines and returns the summary dict; with `result_file` writes pred_joints, pose, betas, camera."""
+    options.eval_pve adds the per-vertex errors (Evaluator).  Prints the reference's lines (verbose=False: nothing, for use inside
+    Trainer.fit) and returns the summary dict; with `result_file` writes pred_joints, pose, betas, camera."""
     plan = dataset_plan(dataset_name)
     infer, net = _model_parts(model)
     device = next(net.parameters()).device
@@ -448,18 +485,19 @@ def run_evaluation(model, dataset_name, dataset, result_file, batch_size=32, img
     renderer = opt('part_renderer')
     if plan['eval_masks'] and renderer is None:
         renderer = synthetic_part_renderer(smpl.faces)
-    ev = Evaluator(dataset_name, Jr, smpl, opt('smpl_male') or smpl, opt('smpl_female') or smpl, renderer)
+    ev = Evaluator(dataset_name, Jr, smpl, opt('smpl_male') or smpl, opt('smpl_female') or smpl, renderer, eval_pve=bool(opt('eval_pve')))
     if result_file is not None:
         shuffle = False                                                            # eval.py:81-83
     for step, host in enumerate(iterate_batches(dataset, batch_size, shuffle, num_workers)):
         batch = to_device(host, device, img_res)
         out = infer(batch['img'])
         ev.update(batch, out['para'])
-        if log_freq and step % log_freq == log_freq - 1:
+        if verbose and log_freq and step % log_freq == log_freq - 1:
             print_summary(ev.summary(), 'step %d' % (step + 1))
     s = ev.summary()
     if result_file is not None:
         r = s['results']
         np.savez(result_file, pred_joints=r['pred_joints'], pose=r['pose'], betas=r['betas'], camera=r['camera'])
-    print_summary(s)
+    if verbose:
+        print_summary(s)
     return s

@@ -395,6 +395,24 @@ def pose_eval(pred_vertices, J_regressor, joint_mapper, gt_keypoints_3d=None, gt
     return e, r, j17
 
 
+def vertex_eval(pred_vertices, gt_vertices, pelvis_row):
+    """The PVE rule of DESIGN.md 4c as ONE launch (csrc/eval_ops.hip): pred_vertices, gt_vertices [B,V,3], pelvis_row [V] (row 0 of the
+    H36M joint regressor) -> (pve [B], pa_pve [B]) in metres: the mean vertex distance of the two meshes, each centred at its own
+    pelvis, and the mean distance after the Procrustes alignment of the V raw points.  Allocates its two outputs and nothing else;
+    capturable under torch.cuda.graph."""
+    L = _lib.lib()
+    v = _f32c(_dev_tensor(pred_vertices, 'vertex_eval'))
+    g = _f32c(_dev_tensor(gt_vertices, 'vertex_eval'))
+    w = _f32c(_dev_tensor(pelvis_row, 'vertex_eval'))
+    if v.dim() != 3 or v.shape[2] != 3 or g.shape != v.shape or tuple(w.shape) != (v.shape[1],):
+        raise ValueError('vertex_eval: vertices %s / %s, pelvis_row %s (expected [B,V,3] twice and [V])' % (tuple(v.shape), tuple(g.shape), tuple(w.shape)))
+    B, V = v.shape[0], v.shape[1]
+    pve = torch.empty(B, device=v.device, dtype=torch.float32)
+    pa = torch.empty(B, device=v.device, dtype=torch.float32)
+    check(L.danet_vertex_eval(ptr(v), ptr(g), ptr(w), B, V, ptr(pve), ptr(pa), stream()), 'danet_vertex_eval')
+    return pve, pa
+
+
 SEG_COUNTERS = 32
 SEG = {'tp': 0, 'fp': 2, 'fn': 4, 'accuracy': 6, 'pixel_count': 7, 'parts_tp': 8, 'parts_fp': 15, 'parts_fn': 22,
        'parts_accuracy': 29, 'parts_pixel_count': 30}              # include/danet_hip.h DANET_SEG_*

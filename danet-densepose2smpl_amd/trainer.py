@@ -721,12 +721,51 @@ class Trainer(object):
             return {t: float(v) for t, v in zip([t for t in self.VIS_SCALARS if t in sheets], host[at:].view(np.float32))}
         return {t: float(sheets[t]) for t in self.VIS_SCALARS if t in sheets}
 
+    # ------------------------------------------------------------------------------------------
+    # Validation (train/base_trainer.py:89-91,121-122: `test` is declared and left empty there).
+    def test(self, val, options=None):
+        """Scores the model as it stands on a validation set: val = (dataset_name, dataset), an evaluate.EvalDataset or anything
+        evaluate.iterate_batches takes.  Runs evaluate.run_evaluation(self.model, ..., verbose=False) in eval mode on the step's stream
+        with options.batch_size (options: default self.options; eval_pve, num_workers, J_regressor, smpl_male / smpl_female and
+        part_renderer are read from it) and puts the model back into the mode it found.  -> {'val_dataset', 'val_num_samples',
+        'val_mpjpe', 'val_recon_err'[, 'val_pve', 'val_pa_pve']}; for 'lsp' the accuracy / F1 numbers under val_ names.
+        Leaves the training run alone: eval mode updates no BatchNorm statistics and draws no random numbers, nothing of the
+        optimizer, the loader or step_count is touched, and a captured graph with its static batch and pool is not either -- the
+        loop runs eagerly between replays, like visualize.  The inference forward packs every conv weight afresh from the fp32
+        parameters: the packed-weight cache is emptied before, because a replayed optimizer step changes the
+        parameters without moving the version numbers the cache keys on, and again afterwards, so that no copy packed here can be
+        taken for current at a later validation.  The bank the captured step reads is a buffer of its own and is not touched.
+        With world_size > 1 rank 0 validates the whole set and the other ranks wait at the next step's collective; the
+        validation set is not sharded."""
+        from . import evaluate
+        name, dataset = val
+        o = options if options is not None else self.options
+        if self.distributed and torch.distributed.get_rank() != 0:
+            return {}
+        was_training = self.model.training
+        recorder, _conv.RECORDER = _conv.RECORDER, None      # (a weight bank in its recording step notes training requests only)
+        _conv._PACK_CACHE.clear()
+        self.model.eval()
+        try:
+            with self._on_stream():
+                s = evaluate.run_evaluation(self.model, name, dataset, None, batch_size=int(getattr(o, 'batch_size', 32)),
+                                            num_workers=int(getattr(o, 'num_workers', 0) or 0), log_freq=0, options=o, verbose=False)
+        finally:
+            self.model.train(was_training)
+            _conv._PACK_CACHE.clear()
+            _conv.RECORDER = recorder
+        out = {'val_dataset': name, 'val_num_samples': s['num_samples']}
+        for k in ('mpjpe', 'recon_err', 'pve', 'pa_pve', 'accuracy', 'f1', 'parts_accuracy', 'parts_f1'):
+            if k in s:
+                out['val_' + k] = s[k]
+        return out
+
     @staticmethod
     def latest_checkpoint(checkpoint_dir):
         names = sorted(n for n in os.listdir(checkpoint_dir) if n.startswith('step_') and n.endswith('.pt')) if os.path.isdir(checkpoint_dir) else []
         return os.path.join(checkpoint_dir, names[-1]) if names else None
 
-    def fit(self, train_ds, fits_dict, options, on_step=None):
+    def fit(self, train_ds, fits_dict, options, on_step=None, val=None):
         """Trains on `train_ds` (a datasets.MixedDataset / TrainDataset) with the pseudo-label store `fits_dict`.  options:
         num_epochs, batch_size, checkpoint_steps, summary_steps, pretr_step, train_data, num_workers, time_to_run (seconds), seed,
         shuffle_train, log_dir, checkpoint_dir, resume (a checkpoint file, or True: the newest of checkpoint_dir), pretrained_checkpoint.
@@ -745,11 +784,18 @@ class Trainer(object):
         its sheets go to <log_dir>/vis/step_%08d/<tag>.png and index_fg / p_index_fg into the step's JSON line (a line of its own
         where the summary schedule has none).  Eager runs set `vis_on` on exactly those steps (base_trainer.py:73); a graphed run
         sets it on EVERY step, since the capture freezes the switch, and a replayed visualisation step reads the graph's static
-        outputs before the next replay overwrites them.  visualize itself always runs eagerly, outside the graph."""
+        outputs before the next replay overwrites them.  visualize itself always runs eagerly, outside the graph.
+        options.test_steps (absent, None or 0: off; the reference's default is 1000) with val = (dataset_name, dataset): every step
+        with step_count % test_steps == 0 (base_trainer.py:90) is followed, after its checkpoint, by self.test(val, options); the
+        val_* numbers go into the step's JSON line (a line of its own where the summary schedule has none).  test_steps > 0 without
+        `val` raises ValueError before the first step.  Validation runs eagerly between replays and leaves the run alone (test)."""
         import json
         import time
-        from . import checkpoint, datasets, train_vis
+        from . import checkpoint, datasets, evaluate, train_vis
         opt = lambda k, d=None: d if getattr(options, k, None) is None else getattr(options, k)       # noqa: E731
+        test_steps = int(opt('test_steps', 0))
+        if test_steps > 0 and val is None:
+            raise ValueError('fit: options.test_steps = %d needs a validation set: pass val=(dataset_name, dataset)' % test_steps)
         bs, ckpt_dir, log_dir = int(options.batch_size), opt('checkpoint_dir', 'checkpoints'), opt('log_dir', 'logs')
         endtime = time.time() + float(opt('time_to_run', np.inf))
         book, epoch0 = None, 0
@@ -802,13 +848,19 @@ class Trainer(object):
                     if train_vis.vis_due(self.step_count, vis_interval):
                         line = line or {'step': self.step_count, 'epoch': epoch, 'batch_idx': step}
                         line.update(self.write_sheets(os.path.join(log_dir, 'vis', 'step_%08d' % self.step_count), self.visualize(seen, output, losses)))
-                    if line is not None:
+                    due = evaluate.val_due(self.step_count, test_steps)
+                    if line is not None and not due:
                         log.write(json.dumps(line) + '\n')
                         log.flush()
                     if on_step is not None:
                         on_step(self.step_count, in_dict, losses)
                     if self.step_count % int(opt('checkpoint_steps', 10000)) == 0:
                         save(epoch, step + 1, loader.sampler.dataset_perm)
+                    if due:                                                # (base_trainer.py:89-91, after the checkpoint of the step)
+                        line = line or {'step': self.step_count, 'epoch': epoch, 'batch_idx': step}
+                        line.update(self.test(val, options))
+                        log.write(json.dumps(line) + '\n')
+                        log.flush()
                 book = None                                                # (a checkpoint positions the first epoch only)
                 if (epoch + 1) % 10 == 0:
                     save(epoch + 1, 0, None)

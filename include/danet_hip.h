@@ -733,6 +733,12 @@ int danet_demo_compose(const float* images, const float* glob, const float* part
  * regressed, mapped and centred like the prediction's) -> mpjpe [B], recon_err [B] (Procrustes-aligned, solved in fp64),
  * pred_joints17 [B,17,3] (not centred).  No workspace; capturable.
  *
+ * vertex_eval (the PVE rule of DESIGN.md 4c), ONE launch, one workgroup per sample: pred_vertices, gt_vertices [B,V,3] f32,
+ * pelvis_row [V] f32 (row 0 of the H36M joint regressor) -> pve [B] = mean_v |(p_v - pelvis_row . p) - (g_v - pelvis_row . g)|
+ * and pa_pve [B] = mean_v |s R p_v + t - g_v| under the similarity transform of compute_similarity_transform on the V raw
+ * points (det R = +1), both f32 in metres; every sum and the solve in fp64.  B < 1, V < 1 or a null pointer: DANET_ERR_ARG.
+ * No workspace, nothing allocated; enqueues on `stream` only; capturable.
+ *
  * seg_confusion (eval.py:222-266), ONE launch for a batch: mask [B,res,res] f32 and parts [B,res,res] i64 as
  * PartRenderer.__call__ returns them; gt_mask / gt_parts (either may be NULL) the label images of the batch as packed u8 buffers
  * of label_bytes bytes each, sample b at offsets[b] (i64 [B+1]) with shapes[b] = (rows, cols) (i32 [B,2]); rects i32 [B,6] =
@@ -761,6 +767,8 @@ int danet_demo_compose(const float* images, const float* glob, const float* part
 int danet_pose_eval(const float* pred_vertices, const float* J_regressor, const int32_t* joint_mapper, int J,
                     const float* gt_keypoints_3d, const float* gt_vertices, int B, int V,
                     float* mpjpe, float* recon_err, float* pred_joints17, void* stream);
+int danet_vertex_eval(const float* pred_vertices, const float* gt_vertices, const float* pelvis_row, int B, int V,
+                      float* pve, float* pa_pve, void* stream);
 int danet_seg_confusion(const float* mask, const int64_t* parts, const uint8_t* gt_mask, const uint8_t* gt_parts,
                         int64_t label_bytes, const int64_t* offsets, const int32_t* shapes, const int32_t* rects,
                         const int32_t* tables, int table_len, int B, int res, int max_pixels, int64_t* counters, void* stream);

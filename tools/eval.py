@@ -1,12 +1,14 @@
 """Evaluate a DaNet model on 3D pose (MPJPE, reconstruction error) or on the LSP mask / part segmentation: the reference's eval.py.
 
   python tools/eval.py --dataset h36m-p2 [--checkpoint FILE] [--cfg YAML] [--annot FILE.npz --img_dir DIR [--label_dir DIR]]
-                       [--batch_size N] [--result_file OUT.npz] [--log_freq K] [--engine]
+                       [--batch_size N] [--result_file OUT.npz] [--log_freq K] [--engine] [--eval_pve]
 
 --dataset: h36m-p1 | h36m-p2 | 3dpw | lsp | mpi-inf-3dhp.  --annot is the annotation .npz of the reference's layout; images and
 label images are .npy arrays always, .png / .jpg if PIL is installed.  --joint_regressor (J_regressor_h36m.npy) and --smpl_dir
 (SMPL_MALE / SMPL_FEMALE .pkl, for 3dpw) name the licence-gated files where they exist.  Without --checkpoint the model has seeded
 random weights, and without --annot a small synthetic dataset is written to --scratch, so the tool runs on a machine with no data.
+--eval_pve adds the per-vertex error over all mesh vertices, PVE and its Procrustes-aligned form PA-PVE in mm (the
+reference declares the option and reads it nowhere).
 Last line: one JSON object with the summary."""
 import argparse
 import json
@@ -36,6 +38,7 @@ def main(argv=None):
     ap.add_argument('--smpl_dir', default=None)
     ap.add_argument('--scratch', default=None, help='where the synthetic dataset goes (default: a temporary directory)')
     ap.add_argument('--num_synthetic', default=32, type=int)
+    ap.add_argument('--eval_pve', default=False, action='store_true', help='evaluate PVE')
     a = ap.parse_args(argv)
 
     import torch
@@ -65,7 +68,7 @@ def main(argv=None):
     if a.checkpoint:
         checkpoint.load_pretrained(model, a.checkpoint)
     model = model.cuda().eval()
-    options = types.SimpleNamespace(checkpoint=a.checkpoint, dataset=a.dataset, J_regressor=a.joint_regressor)
+    options = types.SimpleNamespace(checkpoint=a.checkpoint, dataset=a.dataset, J_regressor=a.joint_regressor, eval_pve=a.eval_pve)
     if a.smpl_dir:
         options.smpl_male = SMPL(a.smpl_dir, gender='male').cuda()
         options.smpl_female = SMPL(a.smpl_dir, gender='female').cuda()
@@ -75,7 +78,7 @@ def main(argv=None):
                                 num_workers=a.num_workers, log_freq=a.log_freq, options=options)
     if a.engine:
         runner.close()
-    keep = {k: v for k, v in s.items() if k in ('dataset', 'num_samples', 'mpjpe', 'recon_err', 'accuracy', 'f1', 'parts_accuracy', 'parts_f1', 'actions')}
+    keep = {k: v for k, v in s.items() if k in ('dataset', 'num_samples', 'mpjpe', 'recon_err', 'accuracy', 'f1', 'parts_accuracy', 'parts_f1', 'actions', 'pve', 'pa_pve', 'pve_num_samples')}
     print(json.dumps(keep), flush=True)
     if tmp is not None:
         tmp.cleanup()

@@ -1,11 +1,12 @@
 """Timings of the evaluation pipeline at B = 32 (one JSON line each):
 
   pose      ops.pose_eval (one launch) against metrics.pose_errors (tensor ops, fp64 torch.linalg.svd) on the same inputs
+  pve       ops.vertex_eval (one launch: PVE and PA-PVE over all V vertices) beside ops.pose_eval with ground-truth vertices
   seg       ops.seg_confusion (one launch, label upload included) against the per-sample host loop of tests/eval_oracle.py
             including its device -> host copies of the rendered mask / part images
   loop      images/s of evaluate.run_evaluation for 'h36m-p1' and 'lsp' on a synthetic dataset with an InferenceEngine
 
-  python tools/eval_bench.py [--what pose,seg,loop] [--reps 30] [--images 128]
+  python tools/eval_bench.py [--what pose,pve,seg,loop] [--reps 30] [--images 128]
 
 Variants alternate inside one repetition loop (a drift hits both alike); device work is timed with events on the stream, the host
 loop with the wall clock around a synchronize; medians with p10 / p90 after 5 warm-up rounds."""
@@ -62,6 +63,21 @@ def bench_pose(reps, B=32, V=6890):
                       'pose_eval_vertices': lambda: ops.pose_eval(pv, Jr, m, gt_vertices=gv),
                       'pose_errors_vertices': lambda: metrics.pose_errors(pv, Jr, m, gt_vertices=gv)}, reps)
     res.update(tool='eval_bench', what='pose', B=B, V=V, reps=reps)
+    return res
+
+
+def bench_pve(reps, B=32, V=6890):
+    import torch
+    from danet_densepose2smpl_amd import constants, ops
+    g = torch.Generator().manual_seed(0)
+    Jr = torch.rand(17, V, generator=g)
+    Jr = (Jr / Jr.sum(1, keepdim=True)).cuda()
+    pv = torch.randn(B, V, 3, generator=g).cuda()
+    gv = pv + 0.06 * torch.randn(B, V, 3, generator=g).cuda()
+    row = Jr[0].contiguous()
+    res = _alternate({'vertex_eval': lambda: ops.vertex_eval(pv, gv, row),
+                      'pose_eval_vertices': lambda: ops.pose_eval(pv, Jr, constants.H36M_TO_J14, gt_vertices=gv)}, reps)
+    res.update(tool='eval_bench', what='pve', B=B, V=V, reps=reps)
     return res
 
 
@@ -128,7 +144,7 @@ def bench_loop(images, B=32):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument('--what', default='pose,seg,loop')
+    ap.add_argument('--what', default='pose,pve,seg,loop')
     ap.add_argument('--reps', type=int, default=30)
     ap.add_argument('--images', type=int, default=128)
     a = ap.parse_args(argv)
@@ -136,7 +152,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit('tools/eval_bench.py needs a GPU')
     for w in a.what.split(','):
-        res = {'pose': lambda: bench_pose(a.reps), 'seg': lambda: bench_seg(a.reps), 'loop': lambda: bench_loop(a.images)}[w]()
+        res = {'pose': lambda: bench_pose(a.reps), 'pve': lambda: bench_pve(a.reps), 'seg': lambda: bench_seg(a.reps), 'loop': lambda: bench_loop(a.images)}[w]()
         print(json.dumps(res), flush=True)
     return 0
 

@@ -3,13 +3,17 @@
   python tools/train.py --name RUN [--data_root DIR] [--train_data h36m_dp|h36m_coco_itw] [--num_epochs N] [--batch_size B]
                         [--checkpoint_steps K] [--summary_steps K] [--pretr_step K] [--resume] [--pretrained_checkpoint FILE]
                         [--num_workers W] [--ignore_3d] [--time_to_run SECONDS] [--cfg YAML] [--log_dir DIR] [--graph]
-                        [--vis_interval K]
+                        [--vis_interval K] [--test_steps K [--val_dataset NAME] [--val_annot FILE.npz --val_img_dir DIR] [--eval_pve]]
 
 --data_root holds, for every dataset <ds> of --train_data, <ds>_train.npz (the reference's annotation layout), the image folder <ds>/
 and the fits folders final_fits/ and static_fits/.  Without it a small synthetic 'h36m_dp' set is written to a scratch directory and
 trained on, so the tool runs on a machine with no data.  --graph runs the steps as hipGraph replays (Trainer.fit: two eager steps and
 one capture per pretrain_mode phase).  --vis_interval K (default 0 = off; the reference's default is 1000) writes the image sheets of
-Trainer.visualize to <log_dir>/<name>/vis/step_<n>/<tag>.png after every K-th step.  Logs (train_log.jsonl) and checkpoints go to <log_dir>/<name>/.
+Trainer.visualize to <log_dir>/<name>/vis/step_<n>/<tag>.png after every K-th step.  --test_steps K (default 0 = off; the reference's
+default is 1000, and its test() is empty) runs the evaluation loop of tools/eval.py on --val_dataset (default h36m-p2) after every K-th
+step and writes val_mpjpe, val_recon_err and, with --eval_pve, val_pve / val_pa_pve (mm) into that step's line of train_log.jsonl;
+without --val_annot a small synthetic validation set is written to the run's scratch directory.  Logs (train_log.jsonl) and checkpoints
+go to <log_dir>/<name>/.
 Last line: one JSON object (steps run, last losses)."""
 import argparse
 import json
@@ -20,7 +24,7 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description='DaNet training')
     ap.add_argument('--name', required=True, help='name of the run')
     ap.add_argument('--data_root', default=None)
@@ -41,10 +45,19 @@ def main(argv=None):
     ap.add_argument('--num_synthetic', type=int, default=32)
     ap.add_argument('--graph', action='store_true', help='replay captured steps (one hipGraph per pretrain_mode phase)')
     ap.add_argument('--vis_interval', type=int, default=0, help='steps between image sheets under <log_dir>/<name>/vis (0: none)')
-    a = ap.parse_args(argv)
+    ap.add_argument('--test_steps', type=int, default=0, help='steps between validation runs (0: none)')
+    ap.add_argument('--val_dataset', default='h36m-p2', choices=['h36m-p1', 'h36m-p2', 'lsp', '3dpw', 'mpi-inf-3dhp'])
+    ap.add_argument('--val_annot', default=None, help='annotation .npz of the validation set (default: a synthetic one)')
+    ap.add_argument('--val_img_dir', default=None)
+    ap.add_argument('--eval_pve', action='store_true', help='validation also reports the per-vertex errors PVE / PA-PVE')
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
 
     import torch
-    from danet_densepose2smpl_amd import datasets
+    from danet_densepose2smpl_amd import datasets, evaluate
     from danet_densepose2smpl_amd.config import cfg, cfg_from_file
     from danet_densepose2smpl_amd.fits_dict import FitsDict
     from danet_densepose2smpl_amd.trainer import Trainer
@@ -68,6 +81,16 @@ def main(argv=None):
                 for n in datasets.TRAIN_SETS[a.train_data]]
         train_ds = datasets.MixedDataset(a, sets)
         fits_dirs = (os.path.join(a.data_root, 'final_fits'), os.path.join(a.data_root, 'static_fits'))
+    val = None
+    if a.test_steps > 0:
+        if a.val_annot is None:
+            if tmp is None:
+                tmp = tempfile.TemporaryDirectory()
+            a.val_img_dir = os.path.join(tmp.name, 'val')
+            a.val_annot = evaluate.write_synthetic_dataset(a.val_img_dir, a.val_dataset, n=a.num_synthetic, seed=a.seed)
+        elif a.val_img_dir is None:
+            raise SystemExit('--val_annot needs --val_img_dir')
+        val = (a.val_dataset, evaluate.EvalDataset(a.val_annot, a.val_img_dir, a.val_dataset))
     torch.manual_seed(a.seed)
     trainer = Trainer(a)
     fits = FitsDict(a, train_ds, fits_dirs[0], fits_dirs[1], trainer.device)
@@ -76,7 +99,7 @@ def main(argv=None):
     def on_step(step, in_dict, losses):
         last.clear()
         last.update(step=step, **losses)         # (tensors: read once, after the last step -- no host read per step)
-    steps = trainer.fit(train_ds, fits, a, on_step=on_step)
+    steps = trainer.fit(train_ds, fits, a, on_step=on_step, val=val)
     last = {k: (float(v.detach()) if torch.is_tensor(v) else v) for k, v in last.items()}
     fits.save()
     print(json.dumps({'steps': steps, 'last': last}), flush=True)
