@@ -161,6 +161,10 @@ _SIGNATURES = {
     'danet_label_augment': (c_i, [c_f] * 7 + [c_i] * 3 + [c_f] * 7),
     'danet_vis_grid': (c_i, [c_f, c_f, ctypes.POINTER(ctypes.c_int64)] + [c_i] * 7 + [c_fl, c_i, c_f, c_i, c_i, c_f, c_f, c_f]),
     'danet_vis_joints': (c_i, [c_f, c_i, c_i, c_f, ctypes.POINTER(ctypes.c_int64), c_f, ctypes.POINTER(ctypes.c_int64)] + [c_i] * 6 + [c_f]),
+    'danet_scene_render_ws_bytes': (c_sz, [c_i, c_i, ctypes.c_int64]),
+    'danet_scene_render': (c_i, [c_f, c_f, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, ctypes.c_int64, c_f, c_f, c_i,
+                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
+                                 c_f, c_f, c_f, c_f, c_sz, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations

@@ -561,3 +561,53 @@ def label_augment(rot_flip, xform=None, keypoints=None, smpl_2dkps=None, pose_3d
                                 o('keypoints'), o('smpl_2dkps'), o('pose_3d'), o('pose'), o('fits_pose'), o('fits_betas'), stream()),
           'danet_label_augment')
     return outs
+
+
+def scene_render(verts, vcol, faces2, cam_t, proj, dscale, person_frame, src, offsets, shapes, return_aux=False, out=None, host=None):
+    """The scene rule of DESIGN.md in three launches (csrc/scene_ops.hip): the shaded meshes of P people drawn into the N frames they
+    were found in, the people of a frame sharing one depth buffer.  verts / vcol [P,V,3] f32: the two halves of mesh_shade_vertices'
+    workspace; faces2 [F2,3] int32 (both windings); cam_t [P,3], proj [P,6], dscale [P] f32 (scene.person_cameras builds them);
+    person_frame [P] int32, non-decreasing; src / offsets int64 [N+1] / shapes int32 [N,2]: batch_crop's packed uint8 HWC frames.
+    -> out (uint8, the size and layout of src; `out`, or a new tensor), with return_aux also ids (int32 per frame pixel, person * F2
+    + face or -1) and depth (f32 per frame pixel, +inf where empty).  `host`: (person_frame, offsets, shapes) as host arrays, which
+    the entry point checks before it launches; without it they are read back from the device (a synchronisation: pass it to capture
+    the call under torch.cuda.graph)."""
+    import ctypes
+    import numpy as np
+    L = _lib.lib()
+    s = _dev_tensor(src, 'scene_render')
+    if s.dtype != torch.uint8 or s.dim() != 1 or s.numel() == 0:
+        raise ValueError('scene_render: the frames come as one packed, non-empty uint8 buffer')
+    v, c = _f32c(_dev_tensor(verts, 'scene_render')), _f32c(_dev_tensor(vcol, 'scene_render'))
+    if v.dim() != 3 or v.shape[2] != 3 or c.shape != v.shape:
+        raise ValueError('scene_render: verts %s, vcol %s (expected two [P,V,3])' % (tuple(v.shape), tuple(c.shape)))
+    P, V = v.shape[0], v.shape[1]
+    N = offsets.numel() - 1
+    F2 = faces2.shape[0]
+    _typed(faces2, torch.int32, (F2, 3), 'scene_render: faces2')
+    ct, pj, ds = (_f32c(_dev_tensor(t, 'scene_render')) for t in (cam_t, proj, dscale))
+    if tuple(ct.shape) != (P, 3) or tuple(pj.shape) != (P, 6) or ds.numel() != P:
+        raise ValueError('scene_render: cam_t %s, proj %s, dscale %s (expected [P,3], [P,6], [P] with P = %d)'
+                         % (tuple(ct.shape), tuple(pj.shape), tuple(ds.shape), P))
+    _typed(person_frame, torch.int32, (P,), 'scene_render: person_frame')
+    _typed(offsets, torch.int64, (N + 1,), 'scene_render: offsets')
+    _typed(shapes, torch.int32, (N, 2), 'scene_render: shapes')
+    if host is None:
+        host = (person_frame.cpu().numpy(), offsets.cpu().numpy(), shapes.cpu().numpy())
+    hp, ho, hs = (np.ascontiguousarray(a, dt) for a, dt in zip(host, (np.int32, np.int64, np.int32)))
+    if hp.size != P or ho.size != N + 1 or hs.size != 2 * N:
+        raise ValueError('scene_render: host copies of %d, %d, %d elements for P = %d, N = %d' % (hp.size, ho.size, hs.size, P, N))
+    npix = max(int(ho[-1] - ho[0]) // 3, 0) if N > 0 else 0
+    if out is None:
+        out = torch.empty_like(s)
+    else:
+        _typed(out, torch.uint8, tuple(s.shape), 'scene_render: out')
+    ids = torch.empty(npix, device=s.device, dtype=torch.int32) if return_aux else None
+    depth = torch.empty(npix, device=s.device, dtype=torch.float32) if return_aux else None
+    nws = L.danet_scene_render_ws_bytes(P, V, npix)
+    ws = torch.empty(nws // 8 + 1, device=s.device, dtype=torch.int64)
+    check(L.danet_scene_render(ptr(v), ptr(c), P, V, ptr(faces2), F2, ptr(ct), ptr(pj), ptr(ds), ptr(person_frame), ptr(s), s.numel(),
+                               ptr(offsets), ptr(shapes), N, hp.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                               ho.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), hs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                               ptr(out), ptr(ids), ptr(depth), ptr(ws), nws, stream()), 'danet_scene_render')
+    return (out, ids, depth) if return_aux else out

@@ -866,6 +866,29 @@ int danet_vis_grid(const void* a, const void* b, const int64_t* strides, int dty
 int danet_vis_joints(float* sheet, int Hs, int Ws, const float* joints, const int64_t* joint_strides, const float* vis,
                      const int64_t* vis_strides, int B, int J, int H, int W, int nrow, int padding, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Scene rasteriser (csrc/scene_ops.hip; forward only, scene.py is the caller; DESIGN.md "scene rule"): the shaded meshes of P
+ * people drawn into the N uncropped frames they were found in, one depth order per frame.  Three launches, a straight chain on
+ * `stream`, no allocation, capturable.
+ *
+ * verts / vcol [P,V,3] f32 are the two halves of mesh_shade_vertices' workspace (B = P); faces2 [F2,3] i32 holds both windings.
+ * Per person: cam_t [P,3] is added to the vertices, proj [P,6] maps the normalised image plane (x_n, y_n) = ((X+tx)/(Z+tz),
+ * (Y+ty)/(Z+tz)) to frame pixel index coordinates, col = p0 x_n + p1 y_n + p2, row = p3 x_n + p4 y_n + p5 (pixel centres at
+ * integers), dscale [P] makes depths comparable, d = (Z+tz) dscale, and person_frame [P] i32 (non-decreasing) names the frame.
+ * The frames are batch_crop's layout: src packed uint8 HWC of src_bytes bytes, offsets [N+1] i64 (bytes, from 0), shapes [N,2]
+ * i32 (rows, cols).  host_person_frame / host_offsets / host_shapes are HOST copies of the three index arrays: every check is
+ * made on them before anything is launched (person_frame in [0, N) and non-decreasing, offsets[n+1] - offsets[n] = 3 H W,
+ * offsets[N] <= src_bytes, P * F2 < 2^31).  out: uint8, the size and layout of src, every byte written once (a pixel no face
+ * covers is its source bytes).  ids (may be NULL): i32 per frame pixel in frame order, person * F2 + face or -1; depth (may be
+ * NULL): f32 per frame pixel, +inf where empty.  ws: danet_scene_render_ws_bytes(P, V, offsets[N] / 3) bytes, 8-byte aligned.
+ */
+size_t danet_scene_render_ws_bytes(int P, int V, int64_t num_pixels);
+int danet_scene_render(const float* verts, const float* vcol, int P, int V, const int32_t* faces2, int F2,
+                       const float* cam_t, const float* proj, const float* dscale, const int32_t* person_frame,
+                       const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int32_t* shapes, int N,
+                       const int32_t* host_person_frame, const int64_t* host_offsets, const int32_t* host_shapes,
+                       uint8_t* out, int32_t* ids, float* depth, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
