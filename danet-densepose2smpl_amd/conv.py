@@ -339,6 +339,11 @@ def _empty_nhwc(B, C, H, W, dtype, device):
     return torch.empty(B, H, W, C, dtype=dtype, device=device).permute(0, 3, 1, 2)
 
 
+def nptr(t):
+    """ptr() of the NHWC storage behind a [B,C,H,W] tensor (None -> NULL): refuses what is not on the device or not channels_last-contiguous."""
+    return None if t is None else ptr(t.permute(0, 2, 3, 1))
+
+
 class WeightBank(object):
     """All packed weights of a model in ONE bf16 buffer, repacked by ONE launch per step.
 
@@ -515,8 +520,8 @@ def _bn_bwd_ptrs(bn_bwd):
         return None, None, None, None, 0
     x, gate_t, saved, red, gate = bn_bwd
     gate = int(gate) if gate_t is not None else 0
-    by = None if gate_t is None else ptr(gate_t if gate else gate_t.permute(0, 2, 3, 1))
-    return ptr(x.permute(0, 2, 3, 1)), by, ptr(saved), ptr(red), gate
+    by = ptr(gate_t) if gate else nptr(gate_t)
+    return nptr(x), by, ptr(saved), ptr(red), gate
 
 
 def _conv_fwd_raw(x, wp, bias, B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups, transposed, relu, out_fp32,
@@ -530,9 +535,8 @@ def _conv_fwd_raw(x, wp, bias, B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, di
     bx, by, sv, rd, gate = _bn_bwd_ptrs(bn_bwd)
     with _timed(lambda: _kernel_name(L.danet_conv_forward_kernel(*dims, int(transposed), int(out_fp32)), (B, H, W, Cin, Cout) if bn_bwd is None else None),
                 lambda: _flops(dims), ('dgrad' if transposed else 'fwd', B, H, W, Cin, Cout, R, stride, groups)):
-        check(L.danet_conv_forward(ptr(x.permute(0, 2, 3, 1)), ptr(wp), ptr(bias), ptr(y.permute(0, 2, 3, 1)), *dims, int(transposed),
-                                   int(relu), int(out_fp32), ptr(bn_sums), bx, by, sv, rd,
-                                   None if addend is None else ptr(addend.permute(0, 2, 3, 1)), gate, stream()), 'danet_conv_forward')
+        check(L.danet_conv_forward(nptr(x), ptr(wp), ptr(bias), nptr(y), *dims, int(transposed),
+                                   int(relu), int(out_fp32), ptr(bn_sums), bx, by, sv, rd, nptr(addend), gate, stream()), 'danet_conv_forward')
     if TRACE is not None:
         TRACE.append(('dgrad' if transposed else 'conv', (B, H, W, Cin, Cout, R, stride), y.float().abs().mean()))
     return y
@@ -543,7 +547,7 @@ def _conv_stem_raw(x, wp16, B, H, W, Cin, OH, OW, Cout, bn_sums=None):
     L = _lib.lib()
     y = _empty_nhwc(B, Cout, OH, OW, torch.bfloat16, x.device)
     with _timed('conv_stem_kernel', 2.0 * B * OH * OW * Cout * Cin * 49, ('fwd', B, H, W, Cin, Cout, 7, 2, 1)):
-        check(L.danet_conv_stem_forward(ptr(x.permute(0, 2, 3, 1)), ptr(wp16), ptr(y.permute(0, 2, 3, 1)), B, H, W, Cin, OH, OW, Cout, ptr(bn_sums), stream()),
+        check(L.danet_conv_stem_forward(nptr(x), ptr(wp16), nptr(y), B, H, W, Cin, OH, OW, Cout, ptr(bn_sums), stream()),
               'danet_conv_stem_forward')
     return y
 
@@ -559,8 +563,7 @@ def _conv3x3a_raw(x, wp16, B, H, W, transposed, bn_sums=None, bn_bwd=None, adden
     y = _empty_nhwc(B, 64, H, W, torch.bfloat16, x.device)
     bx, by, sv, rd, gate = _bn_bwd_ptrs(bn_bwd)
     with _timed('conv3x3a_kernel', 2.0 * B * H * W * 64 * 64 * 9, ('dgrad' if transposed else 'fwd', B, H, W, 64, 64, 3, 1, 1)):
-        check(L.danet_conv3x3a(ptr(x.permute(0, 2, 3, 1)), ptr(wp16), ptr(y.permute(0, 2, 3, 1)), B, H, W, int(transposed), ptr(bn_sums), bx, by, sv, rd, gate,
-                               None if addend is None else ptr(addend.permute(0, 2, 3, 1)), stream()), 'danet_conv3x3a')
+        check(L.danet_conv3x3a(nptr(x), ptr(wp16), nptr(y), B, H, W, int(transposed), ptr(bn_sums), bx, by, sv, rd, gate, nptr(addend), stream()), 'danet_conv3x3a')
     return y
 
 
@@ -571,7 +574,7 @@ def _conv_stem_dgrad_raw(gy, wp16t, B, H, W, Cin, OH, OW, Cout, bn_bwd=None):
     gx = _empty_nhwc(B, Cin, H, W, torch.bfloat16, gy.device)
     bx, by, sv, rd, _ = _bn_bwd_ptrs(bn_bwd)
     with _timed('conv_stem_dgrad_kernel', 2.0 * B * OH * OW * Cout * Cin * 49, ('dgrad', B, OH, OW, Cout, Cin, 7, 2, 1)):
-        check(L.danet_conv_stem_dgrad(ptr(gy.permute(0, 2, 3, 1)), ptr(wp16t), ptr(gx.permute(0, 2, 3, 1)), B, H, W, Cin, OH, OW, Cout, bx, by, sv, rd, stream()),
+        check(L.danet_conv_stem_dgrad(nptr(gy), ptr(wp16t), nptr(gx), B, H, W, Cin, OH, OW, Cout, bx, by, sv, rd, stream()),
               'danet_conv_stem_dgrad')
     return gx
 
@@ -705,7 +708,7 @@ def channel_sum(gy):
     out = out.view(torch.float64) if zero else torch.empty(C * ncopy, dtype=torch.float64, device=gy.device)
     L = _lib.lib()
     fn = L.danet_channel_sum_f32 if gy.dtype == torch.float32 else L.danet_channel_sum
-    check(fn(ptr(gy.permute(0, 2, 3, 1)), B * H * W, C, ptr(out), int(zero), ncopy, stream()), 'danet_channel_sum')
+    check(fn(nptr(gy), B * H * W, C, ptr(out), int(zero), ncopy, stream()), 'danet_channel_sum')
     return out.float() if ncopy == 1 else out.view(ncopy, C).sum(0).float()
 
 
@@ -853,7 +856,7 @@ def _wgrad_into(gw, x, gy, B, H, W, Cin, OH, OW, Cout, Cin_g, R, S, stride, pad,
         nws = L.danet_conv_wgrad_rows_ws_floats(B, OH, OW, Cin, Cout, R, S, groups)
         ws = torch.empty(nws, dtype=torch.float32, device=x.device)
         with _timed('conv_wgrad_rows_kernel', 2.0 * B * OH * OW * Cout * Cin_g * R * S, ('wgrad', B, H, W, Cin, Cout, R, stride, groups)):
-            check(L.danet_conv_wgrad_rows(ptr(x.permute(0, 2, 3, 1)), ptr(gy.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), nws,
+            check(L.danet_conv_wgrad_rows(nptr(x), nptr(gy), ptr(gw), ptr(ws), nws,
                                           B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, groups, 0.0, stream()), 'danet_conv_wgrad_rows')
         return
     if _enqueue_wgrad(gw.data_ptr(), weight, x, gy, B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups):
@@ -861,7 +864,7 @@ def _wgrad_into(gw, x, gy, B, H, W, Cin, OH, OW, Cout, Cin_g, R, S, stride, pad,
     if USE_WGRAD3X3 and L.danet_conv_wgrad3x3_ok(H, W, Cin, Cout, R, S, stride, pad, dil, groups):
         nws = L.danet_conv_wgrad3x3_ws_floats(B, H, W, Cin, Cout, groups, stride)
         ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-        args = (ptr(x.permute(0, 2, 3, 1)), ptr(gy.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), nws, B, H, W, Cin, Cout, groups, stride, 0.0)
+        args = (nptr(x), nptr(gy), ptr(gw), ptr(ws), nws, B, H, W, Cin, Cout, groups, stride, 0.0)
         if PROFILER is None:
             check(L.danet_conv_wgrad3x3(*args, 0, stream()), 'danet_conv_wgrad3x3')
         else:                                          # the MFMA kernel and the reduction bracketed separately
@@ -884,7 +887,7 @@ def _wgrad_into(gw, x, gy, B, H, W, Cin, OH, OW, Cout, Cin_g, R, S, stride, pad,
         kid = L.danet_conv_wgrad_kernel_id(Cin, Cout, groups, R * S)
         return 'conv_wgrad_kernel<%d, %d, %d>' % (kid // 100, (kid // 10) % 10, kid % 10)
     with _timed(name, 2.0 * B * OH * OW * Cout * Cin_g * R * S, ('wgrad', B, H, W, Cin, Cout, R, stride, groups)):
-        check(L.danet_conv_wgrad(ptr(x.permute(0, 2, 3, 1)), ptr(gy.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), nws,
+        check(L.danet_conv_wgrad(nptr(x), nptr(gy), ptr(gw), ptr(ws), nws,
                                  B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, dil, groups, 0.0, int(ws_zero), stream()),
               'danet_conv_wgrad')
 
@@ -1052,24 +1055,15 @@ class MultiConvFunction(torch.autograd.Function):
             # conv -> BatchNorm (+ residual) (+ ReLU) in ONE launch when the streamed 3x3 kernel takes the set (csrc/conv3x3s.hip
             # s3_bn_tail), else the two launches from inside the same call: either way the BatchNorm's outputs exist afterwards and
             # nn.MultiBatchNormFunction finds them on the convolution's output (`_bn_done`)
+            from . import nn as _nn       # (nn imports this module; a spec only ever comes from nn.multi_conv_bn)
             bjobs = (_lib.BnFwdJob * n)()
             done = []
             for i in range(n):
                 spec = bn['jobs'][i]
-                B, Cout, OH, OW = ys[i].shape
                 res = None if spec['res'] is None else nhwc_as(spec['res'], torch.bfloat16)
-                if res is not None and res.shape != ys[i].shape:
-                    raise ValueError('residual shape %s != %s' % (tuple(res.shape), tuple(ys[i].shape)))
-                out = _empty_nhwc(B, Cout, OH, OW, torch.bfloat16, ys[i].device)
-                saved = torch.empty(2, Cout, dtype=torch.float32, device=ys[i].device)
-                mask = torch.empty(B * OH * OW * Cout // 4, dtype=torch.uint8, device=ys[i].device) if spec['want_mask'] else None
-                j = bjobs[i]
-                j.x, j.res, j.y = ys[i].data_ptr(), None if res is None else res.data_ptr(), out.data_ptr()
-                j.gamma, j.beta = spec['gamma'].data_ptr(), spec['beta'].data_ptr()
-                j.running_mean = None if spec['running_mean'] is None else spec['running_mean'].data_ptr()
-                j.running_var = None if spec['running_var'] is None else spec['running_var'].data_ptr()
-                j.saved, j.sums, j.mask = saved.data_ptr(), sums_l[i].data_ptr(), None if mask is None else mask.data_ptr()
-                j.M, j.C, j.sums_state, j.relu = B * OH * OW, Cout, 2, int(spec['relu'])
+                out, saved, mask = _nn._bn_fwd_outputs(ys[i], res, True, spec['relu'])
+                _nn._bn_fwd_job(bjobs[i], ys[i], res, out, spec['gamma'], spec['beta'], spec['running_mean'], spec['running_var'],
+                                saved, sums_l[i], 2, mask, spec['relu'])
                 done.append((out, saved, mask))
                 keep += [res, spec['gamma'], spec['beta']]
             was_fused = ctypes.c_int(0)

@@ -11,7 +11,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import conv as _conv
 from ._lib import ptr, check, stream
-from .conv import Conv2d, conv2d, nhwc_bf16, nhwc_as, nhwc_act, _empty_nhwc, ARENA  # noqa: F401
+from .conv import Conv2d, conv2d, nhwc_bf16, nhwc_as, nhwc_act, _empty_nhwc, nptr, ARENA  # noqa: F401
 
 
 def _k(L, name, dtype):
@@ -236,6 +236,68 @@ class SideBranch:
         return _SideWindowOpen.apply(t) if self.window else t
 
 
+def _dp(t):
+    return None if t is None else t.data_ptr()
+
+
+def _bn_relu_gate(training, relu, has_res):
+    """The ReLU gate of a BatchNorm(+residual)(+ReLU) -> (want_mask, mask_mode, save_y), from RELU_MASK and conv.FUSE_BN_BWD_REDUCE as
+    they are NOW.  want_mask: the forward writes a byte mask (csrc/norm_act.hip ldmask).  mask_mode: where the backward takes the gate
+    from -- 0 the saved output y, 1 the byte mask (with a residual), 2 recomputed from x (without one: the mask then only serves the
+    consumer conv's fused reduction, conv._bn_gate).  save_y: autograd keeps y, for mode 0 only.
+    Without ReLU there is no gate and the mode is 0.  No kernel reads the mode without `relu` (csrc/norm_act.hip: the reduce and the
+    apply kernel dispatch on `relu ? mask_mode : 3`, the one-pass kernel asks `a.relu && a.mask_mode == ...`, the argument checks of
+    danet_bn_backward, danet_bn_backward_multi and danet_bn_backward_onepass_ok begin `!relu ||`; the one-pass kernel's one
+    unconditional read only asks `mask_mode == 1`), and conv._bn_gate returns at `not bn_ctx.relu` before it looks at anything.
+    In eval mode nothing is saved and there is no backward: (False, 0, False)."""
+    if not (training and relu):
+        return False, 0, False
+    if not RELU_MASK:
+        return False, 0, True
+    if has_res:
+        return True, 1, False
+    return bool(_conv.FUSE_BN_BWD_REDUCE), 2, False
+
+
+def _bn_fwd_outputs(x, res, training, relu):
+    """(y, saved, mask) of one BatchNorm over x: the output, the [2, C] batch statistics (training) and the ReLU byte mask when the
+    gate wants one; res (None allowed) is NHWC in x's dtype already and must have x's shape."""
+    if res is not None and res.shape != x.shape:
+        raise ValueError('residual shape %s != %s' % (tuple(res.shape), tuple(x.shape)))
+    B, C, H, W = x.shape
+    y = _empty_nhwc(B, C, H, W, x.dtype, x.device)
+    saved = torch.empty(2, C, dtype=torch.float32, device=x.device) if training else None
+    mask = torch.empty(B * H * W * C // 4, dtype=torch.uint8, device=x.device) if _bn_relu_gate(training, relu, res is not None)[0] else None
+    return y, saved, mask
+
+
+def _bn_fwd_job(j, x, res, y, gamma, beta, running_mean, running_var, saved, sums, sums_state, mask, relu):
+    B, C, H, W = x.shape
+    j.x, j.res, j.y = x.data_ptr(), _dp(res), y.data_ptr()
+    j.gamma, j.beta = gamma.data_ptr(), beta.data_ptr()
+    j.running_mean, j.running_var = _dp(running_mean), _dp(running_var)
+    j.saved, j.sums, j.mask = saved.data_ptr(), sums.data_ptr(), _dp(mask)
+    j.M, j.C, j.sums_state, j.relu = B * H * W, C, sums_state, int(relu)
+
+
+def _bn_bwd_job(j, gy, x, y, gamma, beta, saved, mask, mask_mode, dx, dres, dparam, red, red_state, relu):
+    B, C, H, W = x.shape
+    j.dy, j.x, j.y = gy.data_ptr(), x.data_ptr(), _dp(y)
+    j.gamma, j.beta, j.saved = _dp(gamma), _dp(beta), saved.data_ptr()
+    j.mask, j.mask_mode = _dp(mask), int(mask_mode)
+    j.dx, j.dres, j.dparam, j.red = dx.data_ptr(), _dp(dres), dparam.data_ptr(), red.data_ptr()
+    j.M, j.C, j.red_state, j.relu = B * H * W, C, red_state, int(relu)
+
+
+def _bn_scratch(floats, device):
+    """Statistics / reduction scratch of the single path -> (tensor, state): zeroed arena memory (True: the kernels' state 1), or
+    outside an arena plain memory that the kernel zeroes itself (False: state 0)."""
+    t = ARENA.alloc(floats)
+    if t is None:
+        return torch.empty(floats, dtype=torch.float32, device=device), False
+    return t, True
+
+
 class BatchNormActFunction(torch.autograd.Function):
     """y = [relu](batch_norm(x) [+ res]) on NHWC bf16; training or eval statistics."""
 
@@ -246,37 +308,21 @@ class BatchNormActFunction(torch.autograd.Function):
         dt = x.dtype
         B, C, H, W = x.shape
         M = B * H * W
-        if res is not None:
-            res = nhwc_as(res, dt)
-            if res.shape != x.shape:
-                raise ValueError('residual shape %s != %s' % (tuple(res.shape), tuple(x.shape)))
-        y = _empty_nhwc(B, C, H, W, dt, x.device)
-        saved = torch.empty(2, C, dtype=torch.float32, device=x.device) if training else None
+        res = None if res is None else nhwc_as(res, dt)
+        y, saved, mask = _bn_fwd_outputs(x, res, training, relu)
         sums, sums_zero = None, False
         if training and fused_sums is not None:
             sums, sums_zero = fused_sums, 2                   # accumulated by the producing conv's epilogue
         elif training:
-            sums = ARENA.alloc(L.danet_bn_ws_floats(C))
-            sums_zero = sums is not None
-            if sums is None:
-                sums = torch.empty(L.danet_bn_ws_floats(C), dtype=torch.float32, device=x.device)
+            sums, sums_zero = _bn_scratch(L.danet_bn_ws_floats(C), x.device)
         g = None if gamma is None else gamma.detach().float().contiguous()
         b = None if beta is None else beta.detach().float().contiguous()
-        # ReLU gate for the backward without re-reading y (csrc/norm_act.hip ldmask): a byte mask with a residual,
-        # recomputed from x without one
-        # (without a residual the BatchNorm's own backward recomputes the gate; the mask then only serves conv._bn_gate)
-        mask = torch.empty(M * C // 4, dtype=torch.uint8, device=x.device) \
-            if (training and relu and RELU_MASK and (res is not None or _conv.FUSE_BN_BWD_REDUCE)) else None
-        check(_k(L, 'danet_bn_forward', dt)(ptr(x.permute(0, 2, 3, 1)), None if res is None else ptr(res.permute(0, 2, 3, 1)),
-                                 ptr(y.permute(0, 2, 3, 1)), M, C, ptr(g), ptr(b), ptr(running_mean), ptr(running_var),
-                                 ptr(saved), ptr(sums), int(sums_zero), float(momentum), float(eps), int(training), int(relu),
-                                 ptr(mask), stream()),
-              'danet_bn_forward')
+        check(_k(L, 'danet_bn_forward', dt)(nptr(x), nptr(res), nptr(y), M, C, ptr(g), ptr(b), ptr(running_mean), ptr(running_var),
+                                            ptr(saved), ptr(sums), int(sums_zero), float(momentum), float(eps), int(training), int(relu),
+                                            ptr(mask), stream()), 'danet_bn_forward')
         if training:
-            # the BatchNorm's own backward recomputes the gate from x when it can (no residual: no mask read); the mask then
-            # only serves the consumer conv's fused reduction (conv._bn_gate)
-            ctx.mask_mode = (2 if res is None else (1 if mask is not None else 0)) if RELU_MASK else 0
-            ctx.save_for_backward(x, y if (relu and ctx.mask_mode == 0) else None, g, saved, b, mask)
+            _, ctx.mask_mode, save_y = _bn_relu_gate(True, relu, res is not None)
+            ctx.save_for_backward(x, y if save_y else None, g, saved, b, mask)
             ctx.relu = relu
             ctx.has_res = res is not None
             ctx.link = link
@@ -307,10 +353,7 @@ class BatchNormActFunction(torch.autograd.Function):
         if red is not None:
             red_zero = 2
         else:
-            red = ARENA.alloc(L.danet_bn_ws_floats(C))
-            red_zero = red is not None
-            if red is None:
-                red = torch.empty(L.danet_bn_ws_floats(C), dtype=torch.float32, device=x.device)
+            red, red_zero = _bn_scratch(L.danet_bn_ws_floats(C), x.device)
         dparam = torch.empty(2, C, dtype=torch.float32, device=x.device)      # rows: d beta, d gamma
         bar = _onepass_bar(x.device) if (red_zero != 2 and (C <= 1024 or (C % 1024 == 0 and C <= 12288)) and dt == torch.bfloat16) else None
         done = False
@@ -318,24 +361,16 @@ class BatchNormActFunction(torch.autograd.Function):
             if red_zero is False:
                 red.zero_()
             job = (_lib.BnBwdJob * 1)()
-            j = job[0]
-            j.dy, j.x, j.y = gy.data_ptr(), x.data_ptr(), None if y is None else y.data_ptr()
-            j.gamma, j.saved = None if g is None else g.data_ptr(), saved.data_ptr()
-            j.dx, j.dres, j.dparam, j.red = dx.data_ptr(), None if dres is None else dres.data_ptr(), dparam.data_ptr(), red.data_ptr()
-            j.beta, j.mask, j.mask_mode = None if b is None else b.data_ptr(), None if mask is None else mask.data_ptr(), int(ctx.mask_mode)
-            j.M, j.C, j.red_state, j.relu = M, C, 1, int(ctx.relu)
+            _bn_bwd_job(job[0], gy, x, y, g, b, saved, mask, ctx.mask_mode, dx, dres, dparam, red, 1, ctx.relu)
             budget = onepass_budget(x.device)
             if L.danet_bn_backward_onepass_ok(ctypes.addressof(job), 1, budget):
                 check(L.danet_bn_backward_onepass(ctypes.addressof(job), 1, ptr(bar), budget, stream()), 'danet_bn_backward_onepass')
                 _conv.FUSION['bn_bwd_onepass'] += 1
                 done = True
         if not done:
-            check(_k(L, 'danet_bn_backward', dt)(ptr(gy.permute(0, 2, 3, 1)), ptr(x.permute(0, 2, 3, 1)),
-                                  None if y is None else ptr(y.permute(0, 2, 3, 1)), M, C, ptr(g), ptr(saved),
-                                  int(ctx.relu), ptr(dx.permute(0, 2, 3, 1)),
-                                  None if dres is None else ptr(dres.permute(0, 2, 3, 1)), ptr(dparam), ptr(red), int(red_zero),
-                                  int(ctx.mask_mode), ptr(mask), ptr(b), stream()),
-              'danet_bn_backward')
+            check(_k(L, 'danet_bn_backward', dt)(nptr(gy), nptr(x), nptr(y), M, C, ptr(g), ptr(saved), int(ctx.relu), nptr(dx), nptr(dres),
+                                                 ptr(dparam), ptr(red), int(red_zero), int(ctx.mask_mode), ptr(mask), ptr(b), stream()),
+                  'danet_bn_backward')
         if _conv.TRACE is not None:
             _conv.TRACE.append(('bn_bwd' + ('+red' if red_zero == 2 else ''), tuple(x.shape), dx.float().abs().mean()))
         # unbind gives two independent-looking tensors that AccumulateGrad can keep without a clone
@@ -361,46 +396,54 @@ class BatchNorm2d(nn.BatchNorm2d):
             else:
                 BatchNorm2d._ran.append(self.num_batches_tracked)
 
-    def forward(self, x, res=None, relu=False, link=None):
+    def _prologue(self, x):
+        """What every launch of this module starts with -> (training, fused): `fused` = the batch statistics the producing conv's
+        epilogue left on x (None: this launch sums them itself); in training mode counts the batch and ticks FUSION['bn_stats_*']."""
         training = self.training or not self.track_running_stats
+        fused = None
         if training:
             self._count()
-        momentum = 0.1 if self.momentum is None else self.momentum
-        fused = getattr(x, '_bn_sums', None) if training else None
-        if training:
+            fused = getattr(x, '_bn_sums', None)
             _conv.FUSION['bn_stats_fused' if fused is not None else 'bn_stats_own'] += 1
-        return BatchNormActFunction.apply(x, res, self.weight, self.bias,
-                                          self.running_mean if self.track_running_stats else None,
-                                          self.running_var if self.track_running_stats else None,
-                                          training, momentum, self.eps, relu, fused, link if training else None)
+        return training, fused
+
+    def _momentum(self):
+        return 0.1 if self.momentum is None else self.momentum
+
+    def _running(self):
+        return (self.running_mean, self.running_var) if self.track_running_stats else (None, None)
+
+    def forward(self, x, res=None, relu=False, link=None):
+        training, fused = self._prologue(x)
+        return BatchNormActFunction.apply(x, res, self.weight, self.bias, *self._running(), training, self._momentum(), self.eps, relu,
+                                          fused, link if training else None)
+
+    def forward_padded(self, x, d, relu=False, res=None, padded=None):
+        """BatchNorm2d on a tensor that carries d extra, exactly-zero channels behind this module's num_features (resnet.Bottleneck.
+        _forward_padded): gamma / beta are padded with zeros, so the extra channels come out as zeros again; the running statistics
+        live in padded storage of which `running_mean` / `running_var` are views (state_dict keeps the reference's shapes)."""
+        C = self.num_features
+        training, fused = self._prologue(x)
+        rm = rv = None
+        if self.track_running_stats:
+            pad = getattr(self, '_stat_pad', None)
+            if pad is None or pad[0].shape[0] != C + d or pad[0].device != x.device or self.running_mean.data_ptr() != pad[0].data_ptr():
+                rm, rv = torch.zeros(C + d, device=x.device), torch.ones(C + d, device=x.device)
+                rm[:C].copy_(self.running_mean); rv[:C].copy_(self.running_var)
+                self._stat_pad = (rm, rv)
+                self._buffers['running_mean'], self._buffers['running_var'] = rm[:C], rv[:C]        # views: updated in place by the kernel
+            rm, rv = self._stat_pad
+        gamma, beta = padded if padded is not None else (F.pad(self.weight, (0, d)), F.pad(self.bias, (0, d)))     # (padded: the caller's glue.pad_multi copies)
+        return BatchNormActFunction.apply(x, res, gamma, beta, rm, rv, training, self._momentum(), self.eps, relu, fused, None)
 
 
-def _bn_forward_padded(self, x, d, relu=False, res=None, padded=None):
-    """BatchNorm2d on a tensor that carries d extra, exactly-zero channels behind this module's num_features (resnet.Bottleneck.
-    _forward_padded): gamma / beta are padded with zeros, so the extra channels come out as zeros again; the running statistics
-    live in padded storage of which `running_mean` / `running_var` are views (state_dict keeps the reference's shapes)."""
-    C = self.num_features
-    training = self.training or not self.track_running_stats
-    if training:
-        self._count()
-    rm = rv = None
-    if self.track_running_stats:
-        pad = getattr(self, '_stat_pad', None)
-        if pad is None or pad[0].shape[0] != C + d or pad[0].device != x.device or self.running_mean.data_ptr() != pad[0].data_ptr():
-            rm, rv = torch.zeros(C + d, device=x.device), torch.ones(C + d, device=x.device)
-            rm[:C].copy_(self.running_mean); rv[:C].copy_(self.running_var)
-            self._stat_pad = (rm, rv)
-            self._buffers['running_mean'], self._buffers['running_var'] = rm[:C], rv[:C]        # views: updated in place by the kernel
-        rm, rv = self._stat_pad
-    momentum = 0.1 if self.momentum is None else self.momentum
-    fused = getattr(x, '_bn_sums', None) if training else None
-    if training:
-        _conv.FUSION['bn_stats_fused' if fused is not None else 'bn_stats_own'] += 1
-    gamma, beta = padded if padded is not None else (F.pad(self.weight, (0, d)), F.pad(self.bias, (0, d)))     # (padded: the caller's glue.pad_multi copies)
-    return BatchNormActFunction.apply(x, res, gamma, beta, rm, rv, training, momentum, self.eps, relu, fused, None)
-
-
-BatchNorm2d.forward_padded = _bn_forward_padded
+def _shared_launch(bns, max_n):
+    """These modules can share one multi launch -> (momentum, eps), else None: 1 .. max_n training-mode affine BatchNorm2d of at most
+    1024 channels that agree on momentum and eps (the kernels take one of each per launch)."""
+    if not (1 <= len(bns) <= max_n and all(b.training and b.affine and b.num_features <= 1024 for b in bns)):
+        return None
+    mom, eps = {b._momentum() for b in bns}, {b.eps for b in bns}
+    return (mom.pop(), eps.pop()) if len(mom) == 1 and len(eps) == 1 else None
 
 
 class MultiBatchNormFunction(torch.autograd.Function):
@@ -419,39 +462,24 @@ class MultiBatchNormFunction(torch.autograd.Function):
         ress = [None if t is None else nhwc_as(t, dt) for t in tensors[n:2 * n]]
         gammas = [t.detach().float().contiguous() for t in tensors[2 * n:3 * n]]
         betas = [t.detach().float().contiguous() for t in tensors[3 * n:4 * n]]
-        jobs = (_lib.BnFwdJob * n)()
-        ys, saveds, keep, masks = [], [], [], []
         if done is not None:
             # nothing to launch: conv -> BatchNorm ran as one call (conv.MultiConvFunction.forward); same outputs, same saved tensors
             ys, saveds, masks = [d[0] for d in done], [d[1] for d in done], [d[2] for d in done]
             _conv.FUSION['bn_forward_in_conv_launch'] += n
-        for i in range(n if done is None else 0):
-            B, C, H, W = xs[i].shape
-            if ress[i] is not None and ress[i].shape != xs[i].shape:
-                raise ValueError('residual shape %s != %s' % (tuple(ress[i].shape), tuple(xs[i].shape)))
-            y = _empty_nhwc(B, C, H, W, dt, xs[i].device)
-            saved = torch.empty(2, C, dtype=torch.float32, device=xs[i].device)
-            sums, state = fused[i], 2
-            if sums is None:
-                sums, state = ARENA.zeros(L.danet_bn_ws_floats(C), xs[i].device), 1
-            keep.append(sums)
-            mask = torch.empty(B * H * W * C // 4, dtype=torch.uint8, device=xs[i].device) \
-                if (relus[i] and RELU_MASK and (ress[i] is not None or _conv.FUSE_BN_BWD_REDUCE)) else None
-            masks.append(mask)
-            j = jobs[i]
-            j.mask = None if mask is None else mask.data_ptr()
-            j.x, j.res, j.y = xs[i].data_ptr(), None if ress[i] is None else ress[i].data_ptr(), y.data_ptr()
-            j.gamma, j.beta = gammas[i].data_ptr(), betas[i].data_ptr()
-            j.running_mean = None if rms[i] is None else rms[i].data_ptr()
-            j.running_var = None if rvs[i] is None else rvs[i].data_ptr()
-            j.saved, j.sums = saved.data_ptr(), sums.data_ptr()
-            j.M, j.C, j.sums_state, j.relu = B * H * W, C, state, int(relus[i])
-            ys.append(y)
-            saveds.append(saved)
-        if done is None:
+        else:
+            jobs = (_lib.BnFwdJob * n)()
+            ys, saveds, masks, keep = [], [], [], []
+            for i in range(n):
+                y, saved, mask = _bn_fwd_outputs(xs[i], ress[i], True, relus[i])
+                sums, state = fused[i], 2
+                if sums is None:
+                    sums, state = ARENA.zeros(L.danet_bn_ws_floats(xs[i].shape[1]), xs[i].device), 1
+                _bn_fwd_job(jobs[i], xs[i], ress[i], y, gammas[i], betas[i], rms[i], rvs[i], saved, sums, state, mask, relus[i])
+                ys.append(y); saveds.append(saved); masks.append(mask); keep.append(sums)
             check(_k(L, 'danet_bn_forward_multi', dt)(ctypes.addressof(jobs), n, float(momentum), float(eps), stream()), 'danet_bn_forward_multi')
-        modes = [((2 if r is None else (1 if m is not None else 0)) if RELU_MASK else 0) if rl else 0 for m, r, rl in zip(masks, ress, relus)]
-        ctx.save_for_backward(*xs, *[y if (rl and md == 0) else None for y, md, rl in zip(ys, modes, relus)], *gammas, *saveds, *betas, *masks)
+        gates = [_bn_relu_gate(True, rl, r is not None) for rl, r in zip(relus, ress)]
+        modes = [g[1] for g in gates]
+        ctx.save_for_backward(*xs, *[y if g[2] else None for y, g in zip(ys, gates)], *gammas, *saveds, *betas, *masks)
         ctx.cfg = (n, relus, [r is not None for r in ress], links, modes)
         for y, x, saved, mask, md, rl in zip(ys, xs, saveds, masks, modes, relus):
             y._bn_ctx = _conv.BnCtx(x, bool(rl), saved, mask, md)
@@ -478,15 +506,8 @@ class MultiBatchNormFunction(torch.autograd.Function):
             dres = _empty_nhwc(B, C, H, W, dt, xs[i].device) if has_res[i] else None
             dparam = torch.empty(2, C, dtype=torch.float32, device=xs[i].device)
             keep += [red, gy]
-            j = jobs[i]
-            j.dy, j.x, j.y = gy.data_ptr(), xs[i].data_ptr(), None if ys[i] is None else ys[i].data_ptr()
-            j.beta, j.mask, j.mask_mode = betas[i].data_ptr(), None if masks[i] is None else masks[i].data_ptr(), modes[i]
-            j.gamma, j.saved = gammas[i].data_ptr(), saveds[i].data_ptr()
-            j.dx, j.dres, j.dparam, j.red = dx.data_ptr(), None if dres is None else dres.data_ptr(), dparam.data_ptr(), red.data_ptr()
-            j.M, j.C, j.red_state, j.relu = B * H * W, C, state, int(relus[i])
-            dxs.append(dx)
-            dress.append(dres)
-            dparams.append(dparam)
+            _bn_bwd_job(jobs[i], gy, xs[i], ys[i], gammas[i], betas[i], saveds[i], masks[i], modes[i], dx, dres, dparam, red, state, relus[i])
+            dxs.append(dx); dress.append(dres); dparams.append(dparam)
         bar = _onepass_bar(xs[0].device) if (dt == torch.bfloat16 and all(jobs[i].red_state == 1 for i in range(n))) else None
         budget = onepass_budget(xs[0].device)
         if bar is not None and L.danet_bn_backward_onepass_ok(ctypes.addressof(jobs), n, budget):
@@ -510,10 +531,6 @@ class MultiBatchNormFunction(torch.autograd.Function):
 CONV_BN = bool(int(os.environ.get('DANET_CONV_BN', '0')))
 
 
-def _bn_mask_wanted(relu, has_res):
-    return bool(relu and RELU_MASK and (has_res or _conv.FUSE_BN_BWD_REDUCE))
-
-
 def multi_conv_bn(convs, xs, bns, ress=None, relu=False, conv_links=None, bn_links=None):
     """multi_batch_norm(bns, multi_conv(convs, xs), ress, relu) -- conv -> bn -> [+ residual] -> [relu] of the lockstep branch layers
     (/root/reference/models/module/res_module.py:39-56, hr_module.py:155-177) -- with the BatchNorm applied by the convolutions'
@@ -524,9 +541,9 @@ def multi_conv_bn(convs, xs, bns, ress=None, relu=False, conv_links=None, bn_lin
     rs = list(ress) if ress is not None else [None] * n
     spec = None
     dev = xs[0].device
-    if (CONV_BN and 1 <= n <= 4 and xs[0].is_cuda and _conv.PRECISION != 'fp32' and _conv.FUSE_BN_STATS and torch.is_grad_enabled() and
-            all(b.training and b.affine and b.num_features <= 1024 for b in bns) and
-            len({0.1 if b.momentum is None else b.momentum for b in bns}) == 1 and len({b.eps for b in bns}) == 1):
+    me = _shared_launch(bns, 4) if (CONV_BN and xs[0].is_cuda and _conv.PRECISION != 'fp32' and _conv.FUSE_BN_STATS and
+                                    torch.is_grad_enabled()) else None
+    if me is not None:
         bar = _onepass_bar(dev)
         # the launch crosses a grid barrier with up to `c3s_blocks` workgroups (512): under a data-parallel trainer's co-residency
         # budget (ONEPASS_MAX_BLOCKS = 2 x the compute units left beside the communication kernels) a grid that large may not be
@@ -534,11 +551,11 @@ def multi_conv_bn(convs, xs, bns, ress=None, relu=False, conv_links=None, bn_lin
         if bar is not None and 0 < onepass_budget(dev) < _lib.lib().knob('c3s_blocks'):
             bar = None
         if bar is not None:
-            spec = {'bar': bar, 'momentum': 0.1 if bns[0].momentum is None else bns[0].momentum, 'eps': bns[0].eps,
+            # (whether a job writes a ReLU byte mask is decided where its outputs are allocated: _bn_fwd_outputs)
+            spec = {'bar': bar, 'momentum': me[0], 'eps': me[1],
                     'jobs': [{'res': r, 'gamma': b.weight.detach().float().contiguous(), 'beta': b.bias.detach().float().contiguous(),
-                              'running_mean': b.running_mean if b.track_running_stats else None,
-                              'running_var': b.running_var if b.track_running_stats else None,
-                              'relu': rl, 'want_mask': _bn_mask_wanted(rl, r is not None)} for b, r, rl in zip(bns, rs, relus)]}
+                              'running_mean': b._running()[0], 'running_var': b._running()[1], 'relu': rl}
+                             for b, r, rl in zip(bns, rs, relus)]}
     h = _conv.multi_conv(convs, xs, conv_links, bn=spec)
     return multi_batch_norm(bns, h, ress, relu=relu, links=bn_links)
 
@@ -549,28 +566,53 @@ def multi_batch_norm(bns, xs, ress=None, relu=False, links=None):
     n = len(bns)
     ress = list(ress) if ress is not None else [None] * n
     relus = [bool(r) for r in relu] if isinstance(relu, (list, tuple)) else [bool(relu)] * n      # one flag per BatchNorm, or one for all
-    ok = 1 <= n <= 12 and all(b.training and b.affine and b.num_features <= 1024 for b in bns) and xs[0].is_cuda
     lks = list(links) if links is not None else [None] * n
-    if not ok:
+    me = _shared_launch(bns, 12)
+    if me is None or not xs[0].is_cuda:
         return [b(x, r, rl, link=lk) for b, x, r, rl, lk in zip(bns, xs, ress, relus, lks)]
-    mom = {0.1 if b.momentum is None else b.momentum for b in bns}
-    eps = {b.eps for b in bns}
-    if len(mom) != 1 or len(eps) != 1:
-        return [b(x, r, rl, link=lk) for b, x, r, rl, lk in zip(bns, xs, ress, relus, lks)]
-    for b in bns:
-        b._count()
-    rms = [b.running_mean if b.track_running_stats else None for b in bns]
-    rvs = [b.running_var if b.track_running_stats else None for b in bns]
-    fused = [getattr(x, '_bn_sums', None) for x in xs]
-    for f in fused:
-        _conv.FUSION['bn_stats_fused' if f is not None else 'bn_stats_own'] += 1
+    fused = [b._prologue(x)[1] for b, x in zip(bns, xs)]
+    rms, rvs = zip(*[b._running() for b in bns])
     done = [getattr(x, '_bn_done', None) for x in xs]
     done = done if all(d is not None for d in done) else None
-    static = (n, relus, mom.pop(), eps.pop(), rms, rvs, fused, links, done)
+    static = (n, relus, me[0], me[1], rms, rvs, fused, links, done)
     return list(MultiBatchNormFunction.apply(static, *xs, *ress, *[b.weight for b in bns], *[b.bias for b in bns]))
 
 
 SUM_BWD_ALL = bool(int(os.environ.get('DANET_SUM_BWD_ALL', '1')))
+
+
+def _sum_output(terms, shifts, name):
+    """The (uninitialised) output of sum_t nearest_upsample_{2^shift_t}(term_t); every term must match its shape."""
+    B, C = terms[0].shape[0], terms[0].shape[1]
+    H = max(t.shape[2] << s for t, s in zip(terms, shifts))
+    W = max(t.shape[3] << s for t, s in zip(terms, shifts))
+    for t, s in zip(terms, shifts):
+        if t.shape[1] != C or (t.shape[2] << s) != H or (t.shape[3] << s) != W:
+            raise ValueError('%s: term %s with shift %d does not match output %dx%dx%d' % (name, tuple(t.shape), s, C, H, W))
+    return _empty_nhwc(B, C, H, W, terms[0].dtype, terms[0].device)
+
+
+def _sum_fwd_job(j, terms, shifts, relu, y):
+    for q, (t, s) in enumerate(zip(terms, shifts)):
+        j.terms[q] = t.data_ptr()
+        j.shifts[q] = int(s)
+    B, C, H, W = y.shape
+    j.nterms, j.B, j.H, j.W, j.C, j.relu, j.y = len(terms), B, H, W, C, int(relu), y.data_ptr()
+
+
+def _sum_terms(terms, shifts, relu, name):
+    """y = [relu](sum of the shifted terms) as one launch of its own (terms NHWC, of one dtype)."""
+    n = len(terms)
+    y = _sum_output(terms, shifts, name)
+    B, C, H, W = y.shape
+    check(_k(_lib.lib(), 'danet_sum_relu_forward', y.dtype)((ctypes.c_void_p * n)(*[nptr(t) for t in terms]), (ctypes.c_int * n)(*shifts),
+                                                         n, B, H, W, C, int(relu), nptr(y), stream()), 'danet_sum_relu_forward')
+    return y
+
+
+def _shift_grads(shifts, B, C, H, W, dt, device):
+    """{shift: the gradient buffer of the terms that enter a B x C x H x W fuse sum at that shift}."""
+    return {s: _empty_nhwc(B, C, H >> s, W >> s, dt, device) for s in shifts}
 
 
 class SumReluFunction(torch.autograd.Function):
@@ -578,23 +620,10 @@ class SumReluFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, relu, shifts, *terms):
-        L = _lib.lib()
         terms = [nhwc_act(t) for t in terms]
-        dt = terms[0].dtype
-        n = len(terms)
-        B, C = terms[0].shape[0], terms[0].shape[1]
-        H = max(t.shape[2] << s for t, s in zip(terms, shifts))
-        W = max(t.shape[3] << s for t, s in zip(terms, shifts))
-        for t, s in zip(terms, shifts):
-            if t.shape[1] != C or (t.shape[2] << s) != H or (t.shape[3] << s) != W:
-                raise ValueError('sum_relu: term %s with shift %d does not match output %dx%dx%d' % (tuple(t.shape), s, C, H, W))
-        y = _empty_nhwc(B, C, H, W, dt, terms[0].device)
-        ptrs = (ctypes.c_void_p * n)(*[ptr(t.permute(0, 2, 3, 1)) for t in terms])
-        sh = (ctypes.c_int * n)(*shifts)
-        check(_k(L, 'danet_sum_relu_forward', dt)(ptrs, sh, n, B, H, W, C, int(relu), ptr(y.permute(0, 2, 3, 1)), stream()),
-              'danet_sum_relu_forward')
+        y = _sum_terms(terms, shifts, relu, 'sum_relu')
         ctx.save_for_backward(y if relu else None)
-        ctx.cfg = (relu, tuple(shifts), B, C, H, W, dt)
+        ctx.cfg = (relu, tuple(shifts), *y.shape, y.dtype)
         return y
 
     @staticmethod
@@ -608,22 +637,18 @@ class SumReluFunction(torch.autograd.Function):
         need = sorted({s for i, s in enumerate(shifts) if ctx.needs_input_grad[2 + i]})
         if SUM_BWD_ALL and len(need) > 1 and need[-1] <= 3:
             # every shift in one launch: gy and y are read once (csrc/norm_act.hip sum_relu_bwd_all_kernel)
-            for s in need:
-                cache[s] = _empty_nhwc(B, C, H >> s, W >> s, dt, gy.device)
-            dp = [None if s not in cache else ptr(cache[s].permute(0, 2, 3, 1)) for s in range(4)]
-            check(_k(L, 'danet_sum_relu_backward_all', dt)(ptr(gy.permute(0, 2, 3, 1)), None if y is None else ptr(y.permute(0, 2, 3, 1)),
-                                                B, H, W, C, int(relu), dp[0], dp[1], dp[2], dp[3], stream()),
+            cache = _shift_grads(need, B, C, H, W, dt, gy.device)
+            dp = [nptr(cache.get(s)) for s in range(4)]
+            check(_k(L, 'danet_sum_relu_backward_all', dt)(nptr(gy), nptr(y), B, H, W, C, int(relu), dp[0], dp[1], dp[2], dp[3], stream()),
                   'danet_sum_relu_backward_all')
         for i, s in enumerate(shifts):
             if not ctx.needs_input_grad[2 + i]:
                 outs.append(None)
                 continue
             if s not in cache:
-                d = _empty_nhwc(B, C, H >> s, W >> s, dt, gy.device)
-                check(_k(L, 'danet_sum_relu_backward', dt)(ptr(gy.permute(0, 2, 3, 1)), None if y is None else ptr(y.permute(0, 2, 3, 1)),
-                                                B, H, W, C, s, int(relu), ptr(d.permute(0, 2, 3, 1)), stream()),
+                cache.update(_shift_grads([s], B, C, H, W, dt, gy.device))
+                check(_k(L, 'danet_sum_relu_backward', dt)(nptr(gy), nptr(y), B, H, W, C, s, int(relu), nptr(cache[s]), stream()),
                       'danet_sum_relu_backward')
-                cache[s] = d
             outs.append(cache[s])
         return (None, None) + tuple(outs)
 
@@ -644,20 +669,10 @@ class SumReluMultiFunction(torch.autograd.Function):
         for i, (shifts, nt) in enumerate(meta):
             ts = terms[k:k + nt]
             k += nt
-            B, C = ts[0].shape[0], ts[0].shape[1]
-            H = max(t.shape[2] << s for t, s in zip(ts, shifts))
-            W = max(t.shape[3] << s for t, s in zip(ts, shifts))
-            for t, s in zip(ts, shifts):
-                if t.shape[1] != C or (t.shape[2] << s) != H or (t.shape[3] << s) != W:
-                    raise ValueError('sum_relu_multi: term %s with shift %d does not match output %dx%dx%d' % (tuple(t.shape), s, C, H, W))
-            y = _empty_nhwc(B, C, H, W, dt, ts[0].device)
-            j = jobs[i]
-            for q, (t, s) in enumerate(zip(ts, shifts)):
-                j.terms[q] = t.data_ptr()
-                j.shifts[q] = int(s)
-            j.nterms, j.B, j.H, j.W, j.C, j.relu, j.y = nt, B, H, W, C, int(relu), y.data_ptr()
+            y = _sum_output(ts, shifts, 'sum_relu_multi')
+            _sum_fwd_job(jobs[i], ts, shifts, relu, y)
             ys.append(y)
-            cfg.append((tuple(shifts), B, C, H, W))
+            cfg.append((tuple(shifts), *y.shape))
         check(_k(L, 'danet_sum_relu_forward_multi', dt)(ctypes.addressof(jobs), n, stream()), 'danet_sum_relu_forward_multi')
         ctx.save_for_backward(*(ys if relu else []))
         ctx.cfg = (relu, cfg, dt)
@@ -678,13 +693,13 @@ class SumReluMultiFunction(torch.autograd.Function):
                 per_out.append(None)
                 continue
             gy = nhwc_as(gys[i], dt)
-            cache = {s: _empty_nhwc(B, C, H >> s, W >> s, dt, gy.device) for s in sorted(set(shifts))}
+            cache = _shift_grads(sorted(set(shifts)), B, C, H, W, dt, gy.device)
             j = jobs[nj]
             nj += 1
-            j.gy, j.y = gy.data_ptr(), None if ys[i] is None else ys[i].data_ptr()
+            j.gy, j.y = gy.data_ptr(), _dp(ys[i])
             j.B, j.H, j.W, j.C, j.relu = B, H, W, C, int(relu)
             for s in range(4):
-                j.d[s] = cache[s].data_ptr() if s in cache else None
+                j.d[s] = _dp(cache.get(s))
             keep.append(gy)
             per_out.append(cache)
         if nj:
@@ -732,16 +747,8 @@ class FanOutFunction(torch.autograd.Function):
             if len(grp) == 1:
                 total = grp[0]
                 continue
-            L = _lib.lib()
             dt = torch.float32 if grp[0].dtype == torch.float32 else torch.bfloat16
-            terms = [nhwc_as(t, dt) for t in grp]
-            B, C, H, W = terms[0].shape
-            y = _empty_nhwc(B, C, H, W, dt, terms[0].device)
-            ptrs = (ctypes.c_void_p * len(terms))(*[ptr(t.permute(0, 2, 3, 1)) for t in terms])
-            sh = (ctypes.c_int * len(terms))(*([0] * len(terms)))
-            check(_k(L, 'danet_sum_relu_forward', dt)(ptrs, sh, len(terms), B, H, W, C, 0, ptr(y.permute(0, 2, 3, 1)), stream()),
-                  'danet_sum_relu_forward')
-            total = y
+            total = _sum_terms([nhwc_as(t, dt) for t in grp], [0] * len(grp), False, 'fan_out')
         return total, None
 
 
@@ -776,14 +783,9 @@ class FanOutMultiFunction(torch.autograd.Function):
                 continue
             dt0 = dt
             terms = [nhwc_as(t, dt) for t in grp]
-            B, C, H, W = terms[0].shape
-            y = _empty_nhwc(B, C, H, W, dt, terms[0].device)
-            j = jobs[nj]
+            y = _sum_output(terms, [0] * len(terms), 'fan_out_multi')
+            _sum_fwd_job(jobs[nj], terms, [0] * len(terms), False, y)
             nj += 1
-            for q, t in enumerate(terms):
-                j.terms[q] = t.data_ptr()
-                j.shifts[q] = 0
-            j.nterms, j.B, j.H, j.W, j.C, j.relu, j.y = len(terms), B, H, W, C, 0, y.data_ptr()
             keep.append(terms)
             outs[i] = y
         if nj:
@@ -843,8 +845,8 @@ class StnGatherFunction(torch.autograd.Function):
         P = th.shape[1]
         OH, OW = out_hw
         y = _empty_nhwc(B, P * C, OH, OW, dt, x.device)
-        check(_k(L, 'danet_stn_gather_forward', dt)(ptr(x.permute(0, 2, 3, 1)), ptr(th), B, H, W, C, P, OH, OW, int(align_corners),
-                                         ptr(y.permute(0, 2, 3, 1)), stream()), 'danet_stn_gather_forward')
+        check(_k(L, 'danet_stn_gather_forward', dt)(nptr(x), ptr(th), B, H, W, C, P, OH, OW, int(align_corners), nptr(y), stream()),
+              'danet_stn_gather_forward')
         ctx.save_for_backward(th)
         ctx.cfg = (B, C, H, W, P, OH, OW, int(align_corners), dt)
         return y
@@ -856,8 +858,7 @@ class StnGatherFunction(torch.autograd.Function):
         B, C, H, W, P, OH, OW, align, dt = ctx.cfg
         gy = nhwc_as(gy, dt)
         dx = _empty_nhwc(B, C, H, W, dt, gy.device)
-        check(_k(L, 'danet_stn_gather_backward', dt)(ptr(gy.permute(0, 2, 3, 1)), ptr(th), B, H, W, C, P, OH, OW, align,
-                                          ptr(dx.permute(0, 2, 3, 1)), stream()), 'danet_stn_gather_backward')
+        check(_k(L, 'danet_stn_gather_backward', dt)(nptr(gy), ptr(th), B, H, W, C, P, OH, OW, align, nptr(dx), stream()), 'danet_stn_gather_backward')
         return dx, None, None, None
 
 
@@ -879,8 +880,7 @@ class MaxPool3x3S2Function(torch.autograd.Function):
         OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = _empty_nhwc(B, C, OH, OW, dt, x.device)
         idx = torch.empty(B * OH * OW * C, dtype=torch.uint8, device=x.device)
-        check(_k(L, 'danet_maxpool3x3s2_forward', dt)(ptr(x.permute(0, 2, 3, 1)), ptr(y.permute(0, 2, 3, 1)), ptr(idx), B, H, W, C, stream()),
-              'danet_maxpool3x3s2_forward')
+        check(_k(L, 'danet_maxpool3x3s2_forward', dt)(nptr(x), nptr(y), ptr(idx), B, H, W, C, stream()), 'danet_maxpool3x3s2_forward')
         ctx.save_for_backward(idx)
         ctx.cfg = (B, C, H, W, dt)
         return y
@@ -892,8 +892,7 @@ class MaxPool3x3S2Function(torch.autograd.Function):
         B, C, H, W, dt = ctx.cfg
         gy = nhwc_as(gy, dt)
         dx = _empty_nhwc(B, C, H, W, dt, gy.device)
-        check(_k(L, 'danet_maxpool3x3s2_backward', dt)(ptr(gy.permute(0, 2, 3, 1)), ptr(idx), ptr(dx.permute(0, 2, 3, 1)), B, H, W, C, stream()),
-              'danet_maxpool3x3s2_backward')
+        check(_k(L, 'danet_maxpool3x3s2_backward', dt)(nptr(gy), ptr(idx), nptr(dx), B, H, W, C, stream()), 'danet_maxpool3x3s2_backward')
         return dx
 
 

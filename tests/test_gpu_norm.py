@@ -56,6 +56,50 @@ def test_bn_train_forward_backward(C, H, B, relu, use_res):
     _close(ye, yre, 1e-2, 'eval')
 
 
+@pytest.mark.parametrize('C', [64, 12])
+def test_bn_without_relu_backward_gate_mode_zero(C):
+    """Without ReLU the single path hands the backward kernels mask_mode 0 (nn._bn_relu_gate; it used to say 2, which no kernel read):
+    training-mode BatchNorm2d, relu=False, no residual, on the default stream -- the one-pass backward and, with nn.ONEPASS off, the
+    two-kernel backward -- against torch's batch_norm in fp32 on the same bf16-rounded input, within the bounds of
+    test_bn_train_forward_backward."""
+    from danet_densepose2smpl_amd import nn as dnn, conv as dconv
+    B, H = 2, 16
+    g = torch.Generator().manual_seed(C + H)
+    x = (torch.randn(B, C, H, H, generator=g) * 1.5 + 0.3).bfloat16().float().cuda()
+    gy = torch.randn(B, C, H, H, generator=g).bfloat16().float().cuda()
+    wgt, bia = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1
+    ref = torch.nn.BatchNorm2d(C, momentum=0.1).cuda()
+    with torch.no_grad():
+        ref.weight.copy_(wgt); ref.bias.copy_(bia)
+    xr = x.clone().requires_grad_(True)
+    yr = ref(xr)
+    yr.backward(gy)
+    was = dnn.ONEPASS
+    dnn.ONEPASS_STREAM = None          # (a Trainer of an earlier test confines the one-pass launches to its own stream)
+    try:
+        for onepass in (True, False):
+            dnn.ONEPASS = onepass
+            bn = dnn.BatchNorm2d(C, momentum=0.1).cuda()
+            with torch.no_grad():
+                bn.weight.copy_(wgt); bn.bias.copy_(bia)
+            xt = x.clone().requires_grad_(True)
+            launches = dconv.FUSION['bn_bwd_onepass']
+            y = bn(xt, relu=False)
+            assert y._bn_ctx.mask_mode == 0 and y._bn_ctx.mask is None
+            y.backward(gy.bfloat16())
+            assert dconv.FUSION['bn_bwd_onepass'] - launches == int(onepass)
+            what = ' (one-pass)' if onepass else ' (two kernels)'
+            _close(y, yr, 1e-2, 'y' + what)
+            _close(xt.grad, xr.grad, 3e-2, 'dx' + what)
+            _close(bn.weight.grad, ref.weight.grad, 2e-2, 'dgamma' + what)
+            _close(bn.bias.grad, ref.bias.grad, 2e-2, 'dbeta' + what)
+            _close(bn.running_mean, ref.running_mean, 1e-3, 'running_mean' + what)
+            _close(bn.running_var, ref.running_var, 1e-3, 'running_var' + what)
+    finally:
+        dnn.ONEPASS = was
+    assert not dnn.onepass_error()
+
+
 def test_sum_relu_multi_equals_the_per_output_launches():
     """nn.sum_relu_multi (round 5): the four fuse sums of a 4-branch HighResolutionModule -- shifts (0,1,2,3), (0,0,1,2), (0,0,0,1),
     (0,0,0,0), several terms of an output sharing a shift -- in ONE launch forward and ONE backward: outputs and every term's gradient

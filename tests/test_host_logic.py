@@ -461,3 +461,58 @@ def test_channel_padding_rule_is_one_function():
         assert tuple(got) == want and isinstance(got[1], bool), (args, got, want)
     src = inspect.getsource(inference._FoldedConv._widths)
     assert 'channel_padding(' in src and '% 8' not in src, src
+
+
+def test_bn_relu_gate_rule_table():
+    """nn._bn_relu_gate(training, relu, has_res) under every setting of nn.RELU_MASK and conv.FUSE_BN_BWD_REDUCE -> (want_mask,
+    mask_mode, save_y).  The rows are written out from the expressions the single and the multi BatchNorm path each carried before the
+    rule became one function: mask = training and relu and RELU_MASK and (has_res or FUSE_BN_BWD_REDUCE); mode = (2 if not has_res else
+    (1 if mask else 0)) if RELU_MASK else 0, and 0 without ReLU; save_y = relu and mode == 0."""
+    from danet_densepose2smpl_amd import nn as dnn, conv as dconv
+    T, F = True, False
+    #         training relu has_res RELU_MASK FUSE_BN_BWD_REDUCE
+    table = {(T, T, F, T, T): (T, 2, F),       # gate recomputed from x; the mask only serves the consumer conv's fused reduction
+             (T, T, F, T, F): (F, 2, F),       # ... which is off: no mask at all
+             (T, T, T, T, T): (T, 1, F),       # a residual: the gate cannot be recomputed from x, the backward reads the byte mask
+             (T, T, T, T, F): (T, 1, F),
+             (T, T, F, F, T): (F, 0, T),       # RELU_MASK off: the backward gates on the saved output
+             (T, T, F, F, F): (F, 0, T),
+             (T, T, T, F, T): (F, 0, T),
+             (T, T, T, F, F): (F, 0, T),
+             # no ReLU: there is no gate.  Mode 0 (the single path used to say 2 without a residual under RELU_MASK): no kernel and
+             # not conv._bn_gate reads the mode unless `relu` is set, so the value is free and the multi path's spelling is kept
+             (T, F, F, T, T): (F, 0, F),
+             (T, F, F, T, F): (F, 0, F),
+             (T, F, T, T, T): (F, 0, F),
+             (T, F, T, T, F): (F, 0, F),
+             (T, F, F, F, T): (F, 0, F),
+             (T, F, F, F, F): (F, 0, F),
+             (T, F, T, F, T): (F, 0, F),
+             (T, F, T, F, F): (F, 0, F),
+             # eval mode: the forward writes no mask (`training and ...`), saves nothing and has no backward -- mode and save_y were
+             # never evaluated there; the rule pins them to 0 / False
+             (F, T, F, T, T): (F, 0, F),
+             (F, T, F, T, F): (F, 0, F),
+             (F, T, T, T, T): (F, 0, F),
+             (F, T, T, T, F): (F, 0, F),
+             (F, T, F, F, T): (F, 0, F),
+             (F, T, F, F, F): (F, 0, F),
+             (F, T, T, F, T): (F, 0, F),
+             (F, T, T, F, F): (F, 0, F),
+             (F, F, F, T, T): (F, 0, F),       # (eval and no ReLU: mode 0 for both reasons)
+             (F, F, F, T, F): (F, 0, F),
+             (F, F, T, T, T): (F, 0, F),
+             (F, F, T, T, F): (F, 0, F),
+             (F, F, F, F, T): (F, 0, F),
+             (F, F, F, F, F): (F, 0, F),
+             (F, F, T, F, T): (F, 0, F),
+             (F, F, T, F, F): (F, 0, F)}
+    assert len(table) == 32
+    was = dnn.RELU_MASK, dconv.FUSE_BN_BWD_REDUCE
+    try:
+        for (training, relu, has_res, rmask, fuse), want in table.items():
+            dnn.RELU_MASK, dconv.FUSE_BN_BWD_REDUCE = rmask, fuse          # read at call time, not at import
+            got = dnn._bn_relu_gate(training, relu, has_res)
+            assert tuple(got) == want and all(type(a) is type(b) for a, b in zip(got, want)), ((training, relu, has_res, rmask, fuse), got, want)
+    finally:
+        dnn.RELU_MASK, dconv.FUSE_BN_BWD_REDUCE = was
