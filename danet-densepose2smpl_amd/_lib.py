@@ -165,6 +165,11 @@ _SIGNATURES = {
     'danet_scene_render': (c_i, [c_f, c_f, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, ctypes.c_int64, c_f, c_f, c_i,
                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
                                  c_f, c_f, c_f, c_f, c_sz, c_f]),
+    'danet_texture_map': (c_i, [c_f, c_i, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f]),
+    'danet_texture_unwrap': (c_i, [c_f] * 4 + [c_i] * 3 + [c_f, ctypes.POINTER(ctypes.c_int32), c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_i,
+                                   c_fl, c_fl, c_fl, c_f, c_f]),
+    'danet_texture_render': (c_i, [c_f, c_f, c_i, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_f,
+                                   ctypes.POINTER(ctypes.c_int32), c_f, c_fl, c_i, ctypes.POINTER(c_fl), c_f, c_f, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations

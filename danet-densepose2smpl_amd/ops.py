@@ -611,3 +611,127 @@ def scene_render(verts, vcol, faces2, cam_t, proj, dscale, person_frame, src, of
                                ho.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), hs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                ptr(out), ptr(ids), ptr(depth), ptr(ws), nws, stream()), 'danet_scene_render')
     return (out, ids, depth) if return_aux else out
+
+
+# ---- texture atlases (csrc/texture_ops.hip; DESIGN.md "texture rule") ----------------------------------------------------------
+_TEXTURE_INTS = {}
+
+
+def _texture_ints(host, device):
+    """A small host int32 array on `device`, uploaded once per value (an upload cannot be captured under torch.cuda.graph) and kept
+    for the life of the process: a captured graph holds its address."""
+    key = (str(device), host.tobytes())
+    if key not in _TEXTURE_INTS:
+        _TEXTURE_INTS[key] = torch.from_numpy(host.copy()).to(device)
+    return _TEXTURE_INTS[key]
+
+
+def texture_view_offsets(view_off, N):
+    """The views of person p are view_off[p] .. view_off[p+1] - 1; None: one view per person.  -> host int32 [P+1], checked."""
+    import numpy as np
+    off = np.arange(N + 1, dtype=np.int32) if view_off is None else np.asarray(view_off).reshape(-1)
+    if off.size < 2 or not np.issubdtype(off.dtype, np.integer) or off[0] != 0 or off[-1] != N or (np.diff(off) < 0).any():
+        raise ValueError('texture_unwrap: view_off must be integers, non-decreasing from 0 to N = %d, got %s' % (N, off.tolist()))
+    return np.ascontiguousarray(off, np.int32)
+
+
+def texture_atlas_index(atlas_index, N, P):
+    """Which person's atlas a drawn view uses; None: view n uses atlas n.  -> host int32 [N], checked."""
+    import numpy as np
+    idx = np.arange(N, dtype=np.int32) if atlas_index is None else np.asarray(atlas_index).reshape(-1)
+    if idx.size != N or not np.issubdtype(idx.dtype, np.integer) or (idx < 0).any() or (idx >= P).any():
+        raise ValueError('texture_render: atlas_index must hold %d integers in [0, %d), got %s' % (N, P, idx.tolist()))
+    return np.ascontiguousarray(idx, np.int32)
+
+
+def _texture_size(T):
+    if int(T) != T or int(T) < 2 or int(T) > 4096:
+        raise ValueError('texture: chart size T = %s (an integer in [2, 4096])' % (T,))
+    return int(T)
+
+
+def texture_map(uv, faces, part_off, part_faces, T):
+    """The texel -> surface map of the texture rule, one launch: uv [NDV,2] f32, faces [F,3] int32 over the DensePose vertices,
+    the faces of the 24 parts as a CSR (part_off [25], part_faces [F] int32, ascending within a part) -> (face [24,T,T] int32, -1
+    where no face holds the texel centre; bary [24,T,T,2] f32)."""
+    L = _lib.lib()
+    uv = _dev_tensor(uv, 'texture_map')
+    T = _texture_size(T)
+    NDV, F = uv.shape[0], faces.shape[0]
+    _typed(uv, torch.float32, (NDV, 2), 'texture_map: uv')
+    _typed(faces, torch.int32, (F, 3), 'texture_map: faces')
+    _typed(part_off, torch.int32, (25,), 'texture_map: part_off')
+    _typed(part_faces, torch.int32, (F,), 'texture_map: part_faces')
+    face = torch.empty(24, T, T, device=uv.device, dtype=torch.int32)
+    bary = torch.empty(24, T, T, 2, device=uv.device, dtype=torch.float32)
+    check(L.danet_texture_map(ptr(uv), NDV, ptr(faces), F, ptr(part_off), ptr(part_faces), T, ptr(face), ptr(bary), stream()),
+          'danet_texture_map')
+    return face, bary
+
+
+def texture_unwrap(images, vertices, cam, depth, view_off, vert_mapping, faces, map_face, map_bary, focal, depth_tol=0.02, min_cos=0.1):
+    """Photographs -> atlas [P,24,T,T,4] f32 (r, g, b, summed weight), one launch.  images [N,3,H,H] f32, vertices [N,NV,3], cam
+    [N,3], depth [N,H,H] (iuv_raster's depth plane of `faces` at orig = out_size = H), view_off: HOST integers [P+1] (None: one view
+    per person), vert_mapping [NDV] / faces [F,3] int32, map_face / map_bary: texture_map's."""
+    import ctypes
+    L = _lib.lib()
+    img = _f32c(_dev_tensor(images, 'texture_unwrap'))
+    v, c, d = (_f32c(_dev_tensor(t, 'texture_unwrap')) for t in (vertices, cam, depth))
+    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
+        raise ValueError('texture_unwrap: images %s, expected square [N,3,H,H]' % (tuple(img.shape),))
+    N, H = img.shape[0], img.shape[2]
+    if v.dim() != 3 or v.shape[0] != N or v.shape[2] != 3 or tuple(c.shape) != (N, 3) or tuple(d.shape) != (N, H, H):
+        raise ValueError('texture_unwrap: vertices %s, cam %s, depth %s for %d images of %d pixels'
+                         % (tuple(v.shape), tuple(c.shape), tuple(d.shape), N, H))
+    off = texture_view_offsets(view_off, N)
+    P = off.size - 1
+    T = _texture_size(map_face.shape[-1])
+    NDV, F = vert_mapping.numel(), faces.shape[0]
+    _typed(vert_mapping, torch.int32, (NDV,), 'texture_unwrap: vert_mapping')
+    _typed(faces, torch.int32, (F, 3), 'texture_unwrap: faces')
+    _typed(map_face, torch.int32, (24, T, T), 'texture_unwrap: map_face')
+    _typed(map_bary, torch.float32, (24, T, T, 2), 'texture_unwrap: map_bary')
+    atlas = torch.empty(P, 24, T, T, 4, device=img.device, dtype=torch.float32)
+    check(L.danet_texture_unwrap(ptr(img), ptr(v), ptr(c), ptr(d), N, v.shape[1], H, ptr(_texture_ints(off, img.device)),
+                                 off.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), P, ptr(vert_mapping), NDV, ptr(faces), F,
+                                 ptr(map_face), ptr(map_bary), T, float(focal), float(depth_tol), float(min_cos), ptr(atlas), stream()),
+          'danet_texture_unwrap')
+    return atlas
+
+
+def texture_render(rverts, cam, vert_mapping, faces, uv, face_part, fidx, atlas, atlas_index=None, images=None, focal=5000.,
+                   fill=(0.5, 0.5, 0.5)):
+    """The textured draw, one launch: rverts [N,NV,3] (already rotated), cam [N,3], fidx [N,S,S] int32 (iuv_raster's face-index
+    plane of `faces` at orig = out_size = S), atlas [P,24,T,T,4], atlas_index: HOST integers [N] in [0, P) (None: view n draws
+    atlas n), images [N,3,S,S] or None -> (rgb [N,3,S,S], alpha [N,S,S])."""
+    import ctypes
+    L = _lib.lib()
+    v, c = _f32c(_dev_tensor(rverts, 'texture_render')), _f32c(_dev_tensor(cam, 'texture_render'))
+    at = _dev_tensor(atlas, 'texture_render')
+    if v.dim() != 3 or v.shape[2] != 3 or tuple(c.shape) != (v.shape[0], 3):
+        raise ValueError('texture_render: vertices %s, cam %s' % (tuple(v.shape), tuple(c.shape)))
+    N, S = v.shape[0], fidx.shape[-1]
+    if at.dim() != 5 or at.shape[1] != 24 or at.shape[2] != at.shape[3] or at.shape[4] != 4 or at.shape[0] < 1:
+        raise ValueError('texture_render: atlas %s, expected [P,24,T,T,4]' % (tuple(at.shape),))
+    P, T = at.shape[0], _texture_size(at.shape[2])
+    _typed(at, torch.float32, (P, 24, T, T, 4), 'texture_render: atlas')
+    _typed(fidx, torch.int32, (N, S, S), 'texture_render: fidx')
+    idx = texture_atlas_index(atlas_index, N, P)
+    NDV, F = vert_mapping.numel(), faces.shape[0]
+    _typed(vert_mapping, torch.int32, (NDV,), 'texture_render: vert_mapping')
+    _typed(faces, torch.int32, (F, 3), 'texture_render: faces')
+    _typed(uv, torch.float32, (NDV, 2), 'texture_render: uv')
+    _typed(face_part, torch.int32, (F,), 'texture_render: face_part')
+    img = None
+    if images is not None:
+        img = _f32c(_dev_tensor(images, 'texture_render'))
+        if tuple(img.shape) != (N, 3, S, S):
+            raise ValueError('texture_render: images %s, expected %s' % (tuple(img.shape), (N, 3, S, S)))
+    fl = (ctypes.c_float * 3)(*[float(x) for x in fill])
+    rgb = torch.empty(N, 3, S, S, device=v.device, dtype=torch.float32)
+    alpha = torch.empty(N, S, S, device=v.device, dtype=torch.float32)
+    check(L.danet_texture_render(ptr(v), ptr(c), N, v.shape[1], ptr(vert_mapping), NDV, ptr(faces), F, ptr(uv), ptr(face_part),
+                                 ptr(fidx), ptr(at), P, T, ptr(_texture_ints(idx, v.device)),
+                                 idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(img), float(focal), S, fl, ptr(rgb), ptr(alpha),
+                                 stream()), 'danet_texture_render')
+    return rgb, alpha

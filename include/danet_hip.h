@@ -889,6 +889,35 @@ int danet_scene_render(const float* verts, const float* vcol, int P, int V, cons
                        const int32_t* host_person_frame, const int64_t* host_offsets, const int32_t* host_shapes,
                        uint8_t* out, int32_t* ids, float* depth, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Texture atlases over the 24 DensePose charts (csrc/texture_ops.hip; forward only, texture.py is the caller; DESIGN.md
+ * "texture rule").  One launch each, no workspace, capturable.  The topology tables are texture.atlas_tables': faces [F,3] i32
+ * over the NDV DensePose vertices, uv [NDV,2] f32, vert_mapping [NDV] i32 into the NV mesh vertices, face_part [F] i32 in
+ * [0, 24), and the faces of every part in ascending index as a CSR (part_off [25], part_faces [F]).  The caller vouches for
+ * the index ranges of these tables.
+ *
+ * texture_map: face [24,T,T] i32 (-1: no face) and bary [24,T,T,2] f32 of every texel centre, in double from the f32 table.
+ * texture_unwrap: images [N,3,H,H] f32, verts [N,NV,3], cam [N,3] (s, tx, ty), depth [N,H,H] the rasteriser's depth plane at
+ * orig = S = H, view_off [P+1] i32 (the views of person p are view_off[p] .. view_off[p+1] - 1) with its HOST copy, which is
+ * checked (from 0, non-decreasing, to N) before the launch -> atlas [P,24,T,T,4] f32 (r, g, b, summed weight), 16-byte aligned,
+ * every texel written.
+ * texture_render: rverts [N,NV,3] (already rotated), face_idx [N,S,S] the rasteriser's face-index plane of `faces` at
+ * orig = S, atlas [P,24,T,T,4], atlas_index [N] i32 with its HOST copy (checked: in [0, P)), images [N,3,S,S] or NULL, fill:
+ * 3 HOST floats -> rgb [N,3,S,S], alpha [N,S,S] (1 where a face was drawn).
+ */
+int danet_texture_map(const float* uv, int NDV, const int32_t* faces, int F, const int32_t* part_off,
+                      const int32_t* part_faces, int T, int32_t* face, float* bary, void* stream);
+int danet_texture_unwrap(const float* images, const float* verts, const float* cam, const float* depth, int N, int NV,
+                         int H, const int32_t* view_off, const int32_t* host_view_off, int P,
+                         const int32_t* vert_mapping, int NDV, const int32_t* faces, int F, const int32_t* map_face,
+                         const float* map_bary, int T, float focal, float depth_tol, float min_cos, float* atlas,
+                         void* stream);
+int danet_texture_render(const float* rverts, const float* cam, int N, int NV, const int32_t* vert_mapping, int NDV,
+                         const int32_t* faces, int F, const float* uv, const int32_t* face_part,
+                         const int32_t* face_idx, const float* atlas, int P, int T, const int32_t* atlas_index,
+                         const int32_t* host_atlas_index, const float* images, float focal, int S, const float* fill,
+                         float* rgb, float* alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

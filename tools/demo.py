@@ -1,14 +1,18 @@
 """A folder of images in, one <name>_result.png per image out (/root/reference/demo.py): input | decoded global IUV | the 24
 decoded partial IUV maps | IUV rendering of the predicted mesh over the input | with --mesh: shaded mesh over the input |
-shaded mesh turned by 90 degrees.
+shaded mesh turned by 90 degrees | with --texture: the mesh wearing the photograph's own colours, turned by 90 and by 180 degrees,
+plus one <name>_texture.png, the 4 x 6 sheet of the 24 DensePose charts the photograph was unwrapped to (texture.TextureAtlas).
+With --fuse all images of the folder are views of ONE person: one atlas, fused_texture.png, drawn in every strip.
 
   python tools/demo.py --img_dir DIR --out_dir DIR [--checkpoint FILE] [--cfg YAML] [--mesh] [--engine] [--batch N]
+                       [--texture [--fuse] [--texture_size T]]
 
 Images: .npy arrays always ([S,S,3] or [3,S,S], uint8 or float in [0,1]); .jpg / .png if PIL is installed.  They must be square
 at DANET.INIMG_SIZE (cropping is augment.py's job).  Without --checkpoint the model has seeded random weights and the synthetic
 SMPL / DensePose tables, so the tool runs on a clean checkout.  The PNG files are written by train_vis.write_png (zlib + struct).
 Last line: one JSON object with the milliseconds per image of the panel stage (demo.result_panels, HIP) beside the same panels
-assembled from tensor ops (panels_torch below), 20 alternating repetitions, median and p10..p90."""
+assembled from tensor ops (panels_torch below), 20 alternating repetitions, median and p10..p90; with --texture also the texel map,
+the unwrap and one draw (texture_map_hip, texture_unwrap_hip, texture_draw_hip)."""
 import argparse
 import json
 import os
@@ -77,6 +81,9 @@ def main(argv=None):
     ap.add_argument('--img_dir', required=True)
     ap.add_argument('--out_dir', default='./output')
     ap.add_argument('--mesh', action='store_true', help='add the two shaded-mesh panels (the reference\'s --use_opendr)')
+    ap.add_argument('--texture', action='store_true', help='add the two textured-mesh panels and write the texture sheets')
+    ap.add_argument('--fuse', action='store_true', help='with --texture: all images are views of one person, one fused atlas')
+    ap.add_argument('--texture_size', type=int, default=64, help='texels per side of a chart')
     ap.add_argument('--engine', action='store_true', help='run the BatchNorm-folded InferenceEngine instead of infer_net')
     ap.add_argument('--batch', type=int, default=1)
     ap.add_argument('--reps', type=int, default=20, help='timed repetitions of the panel stage (0: no timing)')
@@ -87,13 +94,14 @@ def main(argv=None):
     from danet_densepose2smpl_amd.config import cfg, cfg_from_file
     from danet_densepose2smpl_amd.danet import DaNet
     from danet_densepose2smpl_amd.renderer import MeshRenderer
+    from danet_densepose2smpl_amd.texture import TextureAtlas
     from danet_densepose2smpl_amd.trainer import default_options
     if not torch.cuda.is_available():
         raise SystemExit('tools/demo.py needs a GPU (there is no CPU path)')
     if a.cfg_file:
         cfg_from_file(a.cfg_file)
     S = cfg.DANET.INIMG_SIZE
-    names = sorted(n for n in os.listdir(a.img_dir) if n.lower().endswith(('.npy', '.jpg', '.jpeg', '.png')) and not n.endswith('_result.png'))
+    names = sorted(n for n in os.listdir(a.img_dir) if n.lower().endswith(('.npy', '.jpg', '.jpeg', '.png')) and not n.endswith(('_result.png', '_texture.png')))
     if not names:
         raise SystemExit('no .npy / .jpg / .png images in %s' % a.img_dir)
     imgs = [load_image(os.path.join(a.img_dir, n), S) for n in names]
@@ -107,19 +115,36 @@ def main(argv=None):
     smpl = model.iuv2smpl.smpl
     mesh_renderer = MeshRenderer(smpl.faces, img_res=S) if a.mesh else None
     engine = model.inference_engine(a.batch, mesh=True) if a.engine else None
+    if a.fuse and not a.texture:
+        raise SystemExit('--fuse needs --texture')
+    tex = TextureAtlas(size=a.texture_size) if a.texture else None
+    sheet_png = lambda atlas: to_uint8(tex.sheet(atlas).permute(0, 2, 3, 1).cpu().numpy())           # noqa: E731
 
+    def batches():
+        for i in range(0, len(imgs), a.batch):
+            chunk = imgs[i:i + a.batch]
+            n = len(chunk)
+            chunk = chunk + [chunk[-1]] * (a.batch - n)            # a short last batch is padded, its extra strips dropped
+            image = torch.from_numpy(np.stack(chunk)).cuda()
+            out = engine(image) if engine is not None else model.infer_net(image)
+            yield i, n, image, out
+
+    texture = tex
+    if a.fuse:                                                     # a first pass: every image is a view of the one person
+        views = [(image[:n], ) + tuple(t[:n].clone() for t in demo.mesh_of(out, smpl)) for _, n, image, out in batches()]
+        fused = tex.unwrap(*(torch.cat(t, 0) for t in zip(*views)), view_offsets=[0, len(imgs)])
+        write_png(os.path.join(a.out_dir, 'fused_texture.png'), sheet_png(fused)[0])
+        texture = (tex, fused)
     last = None
-    for i in range(0, len(imgs), a.batch):
-        chunk = imgs[i:i + a.batch]
-        n = len(chunk)
-        chunk = chunk + [chunk[-1]] * (a.batch - n)                # a short last batch is padded, its extra strips dropped
-        image = torch.from_numpy(np.stack(chunk)).cuda()
-        out = engine(image) if engine is not None else model.infer_net(image)
-        strip = demo.result_panels(out, image, smpl, model.iuv_renderer, mesh_renderer)
+    for i, n, image, out in batches():
+        strip, planes = demo.result_panels(out, image, smpl, model.iuv_renderer, mesh_renderer, return_planes=True, texture=texture)
         arr = to_uint8(strip.cpu().numpy())
+        sheets = sheet_png(planes['atlas']) if a.texture and not a.fuse else None
         for k in range(n):
-            path = os.path.join(a.out_dir, os.path.splitext(names[i + k])[0] + '_result.png')
-            write_png(path, arr[k])
+            stem = os.path.join(a.out_dir, os.path.splitext(names[i + k])[0])
+            write_png(stem + '_result.png', arr[k])
+            if sheets is not None:
+                write_png(stem + '_texture.png', sheets[k])
         last = (out, image)
     print('Demo results have been saved in {}.'.format(a.out_dir))
 
@@ -130,6 +155,14 @@ def main(argv=None):
         variants = {'panels_hip': hip, 'compose_hip': lambda: demo.ops.demo_compose(image, planes['glob'], planes['part'], planes['riuv'],
                                                                                   planes['mesh'], planes['side'], planes['side_alpha']),
                     'compose_tensor_ops': lambda: panels_torch(image, planes)}
+        if tex is not None:
+            import math
+            verts, cam = demo.mesh_of(out, smpl)
+            atlas = tex.unwrap(image, verts, cam)
+            d = tex._dev(image.device)
+            variants.update({'texture_map_hip': lambda: demo.ops.texture_map(d['uv'], d['faces'], d['part_off'], d['part_faces'], tex.size),
+                             'texture_unwrap_hip': lambda: tex.unwrap(image, verts, cam),
+                             'texture_draw_hip': lambda: tex.render(verts, cam, atlas, None, rot_y=math.radians(90), img_res=S)})
         for _ in range(3):
             for f in variants.values():
                 f()
@@ -144,6 +177,8 @@ def main(argv=None):
                 torch.cuda.synchronize()
                 times[k].append(e0.elapsed_time(e1))
         res = {'tool': 'demo', 'B': a.batch, 'S': S, 'mesh': bool(a.mesh), 'reps': a.reps}
+        if tex is not None:
+            res['texture_size'] = tex.size
         res.update({k: _stats(v, a.batch) for k, v in times.items()})
         print(json.dumps(res), flush=True)
     if engine is not None:

@@ -1,9 +1,11 @@
 """Uncropped photographs plus person boxes in, the same photographs with every predicted mesh drawn in place out: per image one
 <name>_scene.png (people in front occlude people behind) and one <name>_people.npz (para, cam, cam_t_full, focal_full, center,
-scale, vertices of every person); with --obj one <name>_person<k>.obj per person.
+scale, vertices of every person); with --obj one <name>_person<k>.obj per person; with --obj --texture instead one textured
+triple per person, <name>_<k>.obj + <name>_<k>.mtl + <name>_<k>_texture.png: the person's crop unwrapped to the 24 DensePose charts
+through the crop camera (texture.TextureAtlas, texture.write_textured_obj).  The scene picture is the same either way.
 
   python tools/demo_scene.py --img_dir DIR --out_dir DIR [--boxes FILE.json] [--keypoints_dir DIR] [--checkpoint FILE] [--cfg YAML]
-                             [--engine] [--batch N] [--obj]
+                             [--engine] [--batch N] [--obj [--texture [--texture_size T]]]
 
 Boxes: --boxes maps an image's file name to a list of [x, y, w, h]; --keypoints_dir holds <name>_keypoints.json in OpenPose's layout
 (one person per people[] entry, pose_keypoints_2d = x, y, confidence, ...); with neither, the whole image is one box.  There is no
@@ -79,19 +81,23 @@ def main(argv=None):
     ap.add_argument('--engine', action='store_true', help='run the BatchNorm-folded InferenceEngine instead of infer_net')
     ap.add_argument('--batch', type=int, default=1)
     ap.add_argument('--obj', action='store_true', help='also write one .obj per person')
+    ap.add_argument('--texture', action='store_true', help='with --obj: textured .obj + .mtl + _texture.png per person')
+    ap.add_argument('--texture_size', type=int, default=64, help='texels per side of a chart')
     ap.add_argument('--reps', type=int, default=20, help='timed repetitions of the three stages (0: no timing)')
     a = ap.parse_args(argv)
 
     import torch
-    from danet_densepose2smpl_amd import checkpoint, scene
+    from danet_densepose2smpl_amd import checkpoint, constants, scene, texture
     from danet_densepose2smpl_amd.config import cfg_from_file
     from danet_densepose2smpl_amd.danet import DaNet
     from danet_densepose2smpl_amd.trainer import default_options
     if not torch.cuda.is_available():
         raise SystemExit('tools/demo_scene.py needs a GPU (there is no CPU path)')
+    if a.texture and not a.obj:
+        raise SystemExit('--texture needs --obj')
     if a.cfg_file:
         cfg_from_file(a.cfg_file)
-    names = sorted(n for n in os.listdir(a.img_dir) if n.lower().endswith(('.npy', '.jpg', '.jpeg', '.png')) and not n.endswith('_scene.png'))
+    names = sorted(n for n in os.listdir(a.img_dir) if n.lower().endswith(('.npy', '.jpg', '.jpeg', '.png')) and not n.endswith(('_scene.png', '_texture.png')))
     if not names:
         raise SystemExit('no .npy / .jpg / .png images in %s' % a.img_dir)
     box_table = json.load(open(a.boxes)) if a.boxes else None
@@ -105,6 +111,7 @@ def main(argv=None):
     smpl = model.iuv2smpl.smpl
     engine = model.inference_engine(a.batch) if a.engine else None
     demo = scene.SceneDemo(engine if engine is not None else model, smpl, a.batch)
+    tex = texture.TextureAtlas(size=a.texture_size, focal_length=demo.focal) if a.texture else None
 
     last, people_total = None, 0
     for i in range(0, len(names), GROUP):
@@ -112,6 +119,14 @@ def main(argv=None):
         frames = [load_frame(os.path.join(a.img_dir, n)) for n in group]
         boxes = [boxes_of(n, f, box_table, a.keypoints_dir) for n, f in zip(group, frames)]
         rendered, people = demo(frames, boxes)
+        sheets = None
+        if tex is not None and any(boxes):                          # every person's crop, de-normalised, through the crop camera
+            mean, std = (torch.tensor(c, device=demo.device).view(1, 3, 1, 1) for c in (constants.IMG_NORM_MEAN, constants.IMG_NORM_STD))
+            crops = (demo.crops(demo.prepare(frames, boxes)) * std + mean).clamp(0.0, 1.0)
+            dev = lambda key: torch.from_numpy(np.concatenate([p[key] for p in people]).astype(np.float32)).to(demo.device)   # noqa: E731
+            atlas = tex.unwrap(crops, dev('vertices'), dev('cam'))
+            sheets = np.rint(tex.sheet(atlas).permute(0, 2, 3, 1).clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
+        person = 0
         for n, img, ppl in zip(group, rendered, people):
             stem = os.path.splitext(n)[0]
             write_png(os.path.join(a.out_dir, stem + '_scene.png'), img)
@@ -119,7 +134,13 @@ def main(argv=None):
             people_total += ppl['para'].shape[0]
             if a.obj:
                 for k in range(ppl['vertices'].shape[0]):
-                    scene.write_obj(os.path.join(a.out_dir, '%s_person%d.obj' % (stem, k)), ppl['vertices'][k], smpl.faces)
+                    if tex is None:
+                        scene.write_obj(os.path.join(a.out_dir, '%s_person%d.obj' % (stem, k)), ppl['vertices'][k], smpl.faces)
+                    else:
+                        write_png(os.path.join(a.out_dir, '%s_%d_texture.png' % (stem, k)), sheets[person + k])
+                        texture.write_textured_obj(os.path.join(a.out_dir, '%s_%d.obj' % (stem, k)), ppl['vertices'][k], tex.tables,
+                                                   '%s_%d_texture.png' % (stem, k))
+            person += ppl['vertices'].shape[0]
         if any(boxes):
             last = (frames, boxes)
     print('Scene demo results (%d frames, %d people) have been saved in %s.' % (len(names), people_total, a.out_dir))
