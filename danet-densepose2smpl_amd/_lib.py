@@ -356,12 +356,34 @@ def check(rc, what):
         raise RuntimeError('%s failed (%d): %s' % (what, rc, msg.decode() if msg else ''))
 
 
+GPU_ONLY = 'danet_hip ops run on the GPU only (%s: got a %s tensor); there is no CPU path'
+
+
+def require_gpu(t, what):
+    """Raises unless `t` is a tensor on the GPU; `what` names the op (or argument) in the message."""
+    import torch
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(GPU_ONLY % (what, t.device if torch.is_tensor(t) else type(t).__name__))
+
+
+def dev_tensor(t, what):
+    """require_gpu, then the tensor detached."""
+    require_gpu(t, what)
+    return t.detach()
+
+
+def f32c(t):
+    """The fp32, contiguous, detached form of a tensor (None -> None)."""
+    import torch
+    return None if t is None else t.detach().to(torch.float32).contiguous()
+
+
 def ptr(t):
     """Device pointer of a contiguous CUDA/HIP tensor (None -> NULL)."""
     if t is None:
         return None
     if not t.is_cuda:
-        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % t.device)
+        raise RuntimeError(GPU_ONLY % ('ptr', t.device))
     if not t.is_contiguous():
         raise RuntimeError('danet_hip ops need contiguous tensors')
     return t.data_ptr()

@@ -15,7 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F  # noqa: F401  (only for nn.init helpers / shape utils)
 
 from . import _lib
-from ._lib import ptr, check, stream
+from ._lib import ptr, check, stream, f32c
 
 _PACK_CACHE = {}
 
@@ -235,8 +235,7 @@ class Conv2dF32Function(torch.autograd.Function):
             raise ValueError('conv2d: input has %d channels, weight expects %d' % (Cin, Cin_g * groups))
         OH, OW = conv_out_size(H, R, stride, pad, dil), conv_out_size(W, S, stride, pad, dil)
         xh = x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
-        w = weight.detach().to(torch.float32).contiguous()
-        b = None if bias is None else bias.detach().to(torch.float32).contiguous()
+        w, b = f32c(weight), f32c(bias)
         Cout_g = Cout // groups
         Cin_gp, Cout_gp = (Cin_g + 3) // 4 * 4, (Cout_g + 3) // 4 * 4
         Cin_p, Cout_p = Cin_gp * groups, Cout_gp * groups

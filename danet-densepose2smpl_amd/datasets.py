@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import augment, constants, dp_utils, ops
+from ._lib import GPU_ONLY
 from .evaluate import read_array
 
 TRAIN_SETS = {'h36m_dp': ['h36m', 'dp_coco'],
@@ -263,7 +264,7 @@ def _upload(a, device):
     after the copy that read it has finished; eight deep, so that the wait is for a copy of an earlier batch)."""
     t = torch.from_numpy(np.ascontiguousarray(a))
     if device.type != 'cuda':
-        raise RuntimeError('danet_hip ops run on the GPU only (got device %s); there is no CPU path' % device)
+        raise RuntimeError(GPU_ONLY % ('upload device', device))
     slot = _PINNED.setdefault((t.dtype, device.index), {'bufs': [None] * 8, 'events': [None] * 8, 'turn': 0})
     k = slot['turn']
     slot['turn'] = (k + 1) % 8

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import ptr, check, stream
-from .conv import nhwc_bf16, pack_weight, _conv_fwd_raw, new_wgrad
+from .conv import nhwc_bf16, nptr, pack_weight, _conv_fwd_raw, new_wgrad
 
 
 class ConvTranspose2dFunction(torch.autograd.Function):
@@ -48,7 +48,7 @@ class ConvTranspose2dFunction(torch.autograd.Function):
             gw = new_wgrad(weight, (Cin, Cout, R, S), x.device)
             nws = L.danet_conv_wgrad_ws_floats(Cin, Cout, R, S)
             ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-            check(L.danet_conv_wgrad(ptr(gy.permute(0, 2, 3, 1)), ptr(x.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), nws,
+            check(L.danet_conv_wgrad(nptr(gy), nptr(x), ptr(gw), ptr(ws), nws,
                                      B, OH, OW, Cout, H, W, Cin, R, S, stride, pad, 1, 1, 0.0, 0, stream()), 'danet_conv_wgrad')
         if has_bias and ctx.needs_input_grad[2]:
             gb = gy.float().sum(dim=(0, 2, 3))
@@ -71,7 +71,7 @@ class ConvTranspose2dF32Function(torch.autograd.Function):
         wp = _conv._pack_weight_f32(weight, w, 1, 1, Cin, Cout)
         b = None if bias is None else bias.detach().float().contiguous()
         y = torch.empty(B, OH, OW, Cout, dtype=torch.float32, device=x.device)
-        check(L.danet_conv_f32m_forward(ptr(x.permute(0, 2, 3, 1)), ptr(wp), ptr(b), ptr(y), B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, 1, 1, 1, 0,
+        check(L.danet_conv_f32m_forward(nptr(x), ptr(wp), ptr(b), ptr(y), B, H, W, Cin, OH, OW, Cout, R, S, stride, pad, 1, 1, 1, 0,
                                         stream()), 'danet_conv_f32m_forward')
         ctx.save_for_backward(x, w)
         ctx.weight = weight
@@ -100,7 +100,7 @@ class ConvTranspose2dF32Function(torch.autograd.Function):
             gw = torch.empty_like(w)
             wdims = (B, OH, OW, Cout, H, W, Cin, R, S, stride, pad, 1, 1, Cin, Cout)
             ws = torch.empty(L.danet_conv_f32m_wgrad_ws_floats(*wdims), dtype=torch.float32, device=gy.device)
-            check(L.danet_conv_f32m_wgrad(ptr(g), ptr(x.permute(0, 2, 3, 1)), ptr(gw), ptr(ws), *wdims, stream()), 'danet_conv_f32m_wgrad')
+            check(L.danet_conv_f32m_wgrad(ptr(g), nptr(x), ptr(gw), ptr(ws), *wdims, stream()), 'danet_conv_f32m_wgrad')
         if has_bias and ctx.needs_input_grad[2]:
             gb = gy.sum(dim=(0, 2, 3))
         return gx, gw, gb, None, None, None

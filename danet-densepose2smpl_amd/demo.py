@@ -14,6 +14,7 @@ import math
 import torch
 
 from . import iuvmap, ops
+from ._lib import require_gpu
 from .iuv_estimator import DP2SMPL_MAPPING
 
 
@@ -33,8 +34,7 @@ def result_panels(out, images, smpl, iuv_renderer, mesh_renderer=None, dp2smpl_m
     the strip was composed from (glob, part, riuv, mesh, side, side_alpha).  texture: a TextureAtlas (or a pair (TextureAtlas,
     atlas [1 or B,24,T,T,4]) to draw an atlas made elsewhere, e.g. fused from several views): the strip grows by 2 S, the body
     textured from the images and turned by 90 and by 180 degrees, alpha = coverage; the columns before are unchanged."""
-    if not images.is_cuda:
-        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % images.device)
+    require_gpu(images, 'result_panels')
     B, _, S, _ = images.shape
     vis = out['visualization']
     u, v, idx = vis['iuv_pred'][:3]

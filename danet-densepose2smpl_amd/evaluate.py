@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import augment, constants, ops
+from ._lib import GPU_ONLY, require_gpu
 
 POSE_DATASETS = ('h36m-p1', 'h36m-p2', '3dpw', 'mpi-inf-3dhp')
 DATASETS = POSE_DATASETS + ('lsp',)
@@ -164,7 +165,7 @@ class Evaluator(object):
         self.part_renderer = part_renderer
         self.device = smpl_neutral.v_template.device
         if self.device.type != 'cuda':
-            raise RuntimeError('danet_hip ops run on the GPU only (got a %s SMPL model); there is no CPU path' % self.device)
+            raise RuntimeError(GPU_ONLY % ('Evaluator SMPL model', self.device))
         self.J_regressor = torch.as_tensor(J_regressor).float().contiguous().to(self.device)
         self.counters = torch.zeros(ops.SEG_COUNTERS, dtype=torch.int64, device=self.device)
         self._mpjpe, self._recon, self._j17, self._pose, self._betas, self._cam, self._names = [], [], [], [], [], [], []
@@ -172,8 +173,7 @@ class Evaluator(object):
         self._pve, self._pa_pve, self._pve_on = [], [], []
 
     def update(self, batch, para):
-        if not para.is_cuda:
-            raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % para.device)
+        require_gpu(para, 'Evaluator.update')
         B = para.shape[0]
         cam = para[:, 0:3].clone()                                                 # (an engine's `para` is a static buffer)
         betas = para[:, 3:13].clone()
@@ -474,7 +474,7 @@ def run_evaluation(model, dataset_name, dataset, result_file, batch_size=32, img
     infer, net = _model_parts(model)
     device = next(net.parameters()).device
     if device.type != 'cuda':
-        raise RuntimeError('danet_hip ops run on the GPU only (the model is on %s); there is no CPU path' % device)
+        raise RuntimeError(GPU_ONLY % ('run_evaluation model', device))
     opt = lambda k: getattr(options, k, None) if options is not None else None
     smpl = net.iuv2smpl.smpl
     Jr = opt('J_regressor')

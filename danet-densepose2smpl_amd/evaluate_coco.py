@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import constants, ops
+from ._lib import GPU_ONLY, require_gpu
 from .evaluate import EvalDataset, _model_parts, iterate_batches, to_device     # noqa: F401  (EvalDataset: re-exported)
 
 STAT_NAMES = ['AP', 'Ap .5', 'AP .75', 'AP (M)', 'AP (L)', 'AR', 'AR .5', 'AR .75', 'AR (M)', 'AR (L)']     # coco_keypoint_dataset.py:438
@@ -184,13 +185,12 @@ class CocoEvaluator(object):
         self.smpl = smpl_neutral
         self.device = smpl_neutral.v_template.device
         if self.device.type != 'cuda':
-            raise RuntimeError('danet_hip ops run on the GPU only (got a %s SMPL model); there is no CPU path' % self.device)
+            raise RuntimeError(GPU_ONLY % ('CocoEvaluator SMPL model', self.device))
         self.img_res, self.focal_length = int(img_res), float(focal_length)
         self._preds, self._para, self._center, self._scale, self._names = [], [], [], [], []
 
     def update(self, batch, para):
-        if not para.is_cuda:
-            raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % para.device)
+        require_gpu(para, 'CocoEvaluator.update')
         B = para.shape[0]
         para = para.detach().clone()                                               # (an engine's `para` is a static buffer)
         rotmat = para[:, 13:].contiguous().view(B, 24, 3, 3)
@@ -255,7 +255,7 @@ def run_evaluation(model, dataset, result_file, batch_size=32, img_res=224, num_
     infer, net = _model_parts(model)
     device = next(net.parameters()).device
     if device.type != 'cuda':
-        raise RuntimeError('danet_hip ops run on the GPU only (the model is on %s); there is no CPU path' % device)
+        raise RuntimeError(GPU_ONLY % ('run_evaluation model', device))
     gt = opt('keypoint_json')
     if gt is None:
         raise ValueError('run_evaluation: options.keypoint_json (the person_keypoints_*.json of the images) is required')

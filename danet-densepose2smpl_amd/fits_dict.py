@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._lib import GPU_ONLY
 
 
 class FitsDict(object):
@@ -18,7 +19,7 @@ class FitsDict(object):
     def __init__(self, options, train_dataset, final_fits_dir, static_fits_dir, device):
         self.options, self.train_dataset, self.device = options, train_dataset, torch.device(device)
         if self.device.type != 'cuda':
-            raise RuntimeError('danet_hip ops run on the GPU only (got device %s); there is no CPU path' % self.device)
+            raise RuntimeError(GPU_ONLY % ('FitsDict device', self.device))
         tables, valid, self.base, self.length = [], [], {}, {}
         at = 0
         for ds_name in train_dataset.dataset_dict:

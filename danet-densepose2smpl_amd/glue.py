@@ -5,7 +5,8 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import check, stream, ptr
+from ._lib import check, stream, ptr, f32c
+from .conv import nhwc_as, nptr, _empty_nhwc
 
 PAD_MAX = 16
 
@@ -91,7 +92,6 @@ def loss_finalize(n, scales, w, nw, sums=None, rows=1, grads=None):
     """csrc/glue.hip danet_loss_finalize: the n finished losses from raw double sums (forward: `sums`, rows x n doubles) or the n
     backward coefficients from the incoming gradients (`grads`: list of 1-element tensors / None).  scales = ((a_i, b_i), ...):
     loss_i = sum_i * a_i / (max(sum(w), 1) * b_i) where b_i > 0, sum_i * a_i otherwise; w = per-sample weights [nw] or None (= ones)."""
-    import ctypes
     dev = (sums if sums is not None else next(g for g in grads if g is not None)).device
     a = (ctypes.c_float * 8)(*([float(x[0]) for x in scales] + [0.0] * (8 - n)))
     b = (ctypes.c_float * 8)(*([float(x[1]) for x in scales] + [0.0] * (8 - n)))
@@ -102,7 +102,7 @@ def loss_finalize(n, scales, w, nw, sums=None, rows=1, grads=None):
         arr = (ctypes.c_void_p * 8)()
         for i, g in enumerate(grads):
             if g is not None:
-                g = g.detach().to(torch.float32).contiguous()
+                g = f32c(g)
                 keep.append(g)
                 arr[i] = g.data_ptr()
         gp = ctypes.addressof(arr)
@@ -119,28 +119,18 @@ class RegroupPartsFunction(torch.autograd.Function):
     def forward(ctx, x, NB):
         BJ, C, H, W = x.shape
         J = BJ // NB
-        xc = x.detach()
-        if not xc.permute(0, 2, 3, 1).is_contiguous():
-            xc = xc.contiguous(memory_format=torch.channels_last)
-            if not xc.permute(0, 2, 3, 1).is_contiguous():
-                xc = xc.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-        y = torch.empty(NB, H, W, J * C, dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
-        check(_lib.lib().danet_regroup_parts(ptr(xc.permute(0, 2, 3, 1)), ptr(y.permute(0, 2, 3, 1)), NB, J, H * W, C * x.element_size(), 0, stream()),
-              'danet_regroup_parts')
+        xc = nhwc_as(x.detach(), x.dtype)
+        y = _empty_nhwc(NB, J * C, H, W, x.dtype, x.device)
+        check(_lib.lib().danet_regroup_parts(nptr(xc), nptr(y), NB, J, H * W, C * x.element_size(), 0, stream()), 'danet_regroup_parts')
         ctx.dims = (NB, J, C, H, W)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         NB, J, C, H, W = ctx.dims
-        g = gy
-        if not g.permute(0, 2, 3, 1).is_contiguous():
-            g = g.contiguous(memory_format=torch.channels_last)
-            if not g.permute(0, 2, 3, 1).is_contiguous():
-                g = g.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-        gx = torch.empty(NB * J, H, W, C, dtype=g.dtype, device=g.device).permute(0, 3, 1, 2)
-        check(_lib.lib().danet_regroup_parts(ptr(g.permute(0, 2, 3, 1)), ptr(gx.permute(0, 2, 3, 1)), NB, J, H * W, C * g.element_size(), 1, stream()),
-              'danet_regroup_parts')
+        g = nhwc_as(gy, gy.dtype)
+        gx = _empty_nhwc(NB * J, C, H, W, g.dtype, g.device)
+        check(_lib.lib().danet_regroup_parts(nptr(g), nptr(gx), NB, J, H * W, C * g.element_size(), 1, stream()), 'danet_regroup_parts')
         return gx, None
 
 
@@ -158,6 +148,6 @@ def pack_image(x):
     xc = x.detach()
     if xc.dtype != torch.float32 or not xc.is_contiguous():
         xc = xc.float().contiguous()
-    y = torch.empty(B, H, W, 8, dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
-    check(_lib.lib().danet_pack_image(ptr(xc), ptr(y.permute(0, 2, 3, 1)), B, C, H, W, stream()), 'danet_pack_image')
+    y = _empty_nhwc(B, 8, H, W, torch.bfloat16, x.device)
+    check(_lib.lib().danet_pack_image(ptr(xc), nptr(y), B, C, H, W, stream()), 'danet_pack_image')
     return y

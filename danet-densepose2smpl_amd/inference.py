@@ -25,7 +25,7 @@ import torch.nn as tnn
 
 from . import _lib
 from . import conv as _conv
-from .conv import ptr, check, stream, conv_out_size, nhwc_bf16, _empty_nhwc
+from .conv import ptr, nptr, check, stream, conv_out_size, nhwc_bf16, _empty_nhwc
 from . import nn as _nn
 
 __all__ = ['fold_conv_bn', 'fold_plan', 'FoldPlan', 'InferenceEngine']
@@ -225,7 +225,7 @@ class _FoldedConv(tnn.Module):
         if res is None and not padn and L.danet_conv_stem_ok(B, H, W, Cin, OH, OW, Cout_p, self.R, self.S, self.stride, self.pad, self.dil, g):
             wp, b = self._packed(('s', padc), Cout_p, Cin_gp, 0, 16)
             y = _empty_nhwc(B, Cout_p, OH, OW, torch.bfloat16, x.device)
-            check(L.danet_conv_stem_forward_epi(ptr(x.permute(0, 2, 3, 1)), ptr(wp), ptr(b), ptr(y.permute(0, 2, 3, 1)), B, H, W, Cin, OH, OW, Cout_p,
+            check(L.danet_conv_stem_forward_epi(nptr(x), ptr(wp), ptr(b), nptr(y), B, H, W, Cin, OH, OW, Cout_p,
                                                 int(relu), stream()), 'danet_conv_stem_forward_epi')
             self.engine.launches['conv_stem_bias'] += 1
             return y
@@ -233,8 +233,8 @@ class _FoldedConv(tnn.Module):
             wp, b = self._packed(('a', padc), Cout_p, Cin_gp, 0, 16)
             y = _empty_nhwc(B, Cout_p, OH, OW, torch.bfloat16, x.device)
             add = None if res is None else nhwc_bf16(res)
-            check(L.danet_conv3x3a_forward_epi(ptr(x.permute(0, 2, 3, 1)), ptr(wp), ptr(b), None if add is None else ptr(add.permute(0, 2, 3, 1)),
-                                               ptr(y.permute(0, 2, 3, 1)), B, H, W, int(relu), stream()), 'danet_conv3x3a_forward_epi')
+            check(L.danet_conv3x3a_forward_epi(nptr(x), ptr(wp), ptr(b), nptr(add),
+                                               nptr(y), B, H, W, int(relu), stream()), 'danet_conv3x3a_forward_epi')
             self.engine.launches['conv3x3a_bias'] += 1
             return y
         wp, b = self._packed(('g', padc), Cout_p, Cin_gp, 0, 0)

@@ -190,8 +190,8 @@ class IUV_Estimator(nn.Module):
         (csrc/glue.hip stn_theta_kernel): centres [B,24,2], arg-max index plane uint8 [B,H,W] -> thetas [B,24,2,3].
         No gradient, as in the reference (theta is detached before affine_grid, :197)."""
         from . import _lib
-        from ._lib import ptr, check, stream
-        c = stn_centers.detach().to(torch.float32).contiguous()
+        from ._lib import ptr, check, stream, f32c
+        c = f32c(stn_centers)
         B = c.shape[0]
         jit = float(cfg.DANET.STN_SCALE_JITTER) if self.training else 0.
         rnd = torch.rand(2, B, 24, device=c.device) if jit > 0 else None

@@ -8,9 +8,12 @@ golden vectors)."""
 import torch
 
 from . import _lib
-from ._lib import ptr, check, stream
+from ._lib import ptr, check, stream, f32c, require_gpu
+from .glue import loss_finalize
 
 NP, NA, MAPC = 25, 15, 80
+LDP, LDA = 32, 16          # leading width (floats per pixel row) of the U / V / Index heads and of the Ann head
+VALID, LDS = (NP, NP, NP, NA), (LDP, LDP, LDP, LDA)
 PADDED_BASES = bool(int(__import__('os').environ.get('DANET_IUV_PADDED_BASES', '1')))       # A-B knob
 
 
@@ -25,6 +28,24 @@ def _rows(t, valid, ld):
     return buf.permute(0, 3, 1, 2)[:, :valid]
 
 
+def _head_rows(heads):
+    """The four head outputs (u, v, index, ann) -> (their four row tensors, `full` flags).  full: the input IS the conv epilogue's
+    padded output (all 32 / 16 channels: _padded_bases hands those over when it can) and gets its gradient back at that width -- no
+    slice-backward (a fill + a copy of the padded tensor per head) in between."""
+    return [_rows(t, n, ld) for t, n, ld in zip(heads, VALID, LDS)], tuple(t.shape[1] == ld for t, ld in zip(heads, LDS))
+
+
+def _grad_buffers(B, H, W, device):
+    """The four heads' gradient buffers, NHWC at the leading widths (fully written by the kernels: no memset)."""
+    du = torch.empty(B, H, W, LDP, dtype=torch.float32, device=device)
+    return du, torch.empty_like(du), torch.empty_like(du), torch.empty(B, H, W, LDA, dtype=torch.float32, device=device)
+
+
+def _head_grads(bufs, full):
+    """Gradient buffers + `full` -> the four returned gradients: at full width for padded bases, the valid channels otherwise."""
+    return tuple(t.permute(0, 3, 1, 2) if f else t.permute(0, 3, 1, 2)[:, :n] for t, n, f in zip(bufs, VALID, full))
+
+
 class IuvGlobalFunction(torch.autograd.Function):
     """(u, v, index, ann, gt_img | None, w | None, keep25 | None) -> (sums[4], iuv_map [B,80,H,W] bf16 channels_last,
     argmax [B,H,W] uint8 of the raw index logits)."""
@@ -36,28 +57,21 @@ class IuvGlobalFunction(torch.autograd.Function):
         multiplications / divisions, their backward and the select-backward fills cost ~6 launches per loss and pass."""
         L = _lib.lib()
         B, _, H, W = u.shape
-        # an input that IS the conv epilogue's padded output (all 32 / 16 channels: iuv_global hands those over when it can) gets
-        # its gradient back at that width -- no slice-backward (a fill + a copy of the padded tensor per head) in between
-        ctx.full = (u.shape[1] == 32, v.shape[1] == 32, ix.shape[1] == 32, an.shape[1] == 16)
-        u, v, ix = _rows(u, NP, 32), _rows(v, NP, 32), _rows(ix, NP, 32)
-        an = _rows(an, NA, 16)
+        (u, v, ix, an), ctx.full = _head_rows((u, v, ix, an))
         want = gt is not None
-        gtc = None if gt is None else gt.detach().to(torch.float32).contiguous()
-        wc = None if w is None else w.detach().to(torch.float32).contiguous()
-        kc = None if keep is None else keep.detach().to(torch.float32).contiguous()
+        gtc, wc, kc = f32c(gt), f32c(w), f32c(keep)
         dev = u.device
         mp = torch.empty(B, H, W, MAPC, dtype=torch.bfloat16, device=dev)
         am_raw = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
         am_drop = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
         sums = torch.zeros(4, dtype=torch.float64, device=dev)         # double accumulators: exact, order-independent adds of the workgroups' partial sums
-        check(L.danet_iuv_global_forward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), 32, 16, ptr(gtc), ptr(wc), ptr(kc),
+        check(L.danet_iuv_global_forward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), LDP, LDA, ptr(gtc), ptr(wc), ptr(kc),
                                          B, H, W, int(want), ptr(mp), ptr(am_raw), ptr(am_drop), ptr(sums), stream()), 'danet_iuv_global_forward')
         ctx.save_for_backward(u, v, ix, an, gtc, wc, kc, am_drop)
         ctx.want = want
         ctx.scales = scales
         ctx.mark_non_differentiable(am_raw)
         if scales is not None:
-            from .glue import loss_finalize
             out = loss_finalize(4, scales, wc, B, sums=sums, rows=1)
             ctx.set_materialize_grads(False)
             return out[0:1], out[1:2], out[2:3], out[3:4], mp.permute(0, 3, 1, 2), am_raw
@@ -73,25 +87,20 @@ class IuvGlobalFunction(torch.autograd.Function):
             g4, gmap = grads[:4], grads[4]
             gsums = None
             if ctx.want and any(g is not None for g in g4):
-                from .glue import loss_finalize
                 gsums = loss_finalize(4, ctx.scales, wc, B, grads=list(g4))
         else:
             gsums, gmap = grads[0], grads[1]
-        du = torch.empty(B, H, W, 32, dtype=torch.float32, device=dev)
-        dv, di = torch.empty_like(du), torch.empty_like(du)
-        da = torch.empty(B, H, W, 16, dtype=torch.float32, device=dev)
+        bufs = _grad_buffers(B, H, W, dev)
         coef = None
         if ctx.want:
             coef = torch.zeros(4, dtype=torch.float32, device=dev) if gsums is None else gsums.to(torch.float32).contiguous()
         gm = None
         if gmap is not None:
             gm = gmap.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
-        check(L.danet_iuv_global_backward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), 32, 16, ptr(gtc), ptr(wc), ptr(kc),
+        check(L.danet_iuv_global_backward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), LDP, LDA, ptr(gtc), ptr(wc), ptr(kc),
                                           ptr(am_drop), ptr(gm), ptr(coef), B, H, W, int(ctx.want and coef is not None),
-                                          ptr(du), ptr(dv), ptr(di), ptr(da), stream()), 'danet_iuv_global_backward')
-        f = lambda t, n, full: t.permute(0, 3, 1, 2) if full else t.permute(0, 3, 1, 2)[:, :n]        # noqa: E731
-        fu = ctx.full
-        return f(du, NP, fu[0]), f(dv, NP, fu[1]), f(di, NP, fu[2]), f(da, NA, fu[3]), None, None, None, None
+                                          *[ptr(t) for t in bufs], stream()), 'danet_iuv_global_backward')
+        return _head_grads(bufs, ctx.full) + (None,) * 4
 
 
 def iuv_global(u, v, ix, an, gt=None, w=None, keep=None, scales=None):
@@ -99,27 +108,21 @@ def iuv_global(u, v, ix, an, gt=None, w=None, keep=None, scales=None):
     (zeros when gt is None); iuv_map = [U_clean | V_clean | one-hot | 5 zero channels] as a bf16 channels_last
     [B,80,H,W] tensor (the body regressor's padded first-conv operand); argmax = uint8 [B,H,W] of the raw index head.
     scales = ((a, b),) * 4: the first result is the tuple of the four finished losses sums_i * a_i / (max(sum w, 1) * b_i) instead."""
-    if not u.is_cuda:
-        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % u.device)
-    if PADDED_BASES and torch.is_grad_enabled():
-        # head outputs that are [:, :25] / [:, :15] views of the conv epilogue's zero-padded fp32 NHWC output carry that tensor along
-        # (conv.conv2d `_padded_base`): taking IT as the differentiable input keeps autograd's slice-backward out of the backward pass
-        bases = [getattr(t, '_padded_base', None) for t in (u, v, ix, an)]
-        ok = all(b is not None and b.dtype == torch.float32 and b.shape[0] == t.shape[0] and b.shape[2:] == t.shape[2:] and
-                 b.data_ptr() == t.data_ptr() and b.shape[1] == ld for b, t, ld in zip(bases, (u, v, ix, an), (32, 32, 32, 16)))
-        if ok and all(_rows(b, n, ld) is b for b, n, ld in zip(bases, (NP, NP, NP, NA), (32, 32, 32, 16))):
-            return _pack(IuvGlobalFunction.apply(bases[0], bases[1], bases[2], bases[3], gt, w, keep, scales), scales)
+    require_gpu(u, 'iuv_global')
+    u, v, ix, an = _padded_bases(u, v, ix, an)
     return _pack(IuvGlobalFunction.apply(u, v, ix, an, gt, w, keep, scales), scales)
 
 
 def _padded_bases(u, v, ix, an):
-    """iuv_global's hand-over rule for dp_point_losses: -> the four `_padded_base` tensors when all four head outputs carry one that
-    qualifies (and gradients are being recorded), the tensors as they came otherwise."""
+    """The hand-over rule of iuv_global and dp_point_losses: -> the four `_padded_base` tensors when all four head outputs carry one
+    that qualifies (and gradients are being recorded), the tensors as they came otherwise.  Head outputs that are [:, :25] / [:, :15]
+    views of the conv epilogue's zero-padded fp32 NHWC output carry that tensor along (conv.conv2d `_padded_base`): taking IT as the
+    differentiable input keeps autograd's slice-backward out of the backward pass."""
     if PADDED_BASES and torch.is_grad_enabled():
         bases = [getattr(t, '_padded_base', None) for t in (u, v, ix, an)]
         ok = all(b is not None and b.dtype == torch.float32 and b.shape[0] == t.shape[0] and b.shape[2:] == t.shape[2:] and
-                 b.data_ptr() == t.data_ptr() and b.shape[1] == ld for b, t, ld in zip(bases, (u, v, ix, an), (32, 32, 32, 16)))
-        if ok and all(_rows(b, n, ld) is b for b, n, ld in zip(bases, (NP, NP, NP, NA), (32, 32, 32, 16))):
+                 b.data_ptr() == t.data_ptr() and b.shape[1] == ld for b, t, ld in zip(bases, (u, v, ix, an), LDS))
+        if ok and all(_rows(b, n, ld) is b for b, n, ld in zip(bases, VALID, LDS)):
             return bases
     return u, v, ix, an
 
@@ -158,8 +161,7 @@ class SoftArgmaxFunction(torch.autograd.Function):
 def softargmax(hm, scale=1.0):
     """Expected (x, y) pixel index of softmax(scale * hm) over each joint's map: [B,J,H,W] -> [B,J,2]
     (= softmax_integral_tensor(scale * hm, J, H, W) of geometry.py)."""
-    if not hm.is_cuda:
-        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % hm.device)
+    require_gpu(hm, 'softargmax')
     return SoftArgmaxFunction.apply(hm, scale)
 
 
@@ -172,17 +174,14 @@ class DpPointLossesFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, v, ix, an, X, Y, I, TU, TV, PW, labels, w, align, scales):
-        from .glue import loss_finalize
         L = _lib.lib()
         B, _, H, W = u.shape
         if H != W:
             raise RuntimeError('dp_point_losses: square maps expected, got %d x %d' % (H, W))
-        ctx.full = (u.shape[1] == 32, v.shape[1] == 32, ix.shape[1] == 32, an.shape[1] == 16)
-        u, v, ix = _rows(u, NP, 32), _rows(v, NP, 32), _rows(ix, NP, 32)
-        an = _rows(an, NA, 16)
+        (u, v, ix, an), ctx.full = _head_rows((u, v, ix, an))
         rows = L.danet_dp_point_losses_rows(B, H)
         partial = torch.empty(rows, 4, dtype=torch.float64, device=u.device)      # one row of double sums per workgroup, every row written
-        check(L.danet_dp_point_losses_forward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), 32, 16, ptr(X), ptr(Y), ptr(I), ptr(TU),
+        check(L.danet_dp_point_losses_forward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), LDP, LDA, ptr(X), ptr(Y), ptr(I), ptr(TU),
                                               ptr(TV), ptr(PW), ptr(labels), ptr(w), B, H, int(bool(align)), ptr(partial), stream()),
               'danet_dp_point_losses_forward')
         ctx.save_for_backward(u, v, ix, an, X, Y, I, TU, TV, PW, labels, w)
@@ -193,22 +192,17 @@ class DpPointLossesFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *g4):
-        from .glue import loss_finalize
         L = _lib.lib()
         u, v, ix, an, X, Y, I, TU, TV, PW, labels, w = ctx.saved_tensors
         B, _, H, W = u.shape
         if all(g is None for g in g4):
             return (None,) * 14
         coef = loss_finalize(4, ctx.scales, w, B, grads=list(g4))
-        du = torch.empty(B, H, W, 32, dtype=torch.float32, device=u.device)       # fully written by the kernel: no memset
-        dv, di = torch.empty_like(du), torch.empty_like(du)
-        da = torch.empty(B, H, W, 16, dtype=torch.float32, device=u.device)
-        check(L.danet_dp_point_losses_backward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), 32, 16, ptr(X), ptr(Y), ptr(I), ptr(TU),
+        bufs = _grad_buffers(B, H, W, u.device)
+        check(L.danet_dp_point_losses_backward(u.data_ptr(), v.data_ptr(), ix.data_ptr(), an.data_ptr(), LDP, LDA, ptr(X), ptr(Y), ptr(I), ptr(TU),
                                                ptr(TV), ptr(PW), ptr(labels), ptr(w), ptr(coef), B, H, int(ctx.align),
-                                               ptr(du), ptr(dv), ptr(di), ptr(da), stream()), 'danet_dp_point_losses_backward')
-        f = lambda t, n, full: t.permute(0, 3, 1, 2) if full else t.permute(0, 3, 1, 2)[:, :n]        # noqa: E731
-        fu = ctx.full
-        return (f(du, NP, fu[0]), f(dv, NP, fu[1]), f(di, NP, fu[2]), f(da, NA, fu[3])) + (None,) * 10
+                                               *[ptr(t) for t in bufs], stream()), 'danet_dp_point_losses_backward')
+        return _head_grads(bufs, ctx.full) + (None,) * 10
 
 
 def dp_point_losses(u, v, index, ann, dp, has_dp=None, align=True):
@@ -217,8 +211,7 @@ def dp_point_losses(u, v, index, ann, dp, has_dp=None, align=True):
     (loss_Udp, loss_Vdp, loss_IndexUVdp, loss_segAnndp), one-element tensors.  Every sample is evaluated and weighted by
     has_dp > 0; an all-zero has_dp gives exact zeros.  The backward pass uses no floating-point atomics: two runs are bitwise equal."""
     from .config import cfg
-    if not u.is_cuda:
-        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % u.device)
+    require_gpu(u, 'dp_point_losses')
     B, S = u.shape[0], u.shape[-1]
     f32 = lambda k, n: dp[k].detach().reshape(B, n).to(torch.float32).contiguous()                   # noqa: E731
     w = torch.ones(B, device=u.device) if has_dp is None else (has_dp.detach().reshape(B) > 0).to(torch.float32)

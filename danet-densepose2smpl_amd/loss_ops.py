@@ -8,7 +8,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import check, stream
+from ._lib import check, stream, ptr, f32c, require_gpu
 
 NT = 10
 KEYS = ('joint_rotation0', 'joint_rotation1', 'joint_position0', 'joint_position1', 'keypoints_2d', 'keypoints_3d',
@@ -28,10 +28,6 @@ class _LossG(ctypes.Structure):
                 ('djoints', ctypes.c_void_p), ('dverts', ctypes.c_void_p)]
 
 
-def _c(t):
-    return None if t is None else t.detach().to(torch.float32).contiguous()
-
-
 class SmplLossFunction(torch.autograd.Function):
     """(para, jrot0, jrot1, jpos0, jpos1, joints, verts; constants) -> losses [10] in the order of KEYS (absent stages: 0)."""
 
@@ -41,16 +37,15 @@ class SmplLossFunction(torch.autograd.Function):
         assert L.danet_smpl_loss_param_bytes() == ctypes.sizeof(_LossP) and L.danet_smpl_loss_grad_bytes() == ctypes.sizeof(_LossG)
         target, gt_pts, tverts, kps2d, kps3d, has_smpl, has_kp3d, focal, img, op_w, gt_w, weights = const
         B = para.shape[0]
-        ts = {'para': _c(para), 'target': _c(target), 'jrot0': _c(jrot0), 'jrot1': _c(jrot1), 'jpos0': _c(jpos0), 'jpos1': _c(jpos1),
-              'gt_pts': _c(gt_pts), 'joints': _c(joints), 'verts': _c(verts) if weights[8] != 0 else None,
-              'tverts': _c(tverts) if weights[8] != 0 else None, 'kps2d': _c(kps2d), 'kps3d': _c(kps3d),
-              'has_smpl': _c(has_smpl), 'has_kp3d': _c(has_kp3d)}
+        ts = {'para': f32c(para), 'target': f32c(target), 'jrot0': f32c(jrot0), 'jrot1': f32c(jrot1), 'jpos0': f32c(jpos0), 'jpos1': f32c(jpos1),
+              'gt_pts': f32c(gt_pts), 'joints': f32c(joints), 'verts': f32c(verts) if weights[8] != 0 else None,
+              'tverts': f32c(tverts) if weights[8] != 0 else None, 'kps2d': f32c(kps2d), 'kps3d': f32c(kps3d),
+              'has_smpl': f32c(has_smpl), 'has_kp3d': f32c(has_kp3d)}
         p = _LossP()
-        dp = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        p.para, p.target, p.gt_pts, p.joints = dp(ts['para']), dp(ts['target']), dp(ts['gt_pts']), dp(ts['joints'])
-        p.jrot[0], p.jrot[1], p.jpos[0], p.jpos[1] = dp(ts['jrot0']), dp(ts['jrot1']), dp(ts['jpos0']), dp(ts['jpos1'])
-        p.verts, p.tverts, p.kps2d, p.kps3d = dp(ts['verts']), dp(ts['tverts']), dp(ts['kps2d']), dp(ts['kps3d'])
-        p.has_smpl, p.has_kp3d = dp(ts['has_smpl']), dp(ts['has_kp3d'])
+        p.para, p.target, p.gt_pts, p.joints = ptr(ts['para']), ptr(ts['target']), ptr(ts['gt_pts']), ptr(ts['joints'])
+        p.jrot[0], p.jrot[1], p.jpos[0], p.jpos[1] = ptr(ts['jrot0']), ptr(ts['jrot1']), ptr(ts['jpos0']), ptr(ts['jpos1'])
+        p.verts, p.tverts, p.kps2d, p.kps3d = ptr(ts['verts']), ptr(ts['tverts']), ptr(ts['kps2d']), ptr(ts['kps3d'])
+        p.has_smpl, p.has_kp3d = ptr(ts['has_smpl']), ptr(ts['has_kp3d'])
         p.B, p.V = B, 0 if verts is None else verts.shape[1]
         p.focal, p.img, p.op_w, p.gt_w = float(focal), float(img), float(op_w), float(gt_w)
         V3 = 3.0 * (verts.shape[1] if verts is not None else 1)
@@ -76,9 +71,8 @@ class SmplLossFunction(torch.autograd.Function):
         dpara, djr0, djr1, djp0, djp1, djo = mk(ts['para']), mk(ts['jrot0']), mk(ts['jrot1']), mk(ts['jpos0']), mk(ts['jpos1']), mk(ts['joints'])
         dve = mk(ts['verts'])
         g = _LossG()
-        dp = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        g.dpara, g.djoints, g.dverts = dp(dpara), dp(djo), dp(dve)
-        g.djrot[0], g.djrot[1], g.djpos[0], g.djpos[1] = dp(djr0), dp(djr1), dp(djp0), dp(djp1)
+        g.dpara, g.djoints, g.dverts = ptr(dpara), ptr(djo), ptr(dve)
+        g.djrot[0], g.djrot[1], g.djpos[0], g.djpos[1] = ptr(djr0), ptr(djr1), ptr(djp0), ptr(djp1)
         go = gout.to(torch.float32).contiguous()
         check(L.danet_smpl_loss_backward(ctypes.addressof(p), go.data_ptr(), ctx.norm.data_ptr(), ctypes.addressof(g), stream()), 'danet_smpl_loss_backward')
         res = []
@@ -91,8 +85,7 @@ def smpl_losses(para, joint_rotation, joint_position, joints, verts, target, gt_
                 focal, img, op_w, gt_w, weights):
     """-> {loss name: 0-dim tensor}.  joint_rotation / joint_position: lists (<= 2 stages each) of [B,216] / [B,24,3];
     weights: dict with SMPL_POSE, JOINT_POSITION, PROJ_KPS, KPS3D, SMPL_BETAS, VERTS (the yaml weights)."""
-    if not para.is_cuda:
-        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % para.device)
+    require_gpu(para, 'smpl_losses')
     if len(joint_rotation) > 2 or len(joint_position) > 2:
         raise ValueError('at most two regressor stages')
     jr = list(joint_rotation) + [None] * (2 - len(joint_rotation))

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import check, stream
+from ._lib import check, stream, f32c as _f32, require_gpu
 
 # the chains (joints, LSTM index) in the reference's order (limb_branch_lstm, smpl_regressor.py:470-476); c1..c3 start from c0's
 # final state.  The kernel holds the same table (csrc/lstm_tree.hip kJoint / kLstm).
@@ -50,10 +50,6 @@ class LimbLSTM(nn.Module):
         raise RuntimeError('LimbLSTM runs only inside lstm_tree() (csrc/lstm_tree.hip)')
 
 
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
 def _fill_params(a, ps, grads=False):
     """ps: 40 tensors, LSTM-major, then direction, then (w_ih, w_hh, b_ih, b_hh)."""
     names = ('g_w_ih', 'g_w_hh', 'g_b_ih', 'g_b_hh') if grads else ('w_ih', 'w_hh', 'b_ih', 'b_hh')
@@ -73,7 +69,7 @@ class LstmTreeFunction(torch.autograd.Function):
         if not L.danet_lstm_tree_ok(B):
             raise ValueError('lstm_tree: unsupported batch %d' % B)
         x = _f32(pos)
-        _lib.ptr(x)                                   # (raises on a CPU tensor: there is no CPU path)
+        require_gpu(x, 'lstm_tree')
         ps = [_f32(p) for p in params]
         ws = torch.empty(L.danet_lstm_tree_ws_floats(B), dtype=torch.float32, device=x.device)
         out = torch.empty(B, 24, 256, dtype=torch.float32, device=x.device)

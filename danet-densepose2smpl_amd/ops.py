@@ -4,11 +4,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ptr, check, stream
-
-
-def _f32c(t):
-    return t.detach().to(torch.float32).contiguous()
+from ._lib import ptr, check, stream, f32c as _f32c, dev_tensor as _dev_tensor
 
 
 LBS_ONE_LAUNCH = True       # the SMPL forward as one kernel launch (csrc/smpl_lbs.hip smpl_fused_fwd_kernel); False: prep -> main -> finalize
@@ -19,7 +15,7 @@ SMPL_BWD_FUSED = bool(int(os.environ.get('DANET_LBS_BWD_FUSED', '0')))    # the 
 def lbs_ticket(device, words):
     """The fused forward's arrival counters: zeroed once, then owned (and reset) by the launches on ONE stream -- a buffer
     per (device, stream), so launches that could overlap never share one."""
-    if not LBS_ONE_LAUNCH or device.type != 'cuda':          # (CPU tensors: the C-ABI call below refuses them -- there is no CPU path)
+    if not LBS_ONE_LAUNCH or device.type != 'cuda':          # (CPU tensors: the C-ABI call below refuses them)
         return None
     key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
     t = _LBS_TICKETS.get(key)
@@ -146,13 +142,6 @@ def iuv_raster(verts, cam, vert_mapping, faces, tex, focal, orig, out_size, retu
                                      ptr(faces), ptr(tex), faces.shape[0], float(focal), float(orig), S,
                                      ptr(out), ptr(fidx), ptr(depth), ptr(ws), nws, stream()), 'danet_iuv_raster_forward')
     return (out, fidx, depth) if return_aux else out
-
-
-def _dev_tensor(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError('danet_hip ops run on the GPU only (%s: got a %s tensor); there is no CPU path'
-                           % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-    return t.detach()
 
 
 def iuv_map2img(U, V, I, A=None, table=None):

@@ -9,8 +9,9 @@ Both take the grouped conv's output [B, 24*21, H, W] (bf16, channels_last) as it
 import torch
 
 from . import _lib
-from ._lib import ptr, check, stream
-from .conv import nhwc_bf16, ARENA
+from ._lib import ptr, check, stream, f32c, require_gpu
+from .conv import nhwc_bf16, nptr, _empty_nhwc, ARENA
+from .glue import loss_finalize
 
 NJ, NC = 24, 7
 
@@ -31,37 +32,88 @@ def padded_view6(pp):
     return v
 
 
+def _flat(pred):
+    """The [B, 24*21 | 24*24, H, W] prediction behind a [B,24,3,7,H,W] view: the group-padded tensor riding along as `._padded`, a
+    reshape otherwise; a 4-D prediction as it is."""
+    if pred.dim() == 6:
+        B, J, T, K, H, W = pred.shape
+        padded = getattr(pred, '_padded', None)
+        pred = padded if padded is not None else pred.reshape(B, J * T * K, H, W)
+    _cpj(pred.shape[1])
+    return pred
+
+
+def _gt_args(op, iuv_img, theta, sel, sample_w=None, BHW=None):
+    """(iuv_img, theta, sample_w | None, sel) cast for the kernels and checked against (B, H, W) (None: the IUV image's own)."""
+    img, th, w = f32c(iuv_img), f32c(theta), f32c(sample_w)
+    sel = sel.to(torch.int32).contiguous()
+    if BHW is None:
+        B, _, H, W = img.shape
+    else:
+        B, H, W = BHW
+    if img.shape != (B, 3, H, W) or th.shape != (B, NJ, 2, 3) or sel.shape != (NJ, 6):
+        raise ValueError('%s: bad shapes %s %s %s' % (op, tuple(img.shape), tuple(th.shape), tuple(sel.shape)))
+    return img, th, w, sel
+
+
+# One function per C entry point of csrc/part_ops.hip.  pred, g24: bf16 channels_last; gt = _gt_args' (img, th, w, sel).
+
+def _clean_fwd(pred, k):
+    B, C, H, W = pred.shape
+    x24 = _empty_nhwc(B * NJ, 24, H, W, torch.bfloat16, pred.device)
+    check(_lib.lib().danet_part_clean_forward(nptr(pred), ptr(k), B, H, W, _cpj(C), nptr(x24), stream()), 'danet_part_clean_forward')
+    return x24
+
+
+def _clean_bwd(g24, pred, k):
+    B, C, H, W = pred.shape
+    gp = _empty_nhwc(B, C, H, W, torch.bfloat16, pred.device)
+    check(_lib.lib().danet_part_clean_backward(nptr(g24), nptr(pred), ptr(k), B, H, W, _cpj(C), nptr(gp), stream()), 'danet_part_clean_backward')
+    return gp
+
+
+def _loss_fwd(pred, gt, align):
+    B, C, H, W = pred.shape
+    sums = ARENA.zeros(32 * 3 * 2, pred.device)              # [32][3] doubles: exact, order-independent adds of the workgroups' partial sums
+    check(_lib.lib().danet_part_loss_forward(nptr(pred), *[ptr(t) for t in gt], B, H, W, align, _cpj(C), ptr(sums), stream()),
+          'danet_part_loss_forward')
+    return sums
+
+
+def _loss_bwd(pred, gt, scale, align):
+    B, C, H, W = pred.shape
+    gp = _empty_nhwc(B, C, H, W, torch.bfloat16, pred.device)
+    check(_lib.lib().danet_part_loss_backward(nptr(pred), *[ptr(t) for t in gt], ptr(scale), B, H, W, align, _cpj(C), nptr(gp), stream()),
+          'danet_part_loss_backward')
+    return gp
+
+
+def _fused_bwd(pred, gt, scale, g24, k, align):
+    B, C, H, W = pred.shape
+    gp = _empty_nhwc(B, C, H, W, torch.bfloat16, pred.device)
+    check(_lib.lib().danet_part_backward_fused(nptr(pred), *[ptr(t) for t in gt], ptr(scale), nptr(g24), ptr(k), B, H, W, align, _cpj(C),
+                                               nptr(gp), stream()), 'danet_part_backward_fused')
+    return gp
+
+
 class PartCleanFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, keep):
-        pred = nhwc_bf16(pred)
-        B, C, H, W = pred.shape
-        cpj = _cpj(C)
-        k = None if keep is None else keep.detach().to(torch.float32).contiguous()
-        x24 = torch.empty(B * NJ, H, W, 24, dtype=torch.bfloat16, device=pred.device).permute(0, 3, 1, 2)
-        check(_lib.lib().danet_part_clean_forward(ptr(pred.permute(0, 2, 3, 1)), ptr(k), B, H, W, cpj, ptr(x24.permute(0, 2, 3, 1)), stream()),
-              'danet_part_clean_forward')
+        pred, k = nhwc_bf16(pred), f32c(keep)
         ctx.save_for_backward(pred, k)
-        return x24
+        return _clean_fwd(pred, k)
 
     @staticmethod
     def backward(ctx, g24):
         pred, k = ctx.saved_tensors
-        B, C, H, W = pred.shape
-        g24 = nhwc_bf16(g24)
-        gp = torch.empty(B, H, W, C, dtype=torch.bfloat16, device=pred.device).permute(0, 3, 1, 2)
-        check(_lib.lib().danet_part_clean_backward(ptr(g24.permute(0, 2, 3, 1)), ptr(pred.permute(0, 2, 3, 1)), ptr(k), B, H, W, _cpj(C),
-                                                   ptr(gp.permute(0, 2, 3, 1)), stream()), 'danet_part_clean_backward')
-        return gp, None
+        return _clean_bwd(nhwc_bf16(g24), pred, k), None
 
 
 def part_clean(pred, keep=None):
     """pred [B,504,H,W] (or its [B,24,3,7,H,W] view), keep [B,24,7] or None ->
     (part_iuv_map [B,24,3,7,H,W] bf16 view, x24 [B*24,24,H,W] bf16 channels_last: channels 21..23 are zero)."""
-    if pred.dim() == 6:
-        B, J, T, K, H, W = pred.shape
-        pred = getattr(pred, '_padded', None) if getattr(pred, '_padded', None) is not None else pred.reshape(B, J * T * K, H, W)
-    x24 = PartCleanFunction.apply(pred, keep)
+    require_gpu(pred, 'part_clean')
+    x24 = PartCleanFunction.apply(_flat(pred), keep)
     return padded_part_view(x24), x24
 
 
@@ -75,42 +127,27 @@ class PartLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, iuv_img, theta, sample_w, sel, align, scales=None):
         pred = nhwc_bf16(pred)
-        B, C, H, W = pred.shape
-        img = iuv_img.detach().to(torch.float32).contiguous()
-        th = theta.detach().to(torch.float32).contiguous()
-        w = None if sample_w is None else sample_w.detach().to(torch.float32).contiguous()
-        sel = sel.to(torch.int32).contiguous()
-        ctx.cpj = _cpj(C)
-        if img.shape != (B, 3, H, W) or th.shape != (B, NJ, 2, 3) or sel.shape != (NJ, 6):
-            raise ValueError('part_losses: bad shapes %s %s %s' % (tuple(img.shape), tuple(th.shape), tuple(sel.shape)))
-        sums = ARENA.zeros(32 * 3 * 2, pred.device)              # [32][3] doubles: exact, order-independent adds of the workgroups' partial sums
-        check(_lib.lib().danet_part_loss_forward(ptr(pred.permute(0, 2, 3, 1)), ptr(img), ptr(th), ptr(w), ptr(sel), B, H, W, int(align), ctx.cpj,
-                                                 ptr(sums), stream()), 'danet_part_loss_forward')
-        ctx.save_for_backward(pred, img, th, w, sel)
-        ctx.align = int(align)
-        ctx.scales = scales
+        B, _, H, W = pred.shape
+        gt = _gt_args('part_losses', iuv_img, theta, sel, sample_w, (B, H, W))
+        ctx.align, ctx.scales = int(align), scales
+        sums = _loss_fwd(pred, gt, ctx.align)
+        ctx.save_for_backward(pred, *gt)
         if scales is not None:               # the three finished losses, one launch (glue.loss_finalize; see iuv_ops.IuvGlobalFunction)
-            from .glue import loss_finalize
-            out = loss_finalize(3, scales, w, B, sums=sums, rows=32)
+            out = loss_finalize(3, scales, gt[2], B, sums=sums, rows=32)
             ctx.set_materialize_grads(False)
             return out[0:1], out[1:2], out[2:3]
         return sums.view(torch.float64).view(32, 3).sum(dim=0, dtype=torch.float64).float()
 
     @staticmethod
     def backward(ctx, *grads):
-        pred, img, th, w, sel = ctx.saved_tensors
-        B, C, H, W = pred.shape
-        gp = torch.empty(B, H, W, C, dtype=torch.bfloat16, device=pred.device).permute(0, 3, 1, 2)
+        pred, *gt = ctx.saved_tensors
         if ctx.scales is not None:
-            from .glue import loss_finalize
             if all(g is None for g in grads):
-                return None, None, None, None, None, None, None
-            scale = loss_finalize(3, ctx.scales, w, B, grads=list(grads))
+                return (None,) * 7
+            scale = loss_finalize(3, ctx.scales, gt[2], pred.shape[0], grads=list(grads))
         else:
-            scale = grads[0].detach().to(torch.float32).contiguous()
-        check(_lib.lib().danet_part_loss_backward(ptr(pred.permute(0, 2, 3, 1)), ptr(img), ptr(th), ptr(w), ptr(sel), ptr(scale),
-                                                  B, H, W, ctx.align, ctx.cpj, ptr(gp.permute(0, 2, 3, 1)), stream()), 'danet_part_loss_backward')
-        return gp, None, None, None, None, None, None
+            scale = f32c(grads[0])
+        return (_loss_bwd(pred, gt, scale, ctx.align),) + (None,) * 6
 
 
 def part_losses(pred, iuv_img, theta, sample_w, sel, align, scales=None):
@@ -118,10 +155,8 @@ def part_losses(pred, iuv_img, theta, sample_w, sel, align, scales=None):
     (b, joint, pixel) of w_b * cross-entropy of the index map; ground truth = the 3-channel IUV image
     resampled per joint by `theta` [B,24,2,3] (sel [24,6]: DensePose parts of each joint).
     scales = ((a, b),) * 3: the three FINISHED losses sums_i * a_i / (max(sum w, 1) * b_i) as a tuple of one-element tensors instead."""
-    if pred.dim() == 6:
-        B, J, T, K, H, W = pred.shape
-        pred = getattr(pred, '_padded', None) if getattr(pred, '_padded', None) is not None else pred.reshape(B, J * T * K, H, W)
-    return PartLossFunction.apply(pred, iuv_img, theta, sample_w, sel, align, scales)
+    require_gpu(pred, 'part_losses')
+    return PartLossFunction.apply(_flat(pred), iuv_img, theta, sample_w, sel, align, scales)
 
 
 class PartJointFunction(torch.autograd.Function):
@@ -132,68 +167,41 @@ class PartJointFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, keep, iuv_img, theta, sample_w, sel, align, scales):
-        from .glue import loss_finalize
-        pred = nhwc_bf16(pred)
-        B, C, H, W = pred.shape
-        cpj = _cpj(C)
-        L = _lib.lib()
-        k = None if keep is None else keep.detach().to(torch.float32).contiguous()
-        x24 = torch.empty(B * NJ, H, W, 24, dtype=torch.bfloat16, device=pred.device).permute(0, 3, 1, 2)
-        check(L.danet_part_clean_forward(ptr(pred.permute(0, 2, 3, 1)), ptr(k), B, H, W, cpj, ptr(x24.permute(0, 2, 3, 1)), stream()), 'danet_part_clean_forward')
-        img = iuv_img.detach().to(torch.float32).contiguous()
-        th = theta.detach().to(torch.float32).contiguous()
-        w = None if sample_w is None else sample_w.detach().to(torch.float32).contiguous()
-        sel = sel.to(torch.int32).contiguous()
-        if img.shape != (B, 3, H, W) or th.shape != (B, NJ, 2, 3) or sel.shape != (NJ, 6):
-            raise ValueError('part_joint: bad shapes %s %s %s' % (tuple(img.shape), tuple(th.shape), tuple(sel.shape)))
-        sums = ARENA.zeros(32 * 3 * 2, pred.device)
-        check(L.danet_part_loss_forward(ptr(pred.permute(0, 2, 3, 1)), ptr(img), ptr(th), ptr(w), ptr(sel), B, H, W, int(align), cpj, ptr(sums), stream()),
-              'danet_part_loss_forward')
-        out = loss_finalize(3, scales, w, B, sums=sums, rows=32)
-        ctx.save_for_backward(pred, k, img, th, w, sel)
-        ctx.align, ctx.scales, ctx.cpj = int(align), scales, cpj
+        pred, k = nhwc_bf16(pred), f32c(keep)
+        B, _, H, W = pred.shape
+        gt = _gt_args('part_joint', iuv_img, theta, sel, sample_w, (B, H, W))
+        ctx.align, ctx.scales = int(align), scales
+        x24 = _clean_fwd(pred, k)
+        out = loss_finalize(3, scales, gt[2], B, sums=_loss_fwd(pred, gt, ctx.align), rows=32)
+        ctx.save_for_backward(pred, k, *gt)
         ctx.set_materialize_grads(False)
         return x24, out[0:1], out[1:2], out[2:3]
 
     @staticmethod
     def backward(ctx, g24, *gl):
-        from .glue import loss_finalize
-        pred, k, img, th, w, sel = ctx.saved_tensors
-        B, C, H, W = pred.shape
-        L = _lib.lib()
-        none = (None,) * 8
+        pred, k, *gt = ctx.saved_tensors
         have_loss = any(g is not None for g in gl)
         if g24 is None and not have_loss:
-            return none
-        gp = torch.empty(B, H, W, C, dtype=torch.bfloat16, device=pred.device).permute(0, 3, 1, 2)
+            return (None,) * 8
         if g24 is not None:
             g24 = nhwc_bf16(g24)
         if not have_loss:
-            check(L.danet_part_clean_backward(ptr(g24.permute(0, 2, 3, 1)), ptr(pred.permute(0, 2, 3, 1)), ptr(k), B, H, W, ctx.cpj,
-                                              ptr(gp.permute(0, 2, 3, 1)), stream()), 'danet_part_clean_backward')
-            return (gp,) + none[1:]
-        scale = loss_finalize(3, ctx.scales, w, B, grads=list(gl))
-        if g24 is None or ctx.cpj != 24:
-            check(L.danet_part_loss_backward(ptr(pred.permute(0, 2, 3, 1)), ptr(img), ptr(th), ptr(w), ptr(sel), ptr(scale),
-                                             B, H, W, ctx.align, ctx.cpj, ptr(gp.permute(0, 2, 3, 1)), stream()), 'danet_part_loss_backward')
-            if g24 is not None:              # (the unpadded layout: two kernels and an add, as autograd would)
-                gc = torch.empty_like(gp)
-                check(L.danet_part_clean_backward(ptr(g24.permute(0, 2, 3, 1)), ptr(pred.permute(0, 2, 3, 1)), ptr(k), B, H, W, ctx.cpj,
-                                                  ptr(gc.permute(0, 2, 3, 1)), stream()), 'danet_part_clean_backward')
-                gp = gp + gc
-            return (gp,) + none[1:]
-        check(L.danet_part_backward_fused(ptr(pred.permute(0, 2, 3, 1)), ptr(img), ptr(th), ptr(w), ptr(sel), ptr(scale),
-                                          ptr(g24.permute(0, 2, 3, 1)), ptr(k), B, H, W, ctx.align, ctx.cpj, ptr(gp.permute(0, 2, 3, 1)), stream()),
-              'danet_part_backward_fused')
-        return (gp,) + none[1:]
+            gp = _clean_bwd(g24, pred, k)
+        else:
+            scale = loss_finalize(3, ctx.scales, gt[2], pred.shape[0], grads=list(gl))
+            if g24 is None:
+                gp = _loss_bwd(pred, gt, scale, ctx.align)
+            elif _cpj(pred.shape[1]) != 24:              # (the unpadded layout: two kernels and an add, as autograd would)
+                gp = _loss_bwd(pred, gt, scale, ctx.align) + _clean_bwd(g24, pred, k)
+            else:
+                gp = _fused_bwd(pred, gt, scale, g24, k, ctx.align)
+        return (gp,) + (None,) * 7
 
 
 def part_joint(pred, keep, iuv_img, theta, sample_w, sel, align, scales):
     """-> (x24, lU, lV, lI): part_clean(pred, keep)[1] and part_losses(..., scales=scales) as one autograd node."""
-    if pred.dim() == 6:
-        B, J, T, K, H, W = pred.shape
-        pred = getattr(pred, '_padded', None) if getattr(pred, '_padded', None) is not None else pred.reshape(B, J * T * K, H, W)
-    return PartJointFunction.apply(pred, keep, iuv_img, theta, sample_w, sel, align, scales)
+    require_gpu(pred, 'part_joint')
+    return PartJointFunction.apply(_flat(pred), keep, iuv_img, theta, sample_w, sel, align, scales)
 
 
 class PartGtFunction(torch.autograd.Function):
@@ -204,14 +212,9 @@ class PartGtFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, iuv_img, theta, sel, keep, keep25, align, body):
-        img = iuv_img.detach().to(torch.float32).contiguous()
-        th = theta.detach().to(torch.float32).contiguous()
-        sel = sel.to(torch.int32).contiguous()
+        img, th, _, sel = _gt_args('part_gt', iuv_img, theta, sel)
         B, _, H, W = img.shape
-        if img.shape != (B, 3, H, W) or th.shape != (B, NJ, 2, 3) or sel.shape != (NJ, 6):
-            raise ValueError('part_gt: bad shapes %s %s %s' % (tuple(img.shape), tuple(th.shape), tuple(sel.shape)))
-        k = None if keep is None else keep.detach().to(torch.float32).contiguous()
-        k25 = None if keep25 is None else keep25.detach().to(torch.float32).contiguous()
+        k, k25 = f32c(keep), f32c(keep25)
         if (k is not None and k.shape != (B, NJ, NC)) or (k25 is not None and k25.shape != (B, 25)):
             raise ValueError('part_gt: bad keep shapes')
         x24 = torch.empty(B * NJ, H, W, 24, dtype=torch.bfloat16, device=img.device)
@@ -235,7 +238,7 @@ class PartGtFunction(torch.autograd.Function):
         B, _, H, W = img.shape
         g24 = nhwc_bf16(g24)
         dth = torch.empty(B, NJ, 2, 3, dtype=torch.float32, device=img.device)
-        check(_lib.lib().danet_part_gt_backward(ptr(img), ptr(th), ptr(sel), ptr(k), ptr(g24.permute(0, 2, 3, 1)), B, H, W, ctx.align,
+        check(_lib.lib().danet_part_gt_backward(ptr(img), ptr(th), ptr(sel), ptr(k), nptr(g24), B, H, W, ctx.align,
                                                 ptr(dth), stream()), 'danet_part_gt_backward')
         return None, dth.to(ctx.theta_dtype), None, None, None, None, None
 
@@ -244,6 +247,5 @@ def part_gt(iuv_img, theta, sel, keep=None, keep25=None, align=True, body=False)
     """x24 [B*24,24,H,W] bf16 channels_last = keep * (part_iuv_simp + affine_grid/grid_sample of the IUV image by theta), channels 21..23
     zero (the regressor's limb operand, as part_clean makes it); with body=True also the body operand [B,80,H,W] (iuvmap_clean of the
     keep25-dropped iuv_img2map, [U | V | I | 5 zeros]).  Differentiable in theta.  GPU only."""
-    if not iuv_img.is_cuda:
-        raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % iuv_img.device)
+    require_gpu(iuv_img, 'part_gt')
     return PartGtFunction.apply(iuv_img, theta, sel, keep, keep25, align, body)

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from . import assets, ops
+from ._lib import require_gpu
 
 
 class IUV_Renderer(object):
@@ -160,8 +161,7 @@ class MeshRenderer(object):
         return self._tables[key]
 
     def __call__(self, vertices, cam, images=None, rot_y=0.):
-        if not vertices.is_cuda:
-            raise RuntimeError('danet_hip ops run on the GPU only (got a %s tensor); there is no CPU path' % vertices.device)
+        require_gpu(vertices, 'MeshRenderer')
         R = self.img_res
         vm, f, f2, off, inc, tex = self._dev(vertices.device, vertices.shape[1])
         ws, rverts = ops.mesh_shade_vertices(vertices, f, off, inc, self.lights, rot_y, ALBEDO)

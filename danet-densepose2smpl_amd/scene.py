@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import constants, datasets, ops
+from ._lib import GPU_ONLY
 from .renderer import ALBEDO, MeshRenderer
 
 
@@ -135,7 +136,7 @@ class SceneDemo(object):
         self.focal, self.focal_full = float(focal), focal_full
         self.device = self.engine.device if self.engine is not None else next(self.model.parameters()).device
         if self.device.type != 'cuda':
-            raise RuntimeError('danet_hip ops run on the GPU only (the model is on %s); there is no CPU path' % self.device)
+            raise RuntimeError(GPU_ONLY % ('SceneDemo model', self.device))
         if self.batch < 1:
             raise ValueError('SceneDemo: batch %d' % self.batch)
         self.mesh = MeshRenderer(smpl.faces, focal_length=self.focal, img_res=self.res)      # its face tables and lights

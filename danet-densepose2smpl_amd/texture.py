@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import assets, ops
+from ._lib import require_gpu
 
 PARTS = 24
 SHEET_ROWS, SHEET_COLS = 4, 6
@@ -104,9 +105,7 @@ class TextureAtlas(object):
         return d['map_face'], d['map_bary']
 
     def _check_mesh(self, what, vertices, cam):
-        if not torch.is_tensor(vertices) or not vertices.is_cuda:
-            raise RuntimeError('danet_hip ops run on the GPU only (%s: got a %s tensor); there is no CPU path'
-                               % (what, vertices.device if torch.is_tensor(vertices) else type(vertices).__name__))
+        require_gpu(vertices, what)
         if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[1] < self.num_verts or tuple(cam.shape) != (vertices.shape[0], 3):
             raise ValueError('%s: vertices %s, cam %s (the topology names %d mesh vertices)' % (what, tuple(vertices.shape), tuple(cam.shape), self.num_verts))
 

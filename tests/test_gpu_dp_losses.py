@@ -214,3 +214,30 @@ def test_estimator_dispatches_to_the_op_and_fp32_mode_to_the_torch_form(monkeypa
     assert est.iuv_est.final_pred.predict_ann_index.weight.grad.abs().sum() > 0
     with conv.precision('fp32'), pytest.raises(Reached):
         est(t('img'), t('iuv_gt'), t('kps'), uvia_dp_gt=dp, has_iuv=torch.ones(2, device=DEV), has_dp=has_dp)
+
+
+def test_padded_base_hand_over_is_bit_equal_to_plain_heads():
+    """B = 3, S = 16: dp_point_losses on leaf [B,25|15,S,S] heads and on [:, :25] / [:, :15] views carrying the `_padded_base` of leaf NHWC
+    [B,32|16,S,S] buffers (same values, zeros behind): the losses bit-equal, the gradient on the base at full width with exactly zero
+    pad channels and its leading channels bit-equal -- both runs feed the kernels the same row buffers."""
+    from danet_densepose2smpl_amd import iuv_ops
+    _cfg(**{'DANET.HEATMAP_SIZE': 16})
+    preds, dp, has_dp = _edge_case(S=16, B=3)
+    d, w = {k: v.to(DEV) for k, v in dp.items()}, has_dp.to(DEV)
+    plain = [t.to(DEV).clone().requires_grad_(True) for t in preds]
+    bases = [_padded(t.to(DEV), ld).requires_grad_(True) for t, ld in zip(preds, (32, 32, 32, 16))]
+    views = []
+    for b, t in zip(bases, preds):
+        v = b[:, :t.shape[1]]
+        v._padded_base = b
+        views.append(v)
+    res = []
+    for ins in (plain, views):
+        out = iuv_ops.dp_point_losses(*ins, d, w, True)
+        sum(o * c for o, c in zip(out, (1., 2., 3., 4.))).sum().backward()
+        res.append(torch.cat(out).detach())
+    assert torch.equal(res[0], res[1]) and float(res[0].abs().min()) > 0
+    for p, b, n in zip(plain, bases, (25, 25, 25, 15)):
+        assert b.grad is not None and b.grad.shape == b.shape
+        assert float(b.grad[:, n:].abs().max()) == 0.0
+        assert torch.equal(b.grad[:, :n], p.grad)

@@ -207,3 +207,41 @@ def test_fused_smpl_losses_vs_reference_golden_and_tensor_ops():
     for k, gk in (('smpl_pose', 'loss_pose'), ('joint_rotation0', 'loss_pose'), ('smpl_betas', 'loss_betas'), ('keypoints_3d', 'loss_kp3d'),
                   ('smpl_verts', 'loss_verts'), ('joint_position0', 'loss_l1')):
         np.testing.assert_allclose(float(out[k]), float(g[gk]), rtol=1e-5, err_msg=k)
+
+
+def test_padded_base_hand_over_is_bit_equal_to_plain_heads():
+    """B = 2, S = 12 (144 pixels: no multiple of 256): iuv_global on leaf [B,25|15,S,S] heads and on [:, :25] / [:, :15] views carrying
+    the `_padded_base` of leaf NHWC [B,32|16,S,S] buffers (same values, zeros behind): losses, map and argmax plane bit-equal, the
+    gradient on the base at full width with exactly zero pad channels and its leading channels bit-equal -- both runs feed the kernels
+    the same row buffers, and the kernels accumulate order-independently."""
+    from danet_densepose2smpl_amd import iuv_ops
+    _cfg()
+    B, S = 2, 12
+    gen = torch.Generator().manual_seed(9)
+    heads = [torch.randn(B, c, S, S, generator=gen).cuda() for c in (25, 25, 25, 15)]
+    part = torch.randint(0, 25, (B, 1, S, S), generator=gen).float() / 24.
+    gt = torch.cat([part, torch.rand(B, 2, S, S, generator=gen)], 1).cuda()
+    w = torch.tensor([1., 0.5]).cuda()
+    keep = (torch.rand(B, 25, generator=gen) > 0.3).float().cuda()
+    keep[:, 0] = 1
+    gmap = torch.randn(B, 80, S, S, generator=gen).cuda()
+    scales = ((0.7, 0.), (1.3, 0.), (1., float(S * S)), (0.4, float(S * S)))
+    plain = [t.clone().requires_grad_(True) for t in heads]
+    bases = [torch.nn.functional.pad(t.permute(0, 2, 3, 1), (0, ld - t.shape[1])).permute(0, 3, 1, 2).requires_grad_(True)
+             for t, ld in zip(heads, (32, 32, 32, 16))]
+    views = []
+    for b, t in zip(bases, heads):
+        v = b[:, :t.shape[1]]
+        v._padded_base = b
+        views.append(v)
+    res = []
+    for ins in (plain, views):
+        losses, mp, am = iuv_ops.iuv_global(*ins, gt, w, keep, scales=scales)
+        (sum(o * c for o, c in zip(losses, (1., 2., 3., 4.))).sum() + (mp.float() * gmap).sum()).backward()
+        res.append((torch.cat(losses).detach(), mp.detach(), am))
+    assert torch.equal(res[0][0], res[1][0]) and float(res[0][0].abs().min()) > 0
+    assert torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][2], res[1][2])
+    for p, b, n in zip(plain, bases, (25, 25, 25, 15)):
+        assert b.grad is not None and b.grad.shape == b.shape
+        assert float(b.grad[:, n:].abs().max()) == 0.0
+        assert torch.equal(b.grad[:, :n], p.grad)

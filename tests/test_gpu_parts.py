@@ -228,3 +228,42 @@ def test_part_joint_equals_the_two_separate_ops(with_keep, with_w, S):
             assert torch.equal(res[0][2], res[1][2])                       # one consumer: the same kernel as the separate op
         gr = res[1][2].permute(0, 2, 3, 1).reshape(B, S, S, 24, 24)
         assert float(gr[..., 21:].abs().max()) == 0.0
+
+
+def test_part_joint_unpadded_layout_with_both_consumers():
+    """PartJointFunction.backward on the 21-channel layout with x24 AND the losses live (two kernels and an add) == part_clean +
+    part_losses with autograd's add: x24, the three finished losses and d pred bit for bit -- both paths form ONE bf16 add of the same
+    two kernel outputs, and IEEE addition commutes.  B = 2, S = 12: H * W = 144 is no multiple of 256 (ragged last tile)."""
+    from danet_densepose2smpl_amd import part_ops
+    from danet_densepose2smpl_amd.iuv_estimator import DP2SMPL_MAPPING
+    B, S = 2, 12
+    pred, keep = _inputs(B, S, 21, True)
+    g = torch.Generator().manual_seed(5)
+    img = torch.stack([torch.randint(0, 25, (B, S, S), generator=g).float() / 24., torch.rand(B, S, S, generator=g),
+                       torch.rand(B, S, S, generator=g)], 1).cuda()
+    theta = torch.zeros(B, 24, 2, 3)
+    theta[:, :, 0, 0] = theta[:, :, 1, 1] = 0.6
+    theta[:, :, :, 2] = torch.rand(B, 24, 2, generator=g) - 0.5
+    theta = theta.cuda()
+    w = torch.tensor([1., 0.5]).cuda()
+    sel = torch.tensor(DP2SMPL_MAPPING, dtype=torch.long).cuda()
+    scales = ((0.3, 0.), (0.7, 0.), (1., 24. * S * S))
+    gx = torch.randn(B * 24, 24, S, S, generator=g).cuda().bfloat16()
+    cw = torch.tensor([1.3, 0.4, 2.0]).cuda()
+    res = []
+    for joint in (False, True):
+        p = pred.clone().requires_grad_(True)
+        assert p.shape[1] == 504
+        if joint:
+            x24, lU, lV, lI = part_ops.part_joint(p, keep, img, theta, w, sel, True, scales)
+        else:
+            _, x24 = part_ops.part_clean(p, keep)
+            lU, lV, lI = part_ops.part_losses(p, img, theta, w, sel, True, scales=scales)
+        ((x24.float() * gx.float()).sum() + lU.sum() * cw[0] + lV.sum() * cw[1] + lI.sum() * cw[2]).backward()
+        res.append((x24.detach(), torch.cat([lU, lV, lI]).detach(), p.grad))
+    assert res[0][2].dtype == torch.bfloat16 and float(res[0][2].float().abs().max()) > 0
+    assert torch.equal(res[0][0], res[1][0])
+    assert torch.equal(res[0][1], res[1][1])
+    d = (res[1][2].float() - res[0][2].float()).abs().max()
+    print('max |d grad| %.3e of %.3e' % (float(d), float(res[0][2].float().abs().max())))
+    assert torch.equal(res[0][2], res[1][2])
