@@ -16,6 +16,7 @@ import torch
 from . import iuvmap, ops
 from ._lib import require_gpu
 from .iuv_estimator import DP2SMPL_MAPPING
+from .smpl import from_para
 
 
 def mesh_of(out, smpl):
@@ -23,8 +24,7 @@ def mesh_of(out, smpl):
     para = out['para']
     verts = out.get('vertices')
     if verts is None:
-        rot = para[:, 13:].contiguous().view(-1, 24, 3, 3)
-        verts = smpl(betas=para[:, 3:13].contiguous(), body_pose=rot[:, 1:], global_orient=rot[:, 0].unsqueeze(1), pose2rot=False).vertices
+        verts = from_para(smpl, para).vertices
     return verts.detach(), para[:, 0:3].contiguous()
 
 

@@ -19,6 +19,7 @@ import torch
 
 from . import augment, constants, ops
 from ._lib import GPU_ONLY, require_gpu
+from .smpl import from_para
 
 POSE_DATASETS = ('h36m-p1', 'h36m-p2', '3dpw', 'mpi-inf-3dhp')
 DATASETS = POSE_DATASETS + ('lsp',)
@@ -177,10 +178,9 @@ class Evaluator(object):
         B = para.shape[0]
         cam = para[:, 0:3].clone()                                                 # (an engine's `para` is a static buffer)
         betas = para[:, 3:13].clone()
-        rotmat = para[:, 13:].contiguous().view(B, 24, 3, 3)
         with torch.no_grad():
-            verts = self.smpl_neutral(betas=betas, body_pose=rotmat[:, 1:], global_orient=rotmat[:, 0].unsqueeze(1), pose2rot=False).vertices
-            self._pose.append(ops.rotmat_to_angle_axis(rotmat).view(B, 72))         # eval.py:175-181
+            verts = from_para(self.smpl_neutral, para).vertices
+            self._pose.append(ops.rotmat_to_angle_axis(para[:, 13:]).view(B, 72))   # eval.py:175-181
             self._betas.append(betas)
             self._cam.append(cam)
             self._names += [str(n) for n in batch.get('imgname', [''] * B)]
@@ -449,13 +449,24 @@ def write_synthetic_dataset(root, dataset_name, n=8, seed=0):
 
 
 # ---- the loop ----------------------------------------------------------------------------------------------------------------------
-def _model_parts(model):
-    """(callable image -> dict with 'para', the DaNet behind it)."""
+def eval_target(model):
+    """-> (callable image -> dict with 'para', the DaNet behind it, its device); a model on the CPU is refused."""
     if hasattr(model, 'infer_net'):
-        return model.infer_net, model
-    if hasattr(model, 'model') and hasattr(model.model, 'iuv2smpl') and callable(model):
-        return model, model.model                                                  # an InferenceEngine
-    raise TypeError('run_evaluation: model must be a DaNet or an InferenceEngine, got %s' % type(model).__name__)
+        infer, net = model.infer_net, model
+    elif hasattr(model, 'model') and hasattr(model.model, 'iuv2smpl') and callable(model):
+        infer, net = model, model.model                                            # an InferenceEngine
+    else:
+        raise TypeError('run_evaluation: model must be a DaNet or an InferenceEngine, got %s' % type(model).__name__)
+    device = next(net.parameters()).device
+    if device.type != 'cuda':
+        raise RuntimeError(GPU_ONLY % ('run_evaluation model', device))
+    return infer, net, device
+
+
+def eval_batches(dataset, device, result_file, batch_size, img_res, num_workers, shuffle):
+    """The loop's batches on the device; in dataset order when a result file is written (eval.py:81-83, eval_coco.py:61-63)."""
+    for host in iterate_batches(dataset, batch_size, shuffle and result_file is None, num_workers):
+        yield to_device(host, device, img_res)
 
 
 def val_due(step_count, test_steps):
@@ -471,10 +482,7 @@ def run_evaluation(model, dataset_name, dataset, result_file, batch_size=32, img
     options.eval_pve adds the per-vertex errors (Evaluator).  Prints the reference's lines (verbose=False: nothing, for use inside
     Trainer.fit) and returns the summary dict; with `result_file` writes pred_joints, pose, betas, camera."""
     plan = dataset_plan(dataset_name)
-    infer, net = _model_parts(model)
-    device = next(net.parameters()).device
-    if device.type != 'cuda':
-        raise RuntimeError(GPU_ONLY % ('run_evaluation model', device))
+    infer, net, device = eval_target(model)
     opt = lambda k: getattr(options, k, None) if options is not None else None
     smpl = net.iuv2smpl.smpl
     Jr = opt('J_regressor')
@@ -486,10 +494,7 @@ def run_evaluation(model, dataset_name, dataset, result_file, batch_size=32, img
     if plan['eval_masks'] and renderer is None:
         renderer = synthetic_part_renderer(smpl.faces)
     ev = Evaluator(dataset_name, Jr, smpl, opt('smpl_male') or smpl, opt('smpl_female') or smpl, renderer, eval_pve=bool(opt('eval_pve')))
-    if result_file is not None:
-        shuffle = False                                                            # eval.py:81-83
-    for step, host in enumerate(iterate_batches(dataset, batch_size, shuffle, num_workers)):
-        batch = to_device(host, device, img_res)
+    for step, batch in enumerate(eval_batches(dataset, device, result_file, batch_size, img_res, num_workers, shuffle)):
         out = infer(batch['img'])
         ev.update(batch, out['para'])
         if verbose and log_freq and step % log_freq == log_freq - 1:

@@ -25,7 +25,8 @@ import torch
 
 from . import constants, ops
 from ._lib import GPU_ONLY, require_gpu
-from .evaluate import EvalDataset, _model_parts, iterate_batches, to_device     # noqa: F401  (EvalDataset: re-exported)
+from .evaluate import EvalDataset, eval_batches, eval_target, iterate_batches, to_device     # noqa: F401  (re-exported)
+from .smpl import from_para
 
 STAT_NAMES = ['AP', 'Ap .5', 'AP .75', 'AP (M)', 'AP (L)', 'AR', 'AR .5', 'AR .75', 'AR (M)', 'AR (L)']     # coco_keypoint_dataset.py:438
 IOU_THRS = np.linspace(.5, 0.95, 10)
@@ -193,11 +194,9 @@ class CocoEvaluator(object):
         require_gpu(para, 'CocoEvaluator.update')
         B = para.shape[0]
         para = para.detach().clone()                                               # (an engine's `para` is a static buffer)
-        rotmat = para[:, 13:].contiguous().view(B, 24, 3, 3)
         center, scale = batch['center'].to(self.device), batch['scale'].to(self.device).reshape(B)
         with torch.no_grad():
-            joints = self.smpl(betas=para[:, 3:13].contiguous(), body_pose=rotmat[:, 1:], global_orient=rotmat[:, 0].unsqueeze(1), pose2rot=False).joints
-            preds = ops.coco_keypoints(joints, para[:, 0:3].contiguous(), center, scale, self.img_res, self.focal_length)
+            preds = ops.coco_keypoints(from_para(self.smpl, para).joints, para[:, 0:3].contiguous(), center, scale, self.img_res, self.focal_length)
         self._preds.append(preds)
         self._para.append(para)
         self._center.append(center)
@@ -252,19 +251,13 @@ def run_evaluation(model, dataset, result_file, batch_size=32, img_res=224, num_
         raise NotImplementedError("regressor 'hmr': there is no HMR regressor in this package (DESIGN.md section 8); use 'danet'")
     if regressor != 'danet':
         raise ValueError("unknown regressor %r ('danet')" % (regressor,))
-    infer, net = _model_parts(model)
-    device = next(net.parameters()).device
-    if device.type != 'cuda':
-        raise RuntimeError(GPU_ONLY % ('run_evaluation model', device))
+    infer, net, device = eval_target(model)
     gt = opt('keypoint_json')
     if gt is None:
         raise ValueError('run_evaluation: options.keypoint_json (the person_keypoints_*.json of the images) is required')
     ev = CocoEvaluator(gt, net.iuv2smpl.smpl, img_res)
-    if result_file is not None:
-        shuffle = False                                                            # eval_coco.py:61-63
     print('dataset length: {}'.format(len(dataset)))
-    for host in iterate_batches(dataset, batch_size, shuffle, num_workers):
-        batch = to_device(host, device, img_res)
+    for batch in eval_batches(dataset, device, result_file, batch_size, img_res, num_workers, shuffle):
         ev.update(batch, infer(batch['img'])['para'])
     s = ev.summary()
     r = s['results']

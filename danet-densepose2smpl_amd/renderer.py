@@ -1,11 +1,40 @@
 """IUV_Renderer with the reference's call signature (/root/reference/utils/renderer.py:202-298).
 The rasterisation (neural_renderer in the reference) is the HIP kernel of csrc/iuv_raster.hip.  MeshRenderer is the shaded
 view of /root/reference/utils/renderer.py:125-199 (opendr there) on the same rasteriser plus csrc/vis_ops.hip."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 
 from . import assets, ops
 from ._lib import require_gpu
+
+
+class DeviceTables(dict):
+    """What a renderer uploads once: tables(key, build) -> build(), made at the first call with `key` (the device, as a string,
+    plus any extra such as the vertex count) and kept."""
+
+    def tables(self, key, build):
+        if key not in self:
+            self[key] = build()
+        return self[key]
+
+
+def upload(a, device):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def fill_back(faces):
+    """Every face also with the opposite winding, [F,3] -> [2F,3] int32 (the rasteriser culls faces of non-positive signed area)."""
+    faces = np.asarray(faces).reshape(-1, 3)
+    return np.concatenate([faces, faces[:, ::-1]], 0).astype(np.int32)
+
+
+def plain_tables(num_verts, num_faces, device):
+    """What the rasteriser takes where a mesh is drawn as it is and only coverage, face index and depth are read: (the identity
+    vertex mapping [num_verts] int32, a zero colour per face [num_faces,3] f32); a count of None leaves that half out (None)."""
+    return (None if num_verts is None else torch.arange(num_verts, dtype=torch.int32, device=device),
+            None if num_faces is None else torch.zeros(num_faces, 3, dtype=torch.float32, device=device))
 
 
 class IUV_Renderer(object):
@@ -28,16 +57,11 @@ class IUV_Renderer(object):
         self.vert_mapping = torch.from_numpy(vm.astype(np.int64))
         self.faces = torch.from_numpy(faces[None, :, :])
         self.textures = torch.from_numpy(tex[None, :, None, None, None, :])
-        self._tables = {}
         self._np = (vm, faces, tex)
+        self._cache = DeviceTables()
 
     def _dev(self, device):
-        key = str(device)
-        if key not in self._tables:
-            vm, faces, tex = self._np
-            self._tables[key] = (torch.from_numpy(vm).to(device), torch.from_numpy(faces).contiguous().to(device),
-                                 torch.from_numpy(tex).contiguous().to(device))
-        return self._tables[key]
+        return self._cache.tables(str(device), lambda: tuple(upload(a, device) for a in self._np))
 
     def verts2uvimg(self, verts, cam, return_aux=False):
         """verts [B,6890,3], cam [B,3] (s,x,y) -> IUV image [B,3,out,out]."""
@@ -75,17 +99,13 @@ class PartRenderer(object):
         self.faces = torch.from_numpy(faces)
         self.textures = torch.from_numpy(tex)
         self.cube_parts = torch.as_tensor(np.asarray(cube_parts), dtype=torch.float32)
-        # fill_back: every face also with the opposite winding (the rasteriser culls faces of non-positive signed area)
-        self._np = (np.concatenate([faces, faces[:, ::-1]], 0).astype(np.int32).copy(), np.concatenate([tex, tex], 0).copy())
-        self._tables = {}
+        self._np = (fill_back(faces), np.concatenate([tex, tex], 0))
+        self._cache = DeviceTables()
 
     def _dev(self, device, nv):
-        key = (str(device), nv)
-        if key not in self._tables:
-            f2, t2 = self._np
-            self._tables[key] = (torch.arange(nv, dtype=torch.int32, device=device), torch.from_numpy(f2).contiguous().to(device),
-                                 torch.from_numpy(t2).contiguous().to(device), self.cube_parts.to(device))
-        return self._tables[key]
+        f2, t2 = self._np
+        return self._cache.tables((str(device), nv), lambda: (plain_tables(nv, None, device)[0], upload(f2, device), upload(t2, device),
+                                                         self.cube_parts.to(device)))
 
     def get_parts(self, parts, mask):
         """part_utils.py:27-35: rendered colours [B,3,H,W] + mask [B,H,W] -> part indices [B,H,W] (long)."""
@@ -126,6 +146,8 @@ def vertex_face_csr(faces, num_verts):
 LIGHT_POSITIONS = ((-200., -100., -100.), (800., 10., 300.), (-500., 500., 1000.))      # renderer.py:160-184, before rotateY(120 deg)
 LIGHT_COLORS = ((1., 1., 1.), (1., 1., 1.), (.7, .7, .7))
 ALBEDO = 0.9
+# MeshRenderer.tables: identity vertex mapping, faces, fill_back(faces), vertex_face_csr's two arrays, the rasteriser's unused colours
+MeshTables = namedtuple('MeshTables', ['vert_mapping', 'faces', 'faces2', 'csr_off', 'csr_face', 'tex'])
 
 
 class MeshRenderer(object):
@@ -147,23 +169,21 @@ class MeshRenderer(object):
         pos = [rotateY(np.array(p), np.radians(120)) for p in LIGHT_POSITIONS]
         self.lights = [float(x) for p in pos for x in p] + [float(x) for c in cols for x in c]
         self._faces_np = faces
-        self._tables = {}
+        self._cache = DeviceTables()
 
-    def _dev(self, device, nv):
-        key = (str(device), nv)
-        if key not in self._tables:
+    def tables(self, device, nv):
+        """-> MeshTables on `device` for a mesh of `nv` vertices, made once."""
+        def build():
             f = self._faces_np
             off, inc = vertex_face_csr(f, nv)
-            f2 = np.concatenate([f, f[:, ::-1]], 0).astype(np.int32).copy()             # fill_back, as PartRenderer
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            self._tables[key] = (torch.arange(nv, dtype=torch.int32, device=device), t(f), t(f2), t(off), t(inc),
-                                 torch.zeros(f2.shape[0], 3, dtype=torch.float32, device=device))
-        return self._tables[key]
+            vm, tex = plain_tables(nv, 2 * f.shape[0], device)
+            return MeshTables(vm, upload(f, device), upload(fill_back(f), device), upload(off, device), upload(inc, device), tex)
+        return self._cache.tables((str(device), nv), build)
 
     def __call__(self, vertices, cam, images=None, rot_y=0.):
         require_gpu(vertices, 'MeshRenderer')
         R = self.img_res
-        vm, f, f2, off, inc, tex = self._dev(vertices.device, vertices.shape[1])
-        ws, rverts = ops.mesh_shade_vertices(vertices, f, off, inc, self.lights, rot_y, ALBEDO)
-        _, fidx, _ = ops.iuv_raster(rverts, cam, vm, f2, tex, self.focal_length, R, R, return_aux=True)
-        return ops.mesh_shade_pixels(ws, cam, vertices.shape[1], f2, fidx, images, self.focal_length, R)
+        t = self.tables(vertices.device, vertices.shape[1])
+        ws, rverts = ops.mesh_shade_vertices(vertices, t.faces, t.csr_off, t.csr_face, self.lights, rot_y, ALBEDO)
+        _, fidx, _ = ops.iuv_raster(rverts, cam, t.vert_mapping, t.faces2, t.tex, self.focal_length, R, R, return_aux=True)
+        return ops.mesh_shade_pixels(ws, cam, vertices.shape[1], t.faces2, fidx, images, self.focal_length, R)

@@ -17,6 +17,7 @@ import torch
 from . import constants, datasets, ops
 from ._lib import GPU_ONLY
 from .renderer import ALBEDO, MeshRenderer
+from .smpl import from_para
 
 
 # ---- boxes -----------------------------------------------------------------------------------------------------------------------
@@ -184,10 +185,7 @@ class SceneDemo(object):
         return torch.cat(paras, 0)
 
     def vertices(self, para):
-        P = para.shape[0]
-        rot = para[:, 13:].contiguous().view(P, 24, 3, 3)
-        with torch.no_grad():
-            return self.smpl(betas=para[:, 3:13].contiguous(), body_pose=rot[:, 1:], global_orient=rot[:, :1], pose2rot=False).vertices.detach()
+        return from_para(self.smpl, para).vertices.detach()
 
     def render(self, para, plan, return_aux=False, vertices=None):
         """para [P,229] -> the rendered frames as one packed uint8 tensor in the plan's layout (with return_aux: also ids and depth
@@ -202,12 +200,12 @@ class SceneDemo(object):
                                     plan['d_src'], plan['d_offsets'], plan['d_shapes'], return_aux=return_aux, host=host)
         verts = self.vertices(para) if vertices is None else vertices
         V = verts.shape[1]
-        _, f, f2, off, inc, _ = self.mesh._dev(self.device, V)
-        ws, rverts = ops.mesh_shade_vertices(verts, f, off, inc, self.mesh.lights, 0., ALBEDO)
-        vcol = ws[P * V * 3:].view(P, V, 3)
+        t = self.mesh.tables(self.device, V)
+        ws, _ = ops.mesh_shade_vertices(verts, t.faces, t.csr_off, t.csr_face, self.mesh.lights, 0., ALBEDO)
+        rverts, vcol = ops.mesh_shade_views(ws, P, V)
         cam = para[:, 0:3].detach().float()
         cam_t = torch.stack([cam[:, 1], cam[:, 2], (2.0 * self.focal) / (self.res * cam[:, 0] + 1e-9)], 1)
-        return ops.scene_render(rverts, vcol, f2, cam_t, plan['d_proj'], plan['d_dscale'], plan['d_person_frame'], plan['d_src'],
+        return ops.scene_render(rverts, vcol, t.faces2, cam_t, plan['d_proj'], plan['d_dscale'], plan['d_person_frame'], plan['d_src'],
                                 plan['d_offsets'], plan['d_shapes'], return_aux=return_aux, host=host)
 
     def __call__(self, frames, boxes):

@@ -86,3 +86,10 @@ class SMPL(nn.Module):
             joints_J19 = joints[:, -24:, :][:, self.j24_to_j19, :]   # (models/smpl.py:36-37)
         return ModelOutput_(vertices=vertices, global_orient=global_orient, body_pose=body_pose, joints=joints,
                             joints_J19=joints_J19, smpl_joints=smpl_joints, betas=betas, full_pose=full_pose)
+
+
+def from_para(smpl, para):
+    """The layer's output for parameter rows para [B,229] = (camera 3, betas 10, 24 rotation matrices), without gradients."""
+    rot = para[:, 13:].contiguous().view(-1, 24, 3, 3)
+    with torch.no_grad():
+        return smpl(betas=para[:, 3:13].contiguous(), body_pose=rot[:, 1:], global_orient=rot[:, :1], pose2rot=False)

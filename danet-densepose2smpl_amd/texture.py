@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import assets, ops
-from ._lib import require_gpu
+from .renderer import DeviceTables, plain_tables, upload
 
 PARTS = 24
 SHEET_ROWS, SHEET_COLS = 4, 6
@@ -83,47 +83,42 @@ class TextureAtlas(object):
             densepose = assets.make_synthetic_densepose(smpl_model, 0)
         self.tables = atlas_tables(densepose)
         self.num_verts = int(self.tables['vert_mapping'].max()) + 1           # the mesh must have at least this many vertices
-        self._dev_tables = {}
+        self._cache = DeviceTables()
 
     def _dev(self, device):
         """The tables and the texel map on `device`, made once."""
-        key = str(device)
-        if key not in self._dev_tables:
-            d = {k: torch.from_numpy(a).to(device) for k, a in self.tables.items()}
-            F = d['faces'].shape[0]
-            d['tex'] = torch.zeros(F, 3, dtype=torch.float32, device=device)            # (the rasteriser's colours are not used)
+        def build():
+            d = {k: upload(a, device) for k, a in self.tables.items()}
+            d['tex'] = plain_tables(None, d['faces'].shape[0], device)[1]                    # (the rasteriser's colours are not used)
             d['no_faces'] = torch.zeros(1, 3, dtype=torch.int32, device=device)
-            d['csr_off'] = {}                                                           # per vertex count: an empty vertex -> face table
             d['csr_face'] = torch.zeros(1, dtype=torch.int32, device=device)
             d['map_face'], d['map_bary'] = ops.texture_map(d['uv'], d['faces'], d['part_off'], d['part_faces'], self.size)
-            self._dev_tables[key] = d
-        return self._dev_tables[key]
+            return d
+        return self._cache.tables(str(device), build)
 
     def texel_map(self, device):
         """-> (face [24,T,T] int32, bary [24,T,T,2] f32) on `device`."""
         d = self._dev(device)
         return d['map_face'], d['map_bary']
 
-    def _check_mesh(self, what, vertices, cam):
-        require_gpu(vertices, what)
-        if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[1] < self.num_verts or tuple(cam.shape) != (vertices.shape[0], 3):
-            raise ValueError('%s: vertices %s, cam %s (the topology names %d mesh vertices)' % (what, tuple(vertices.shape), tuple(cam.shape), self.num_verts))
+    def _check_mesh(self, what, vertices):
+        if vertices.shape[1] < self.num_verts:
+            raise ValueError('%s: vertices %s (the topology names %d mesh vertices)' % (what, tuple(vertices.shape), self.num_verts))
 
     def unwrap(self, images, vertices, cam, view_offsets=None, depth_tol=0.02, min_cos=0.1):
         """images [N,3,H,H] in [0,1], vertices [N,NV,3], cam [N,3] (s, tx, ty) -> atlas [P,24,T,T,4].  view_offsets: host integers
         [P+1], the views of person p being view_offsets[p] .. view_offsets[p+1] - 1 (None: every view is a person of its own).  A
         texel no view observes, and every texel of a person without views, is 0."""
-        self._check_mesh('texture unwrap', vertices, cam)
-        if images.dim() != 4 or images.shape[0] != vertices.shape[0] or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
-            raise ValueError('texture unwrap: images %s, expected square [%d,3,H,H]' % (tuple(images.shape), vertices.shape[0]))
-        N, H = images.shape[0], images.shape[2]
+        img, v, c = ops.texture_views(images, vertices, cam, 'texture_unwrap')             # (every refusal comes before the first launch)
+        self._check_mesh('texture unwrap', v)
+        N, H = img.shape[0], img.shape[2]
         off = ops.texture_view_offsets(view_offsets, N)
-        d = self._dev(vertices.device)
+        d = self._dev(v.device)
         if N:
-            _, _, depth = ops.iuv_raster(vertices, cam, d['vert_mapping'], d['faces'], d['tex'], self.focal_length, H, H, return_aux=True)
+            _, _, depth = ops.iuv_raster(v, c, d['vert_mapping'], d['faces'], d['tex'], self.focal_length, H, H, return_aux=True)
         else:
-            depth = torch.empty(0, H, H, device=vertices.device, dtype=torch.float32)
-        return ops.texture_unwrap(images, vertices, cam, depth, off, d['vert_mapping'], d['faces'], d['map_face'], d['map_bary'],
+            depth = torch.empty(0, H, H, device=v.device, dtype=torch.float32)
+        return ops.texture_unwrap(img, v, c, depth, off, d['vert_mapping'], d['faces'], d['map_face'], d['map_bary'],
                                   self.focal_length, depth_tol, min_cos)
 
     def render(self, vertices, cam, atlas, images=None, rot_y=0., atlas_index=None, fill=(0.5, 0.5, 0.5), img_res=None):
@@ -131,21 +126,20 @@ class TextureAtlas(object):
         images `img_res` (default 224).  rot_y (radians) turns the body as MeshRenderer does; atlas_index: host integers [N]
         naming the person whose atlas a view draws (None: view n draws atlas n); a pixel whose chart region nothing was
         unwrapped to is `fill`; a pixel no face covers is the image's (or 0) with alpha 0."""
-        self._check_mesh('texture render', vertices, cam)
-        N, NV = vertices.shape[0], vertices.shape[1]
-        if not torch.is_tensor(atlas) or atlas.dim() != 5 or tuple(atlas.shape[1:]) != (PARTS, self.size, self.size, 4) or atlas.shape[0] < 1:
+        img, v, c = ops.texture_views(images, vertices, cam, 'texture_render', optional=True)
+        self._check_mesh('texture render', v)
+        N, NV = v.shape[0], v.shape[1]
+        _, P, T = ops.texture_atlas(atlas)
+        if T != self.size:
             raise ValueError('texture render: atlas %s, expected [P,%d,%d,%d,4]' % (tuple(atlas.shape), PARTS, self.size, self.size))
-        idx = ops.texture_atlas_index(atlas_index, N, atlas.shape[0])
-        if images is not None and (images.dim() != 4 or tuple(images.shape[:2]) != (N, 3) or images.shape[2] != images.shape[3]):
-            raise ValueError('texture render: images %s, expected square [%d,3,S,S]' % (tuple(images.shape), N))
-        S = int(images.shape[2] if images is not None else (224 if img_res is None else img_res))
-        d = self._dev(vertices.device)
-        if NV not in d['csr_off']:
-            d['csr_off'][NV] = torch.zeros(NV + 1, dtype=torch.int32, device=vertices.device)
+        idx = ops.texture_atlas_index(atlas_index, N, P)
+        S = int(img.shape[2] if img is not None else (224 if img_res is None else img_res))
+        d = self._dev(v.device)
+        csr_off = self._cache.tables((str(v.device), NV), lambda: torch.zeros(NV + 1, dtype=torch.int32, device=v.device))
         # the rotation is MeshRenderer's vertex launch with an empty vertex -> face table (its colours are not used)
-        _, rverts = ops.mesh_shade_vertices(vertices, d['no_faces'], d['csr_off'][NV], d['csr_face'], (0.,) * 18, rot_y, 0.)
-        _, fidx, _ = ops.iuv_raster(rverts, cam, d['vert_mapping'], d['faces'], d['tex'], self.focal_length, S, S, return_aux=True)
-        return ops.texture_render(rverts, cam, d['vert_mapping'], d['faces'], d['uv'], d['face_part'], fidx, atlas, idx, images,
+        _, rverts = ops.mesh_shade_vertices(v, d['no_faces'], csr_off, d['csr_face'], (0.,) * 18, rot_y, 0.)
+        _, fidx, _ = ops.iuv_raster(rverts, c, d['vert_mapping'], d['faces'], d['tex'], self.focal_length, S, S, return_aux=True)
+        return ops.texture_render(rverts, c, d['vert_mapping'], d['faces'], d['uv'], d['face_part'], fidx, atlas, idx, img,
                                   self.focal_length, fill)
 
     def sheet(self, atlas):

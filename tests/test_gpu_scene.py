@@ -156,7 +156,7 @@ def test_scene_coverage_equals_mesh_renderer_at_224(smpl_model):
     _, tinv = datasets.crop_transforms(np.array([[112., 112.]]), np.array([1.12]), np.zeros(1), 224)
     assert np.abs(tinv[0] - np.eye(3)).max() < 1e-12
     k = scene.person_cameras(cam.astype(np.float64), tinv, [[224, 224]], [0], 224)
-    _, f, f2, off, inc, _ = rend._dev(v.device, verts.shape[1])
+    _, f, f2, off, inc, _ = rend.tables(v.device, verts.shape[1])
     ws, rverts = ops.mesh_shade_vertices(v, f, off, inc, rend.lights, 0., ALBEDO)
     V = verts.shape[1]
     vcol = ws[V * 3:].view(1, V, 3)

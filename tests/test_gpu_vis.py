@@ -209,7 +209,7 @@ def test_mesh_vs_fp64_oracle_every_covered_pixel(mesh32, smpl_model):
     meas = {}
     for name, rot, img in (('front', 0., images), ('side', math.radians(90), None)):
         rgb, alpha = rend(v, c, img, rot_y=rot)
-        vm, f, f2, off, inc, tex = rend._dev(v.device, v.shape[1])
+        vm, f, f2, off, inc, tex = rend.tables(v.device, v.shape[1])
         _, rverts = ops.mesh_shade_vertices(v, f, off, inc, rend.lights, rot)
         _, fidx, _ = ops.iuv_raster(rverts, c, vm, f2, tex, 5000., 224, 224, return_aux=True)
         fidx = fidx.cpu().numpy()
