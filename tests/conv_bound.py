@@ -1,5 +1,6 @@
 """The rounding bound the convolution-epilogue tests check against (tests/test_gpu_infer.py, tests/test_gpu_infer_layers.py,
-tests/test_infer_fold.py).  Not a test module: a helper the three import.
+tests/test_infer_fold.py) and, with reference_dgrad / reference_wgrad / int_operands, the backward-pass tests
+(tests/test_gpu_conv_grad.py, tests/test_conv_bound_host.py).  Not a test module: a helper they import.
 
 A launch computes y = round(relu(acc + b[c] + res)) with acc = conv(x, Wq) accumulated in fp32 over exact products of its operands and
 round() the output type's round-to-nearest.  With r the same expression evaluated in fp64 on the same operands (`reference`),
@@ -54,6 +55,45 @@ def reference(x, w, b=None, res=None, relu=False, stride=1, pad=0, dil=1, groups
     if relu:
         r = F.relu(r)
     return Reference(r, r_conv, S, K, res, bool(relu))
+
+
+def reference_dgrad(x_shape, w, gy, stride=1, pad=0, dil=1, groups=1, addend=None):
+    """The backward pass's data gradient (tests/test_gpu_conv_grad.py): fp64 d conv2d(x, w) / dx applied to gy, plus `addend` (the
+    residual branch's gradient, fused into the epilogue), on the operands as given.  w: the forward weight [Cout, Cin/groups, R, S],
+    gy [B, Cout, OH, OW], x_shape = (B, Cin, H, W).  K = Cout/groups * R * S bounds the dot-product length from above: at stride s an
+    input pixel meets only the taps of its parity class, about K / s^2 of them, so the accumulation term -- the small one -- is up to
+    s times too generous, never too tight."""
+    w, gy = w.double(), gy.double()
+    fn = lambda ww, gg: torch.nn.grad.conv2d_input(tuple(x_shape), ww, gg, stride, pad, dil, groups)
+    r_conv = fn(w, gy)
+    S = fn(w.abs(), gy.abs())
+    K = w.shape[0] // groups * w.shape[2] * w.shape[3]
+    r = r_conv
+    if addend is not None:
+        addend = addend.double()
+        r = r + addend
+        S = S + addend.abs()
+    return Reference(r, r_conv, S, K, addend, False)
+
+
+def reference_wgrad(x, gy, w_shape, stride=1, pad=0, dil=1, groups=1):
+    """The weight gradient: fp64 d conv2d(x, w) / dw applied to gy, [Cout, Cin/groups, R, S] (for `ratios` its "channels" are dim 1,
+    the input channels of a group); K = B * OH * OW, the pixels every element sums over."""
+    x, gy = x.double(), gy.double()
+    fn = lambda xx, gg: torch.nn.grad.conv2d_weight(xx, tuple(w_shape), gg, stride, pad, dil, groups)
+    r = fn(x, gy)
+    S = fn(x.abs(), gy.abs())
+    return Reference(r, r, S, gy.shape[0] * gy.shape[2] * gy.shape[3], None, False)
+
+
+def int_operands(shape, lo, hi, generator):
+    """Integers of [lo, hi] as an fp32 tensor; |values| <= 256, so each one is a bf16 number (8 significant bits) and sums of products
+    of such operands are exact in fp32, in any order, as long as they stay below 2^24."""
+    if not -256 <= lo <= hi <= 256:
+        raise ValueError('int_operands: [%d, %d] is not exactly representable in bf16' % (lo, hi))
+    t = torch.randint(lo, hi + 1, tuple(shape), generator=generator).float()
+    assert torch.equal(t.bfloat16().float(), t)
+    return t
 
 
 def rounded(ref, u, rounded_conv=False):
