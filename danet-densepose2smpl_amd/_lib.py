@@ -330,6 +330,18 @@ def knobs(**settings):
             L.knob(k, v)
 
 
+@contextlib.contextmanager
+def scoped(owner, name, value):
+    """`owner.name = value` for the duration of a `with` block; what was found there is put back on every exit, an exception
+    included.  The modules that own a step global build their scope from this (conv.grad_store, nn.onepass_blocks, ...)."""
+    found = getattr(owner, name)
+    setattr(owner, name, value)
+    try:
+        yield
+    finally:
+        setattr(owner, name, found)
+
+
 def lib():
     """Load the shared library (once).  Raises if it has not been built."""
     global _lib

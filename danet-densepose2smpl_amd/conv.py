@@ -7,6 +7,7 @@ through the wgrad kernel (fp32), dbias as a channel sum.
 """
 import contextlib
 import os
+import sys
 import weakref
 from collections import namedtuple
 
@@ -16,6 +17,8 @@ import torch.nn.functional as F  # noqa: F401  (only for nn.init helpers / shape
 
 from . import _lib
 from ._lib import ptr, check, stream, f32c
+
+_THIS = sys.modules[__name__]       # (the owner the scopes of this module's step globals name: _lib.scoped)
 
 _PACK_CACHE = {}
 
@@ -359,7 +362,15 @@ class WeightBank(object):
         self.jobs = None
 
     def start_recording(self):
+        global RECORDER
         self.requests = {}
+        RECORDER = self
+
+    def stop_recording(self):
+        """Un-register a bank that is dropped before its build()."""
+        global RECORDER
+        if RECORDER is self:
+            RECORDER = None
 
     def note(self, weight, groups, mode, chunk, pad_to=None):
         if self.requests is not None:
@@ -414,6 +425,18 @@ class WeightBank(object):
 
 
 RECORDER = None         # a WeightBank in its recording step
+
+
+@contextlib.contextmanager
+def fresh_packs():
+    """For a pass between training steps that must pack every weight afresh from the fp32 parameters (Trainer.test): the packed-weight
+    cache is emptied before and after, and a recording weight bank is parked meanwhile (it notes training requests only)."""
+    with _lib.scoped(_THIS, 'RECORDER', None):
+        _PACK_CACHE.clear()
+        try:
+            yield
+        finally:
+            _PACK_CACHE.clear()
 
 
 def _padded_dims(weight, pad_to):
@@ -726,6 +749,23 @@ _WQG = []                 # everything else (conv_wgrad.hip)
 GRAD_STORE = None         # distributed.GradStore of the running trainer: weight gradients are written into its views
 
 
+def grad_store(store):
+    """`with grad_store(st):` -- weight gradients computed inside are written into st's slots (new_wgrad) and flush_wgrads selects by
+    st's buckets: a step's backward pass and its tail flush."""
+    return _lib.scoped(_THIS, 'GRAD_STORE', store)
+
+
+def deferred_wgrads(on=True):
+    """`with deferred_wgrads():` -- weight gradients of the backward pass inside are queued for flush_wgrads (DEFER_WGRAD)."""
+    return _lib.scoped(_THIS, 'DEFER_WGRAD', bool(on))
+
+
+def drop_wgrads():
+    """Forget every queued weight gradient: what an abandoned step queued points at tensors nobody will ask for again."""
+    _WQ.clear()
+    _WQG.clear()
+
+
 def new_wgrad(weight, shape, device):
     """The tensor a weight-gradient kernel writes: the parameter's slot of the flat gradient storage (zero-copy for
     the all-reduce and the optimizer) when there is one and the parameter has no gradient yet, else a new tensor."""
@@ -744,8 +784,7 @@ def _check_adopted(queue):
         weight = q.weight
         gptr = q.gptr if q.post is None else q.post[1]      # (a channel-padded layer: the kernel writes a padded temporary, .grad is the tensor it is cropped into)
         if weight.grad is None or weight.grad.data_ptr() != gptr:
-            _WQ.clear()
-            _WQG.clear()
+            drop_wgrads()
             raise RuntimeError('deferred weight gradient of a %s parameter was copied or accumulated by autograd; '
                                'set DANET_DEFER_WGRAD=0 for this model' % (tuple(weight.shape),))
 
@@ -790,6 +829,8 @@ def flush_wgrads(bucket=None, hold=None):
     in order and all-reduces each one while the next one's launches run).  hold: a list that receives the processed queue
     entries -- a caller that flushes on a SIDE stream keeps the operands (x, dy: allocated on the step's stream) alive until the
     streams have joined again."""
+    if not (_WQ or _WQG):
+        return
     L = _lib.lib()
 
     if bucket is not None and not isinstance(bucket, int):

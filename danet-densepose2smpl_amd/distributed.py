@@ -233,17 +233,21 @@ class GradStore(object):
             return
         self._pending[b] -= 1
 
-    def release_ready(self, fn):
-        """Between two segments of the backward pass (main thread): fn(bucket) for every bucket that is complete, strictly in
-        index order.  The last bucket is never released here: it carries the usage mask, which is only known once the
-        backward pass has finished.  Returns the number of buckets released."""
-        n = 0
+    def _ready(self):
+        """The walk of both release_ready forms, between two segments of the backward pass (main thread): yields every bucket that is
+        complete, strictly in index order, counting it as released.  The last bucket is never released here: it carries the usage
+        mask, which is only known once the backward pass has finished."""
         if self._pending is None or not self._in_backward:
-            return n
+            return
         while self._next < len(self.buckets) - 1 and self._pending[self._next] == 0:
-            bi = self._next
             self._next += 1
             self.issued_early += 1
+            yield self._next - 1
+
+    def release_ready(self, fn):
+        """fn(bucket) for every complete bucket (_ready).  Returns the number of buckets released."""
+        n = 0
+        for bi in self._ready():
             fn(bi)
             n += 1
         return n
@@ -254,15 +258,10 @@ class GradStore(object):
         store instead of one of each per bucket (round 6: the regressor segment alone completes five 32 MB buckets at once; 13 bucket-sized
         flushes cost the N > 1 path 0.5 ms/step over the single flush of a one-process step).  Same order on every rank as release_ready:
         which buckets are complete after a segment depends on the model and on the global usage mask only."""
-        if self._pending is None or not self._in_backward:
-            return 0
-        b0 = self._next
-        while self._next < len(self.buckets) - 1 and self._pending[self._next] == 0:
-            self._next += 1
-            self.issued_early += 1
-        if self._next > b0:
-            fn(b0, self._next)
-        return self._next - b0
+        run = list(self._ready())
+        if run:
+            fn(run[0], run[-1] + 1)
+        return len(run)
 
     def next_bucket(self):
         """First bucket the backward pass did not release (the trainer's tail loop continues from here)."""
@@ -299,31 +298,19 @@ class GradStore(object):
 
     # ---- reduction -----------------------------------------------------------------------------------------------
     def reduce_bucket(self, bi):
-        """Sum bucket bi over the ranks.  Asynchronous on accelerators: the collective runs on the process group's
-        communication stream after everything queued so far on the current stream; call wait() before reading."""
-        if self.world == 1 and self.group is None and not (dist.is_available() and dist.is_initialized()):
-            return
-        s, e, _, _ = self.buckets[bi]
-        self.issued.append(bi)
-        if bi == len(self.buckets) - 1 and not self._mask_fresh:
-            self.used.fill_(1.0)            # a step outside backward_scope: no mask, every parameter with a gradient pointer is updated
-        if self.wire is None:
-            work = dist.all_reduce(self.flat[s:e], op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        else:
-            self.wire[s:e].copy_(self.flat[s:e])
-            work = dist.all_reduce(self.wire[s:e], op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        self._works.append((work, s, e))
+        """Sum bucket bi over the ranks (reduce_buckets for a run of one)."""
+        return self.reduce_buckets(bi, bi + 1)
 
     def reduce_buckets(self, b0, b1):
-        """reduce_bucket for the run b0 .. b1 - 1 as ONE collective: the run's slots are contiguous in the flat store."""
-        if b1 - b0 == 1:
-            return self.reduce_bucket(b0)
+        """Sum the run of buckets b0 .. b1 - 1 over the ranks as ONE collective: the run's slots are contiguous in the flat store.
+        Asynchronous on accelerators: the collective runs on the process group's communication stream after everything queued so
+        far on the current stream; call wait() before reading."""
         if self.world == 1 and self.group is None and not (dist.is_available() and dist.is_initialized()):
             return
         s, e = self.buckets[b0][0], self.buckets[b1 - 1][1]
         self.issued.extend(range(b0, b1))
         if b1 == len(self.buckets) and not self._mask_fresh:
-            self.used.fill_(1.0)
+            self.used.fill_(1.0)            # a step outside backward_scope: no mask, every parameter with a gradient pointer is updated
         if self.wire is None:
             work = dist.all_reduce(self.flat[s:e], op=dist.ReduceOp.SUM, group=self.group, async_op=True)
         else:
@@ -336,6 +323,10 @@ class GradStore(object):
             w.wait()                    # (accelerator tensors: the current stream waits, the host does not block)
             if self.wire is not None:
                 self.flat[s:e].copy_(self.wire[s:e])
+        self._works = []
+
+    def forget_pending(self):
+        """Drop the collectives of an abandoned step without waiting for them (their results belong to nobody)."""
         self._works = []
 
     def quiesce(self):

@@ -109,10 +109,7 @@ class GcnTailFunction(torch.autograd.Function):
         check(L.danet_gcn_tail_forward(ctypes.addressof(a), stream()), 'danet_gcn_tail_forward')
         _nn.onepass_watch(dev)                        # (outside a Trainer: a barrier that gave up is reported by the next launch)
         for bn in bns:                                    # torch's per-module counter (nn.BatchNorm1d.forward)
-            if _nn.BatchNorm2d.count_batches:
-                bn.num_batches_tracked.add_(1)
-            else:
-                _nn.BatchNorm2d._ran.append(bn.num_batches_tracked)
+            _nn.count_batch(bn.num_batches_tracked)
         ctx.save_for_backward(xc, ws, *ps)
         ctx.bufs = bufs
         ctx.bn = (float(bns[0].momentum), float(bns[0].eps))

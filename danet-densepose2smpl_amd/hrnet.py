@@ -6,11 +6,13 @@ Mirrors the module tree / state-dict keys of /root/reference/models/module/hr_mo
 sum_relu launch over at most four terms that reads the low-resolution terms in place.
 """
 import os
+import sys
 
 import torch
 import torch.nn as nn
 
 from . import segments
+from ._lib import scoped
 from .config import cfg
 from .nn import fan_out, fan_out_multi, sum_relu, sum_relu_multi, multi_batch_norm, multi_conv_bn
 from .resnet import BasicBlock, Bottleneck, ConvBN, IUV_predict_layer, make_res_layer, BN_MOMENTUM
@@ -40,6 +42,11 @@ FUSE_GROUP = int(os.environ.get('DANET_FUSE_GROUP', '12'))    # exchange paths p
 FUSE_SPLIT_RELU = bool(int(os.environ.get('DANET_FUSE_SPLIT_RELU', '0')))       # A-B knob: 1 = ReLU and non-ReLU exchange stages in separate launches (rounds 2-4)
 SUM_MULTI = bool(int(os.environ.get('DANET_SUM_MULTI', '1')))       # a module's fuse sums (and their gradients) in one launch each
 BRANCH_STREAMS = False      # run the low-resolution branches on side streams (set by the trainer's hipGraph capture)
+
+
+def branch_streams(on):
+    """`with branch_streams(on):` -- BRANCH_STREAMS = on for the forward passes inside (the capture of a step)."""
+    return scoped(sys.modules[__name__], 'BRANCH_STREAMS', bool(on))
 
 
 class HighResolutionModule(nn.Module):

@@ -4,6 +4,7 @@ import contextlib
 import ctypes
 
 import os
+import sys
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -45,6 +46,23 @@ SIDE_LIVE = 0
 SIDE_CAP = bool(int(os.environ.get('DANET_SIDE_CAP', '1')))      # 0: A-B timing of the cap ONLY (the hazard above is real)
 _ONEPASS_BAR = {}
 _CUS = {}
+_THIS = sys.modules[__name__]
+
+
+def confine_onepass(stream):
+    """Name the one stream the one-pass launches run on from here on (a trainer's step stream; None: the default stream)."""
+    global ONEPASS_STREAM
+    ONEPASS_STREAM = stream
+
+
+@contextlib.contextmanager
+def onepass_blocks(blocks):
+    """`with onepass_blocks(n):` -- a trainer's step: ONEPASS_MAX_BLOCKS = n inside.  Entering also closes a side-stream window that
+    a backward pass left open when it raised inside it (SIDE_LIVE = 0)."""
+    global SIDE_LIVE
+    SIDE_LIVE = 0
+    with _lib.scoped(_THIS, 'ONEPASS_MAX_BLOCKS', blocks):
+        yield
 
 
 def onepass_budget(device=None):
@@ -384,17 +402,14 @@ class BatchNormActFunction(torch.autograd.Function):
 class BatchNorm2d(nn.BatchNorm2d):
     """nn.BatchNorm2d (same parameters / buffers) with optional fused residual add and ReLU."""
 
-    # per-module `num_batches_tracked += 1` is one tiny launch per layer (353 per step); a trainer may
-    # switch it off and bump all counters with one multi-tensor op (bump_batch_counters)
+    # per-module `num_batches_tracked += 1` is one tiny launch per layer (353 per step); a trainer
+    # switches it off and bumps all counters with one multi-tensor op (deferred_batch_counts)
     count_batches = True
     _ran = []                 # counters of the modules that ran in training mode while count_batches was off
 
     def _count(self):
         if self.track_running_stats and self.num_batches_tracked is not None:
-            if BatchNorm2d.count_batches:
-                self.num_batches_tracked.add_(1)
-            else:
-                BatchNorm2d._ran.append(self.num_batches_tracked)
+            count_batch(self.num_batches_tracked)
 
     def _prologue(self, x):
         """What every launch of this module starts with -> (training, fused): `fused` = the batch statistics the producing conv's
@@ -906,10 +921,27 @@ def maxpool3x3s2(x):
     return MaxPool3x3S2Function.apply(x)
 
 
-def bump_batch_counters(module=None):
-    """num_batches_tracked += 1 for every BatchNorm2d that ran in training mode since the last call (with
-    BatchNorm2d.count_batches switched off), as ONE multi-tensor launch -- the modules torch would have counted
-    (/root/reference's nn.BatchNorm2d.forward): not the never-used stacks, not eval-mode layers, not a skipped regressor."""
-    counters, BatchNorm2d._ran = BatchNorm2d._ran, []
-    if counters:
-        torch._foreach_add_(counters, 1)
+def count_batch(counter):
+    """A module in training mode has seen one more batch: its `num_batches_tracked` is incremented now, or -- inside
+    deferred_batch_counts -- noted for the one bump after the forward pass."""
+    if BatchNorm2d.count_batches:
+        counter.add_(1)
+    else:
+        BatchNorm2d._ran.append(counter)
+
+
+@contextlib.contextmanager
+def deferred_batch_counts():
+    """`with deferred_batch_counts(): out = model(batch)` -- no per-module increment inside.  After a forward pass that returned:
+    num_batches_tracked += 1 for every module that ran in training mode, as ONE multi-tensor launch -- the modules torch would have
+    counted (/root/reference's nn.BatchNorm2d.forward): not the never-used stacks, not eval-mode layers, not a skipped regressor.
+    After one that raised the noted counters are dropped, so that no later step counts that batch.  The scope owns its list: the
+    switch and the list it found are back in place on every exit."""
+    found = BatchNorm2d.count_batches, BatchNorm2d._ran
+    BatchNorm2d.count_batches, BatchNorm2d._ran = False, []
+    try:
+        yield
+        if BatchNorm2d._ran:
+            torch._foreach_add_(BatchNorm2d._ran, 1)
+    finally:
+        BatchNorm2d.count_batches, BatchNorm2d._ran = found

@@ -18,6 +18,8 @@ construction, a capture records exactly what an eager step issues, and there is 
 
 The registry is per forward pass (`begin()`); with `ACTIVE` false `cut` is the identity and `backward` is one ordinary
 backward call."""
+import contextlib
+
 import torch
 
 ACTIVE = False            # set by the trainer around the forward pass of a step that wants segments
@@ -35,10 +37,19 @@ def begin(active):
 
 def end():
     """Forget the step's cut tensors (they keep their graphs alive)."""
-    global ACTIVE
-    ACTIVE = False
-    del _cuts[:]
-    _loss_level.clear()
+    begin(False)
+
+
+@contextlib.contextmanager
+def recording(active):
+    """`with recording(active):` around the forward and the backward pass of one step: begin(active), and on every exit end() and
+    the value of ACTIVE that was found."""
+    found = ACTIVE
+    begin(active)
+    try:
+        yield
+    finally:
+        begin(found)
 
 
 def level():

@@ -16,8 +16,8 @@ from . import ops
 from .config import cfg
 from .danet import DaNet
 from .distributed import GradStore
-from .nn import BatchNorm2d, SideBranch, bump_batch_counters
-from . import conv as _conv
+from .nn import SideBranch
+from . import conv as _conv, hrnet, nn as _nn, segments
 from .geometry import perspective_projection, label_prologue
 
 
@@ -148,11 +148,11 @@ class Trainer(object):
         self.stream = torch.cuda.Stream(device=self.device, priority=int(os.environ.get('DANET_MAIN_PRIORITY', '0'))) if on_gpu else None
         self.wgrad_stream = torch.cuda.Stream(device=self.device, priority=int(os.environ.get('DANET_WGRAD_PRIORITY', '0'))) if on_gpu else None
         self._held = []
+        self.onepass_blocks = 0
         self.segmented = (self.distributed and SEGMENTS != '0') or SEGMENTS == '1'
         if on_gpu:
             _conv.ARENA.enable(self.device)
-            from . import nn as _nn
-            _nn.ONEPASS_STREAM = self.stream        # the one-pass BatchNorm backward is confined to the step's own stream
+            _nn.confine_onepass(self.stream)        # the one-pass BatchNorm backward is confined to the step's own stream
             if isinstance(self.optimizer, torch.optim.Optimizer) is False:
                 # a step whose one-pass BatchNorm backward timed out at its grid barrier is skipped by the Adam kernel itself
                 self.optimizer.poison = _nn.onepass_poison(self.device)
@@ -164,7 +164,6 @@ class Trainer(object):
             # workgroup budget of the one-pass BatchNorm backward in THIS trainer's steps (installed by _core for the duration of a
             # step): 0 = the whole device; data-parallel: all-reduce kernels of earlier buckets run beside the backward pass, so the grid
             # barrier must fit next to them -- 2 * (compute units - channel limit); -1 = no limit known: two-kernel path
-            self.onepass_blocks = 0
             if os.environ.get('DANET_ONEPASS_BLOCKS'):            # experiment knob: an explicit budget
                 self.onepass_blocks = int(os.environ['DANET_ONEPASS_BLOCKS'])
             elif self.distributed:
@@ -236,11 +235,10 @@ class Trainer(object):
         captured graph dropped, and the caller told.  Data-parallel: the decision is taken from the all-reduced poison word
         (GradStore.poison: the error word is sticky, so the last step's sum tells whether ANY rank has timed out since the last
         check) -- every rank recovers and raises in the same call, none is left waiting in a collective."""
-        from . import nn as dnn
         if self.device.type != 'cuda':
             return
         elsewhere = bool(self.distributed and self.store is not None and self.store.poison_src is not None and float(self.store.poison) > 0)
-        if dnn.onepass_recover(self.device, force=elsewhere):
+        if _nn.onepass_recover(self.device, force=elsewhere):
             self._graph = None
             guarded = getattr(self.optimizer, 'poison', None) is not None
             raise RuntimeError('a one-pass BatchNorm launch timed out at its grid barrier' + (' on some rank' if elsewhere else '') +
@@ -289,19 +287,23 @@ class Trainer(object):
             if self.bank is None:
                 self.bank = _conv.WeightBank()
                 self.bank.start_recording()
-                _conv.RECORDER = self.bank
             elif self.bank.requests is not None:
                 self.bank.build()
             self.bank.refresh()
 
-    def _abort_cleanup(self):
-        """Host-side state an aborted step (a failed graph capture) leaves behind: BatchNorm call counters of the modules
-        that ran, gradients that point into the aborted pool.  (The arena cursor and the weight bank are re-armed by the
-        next step's _begin_step; queued weight-gradient jobs are dropped by the caller.)"""
-        BatchNorm2d._ran = []
-        BatchNorm2d.count_batches = True
-        _conv.DEFER_WGRAD = False
-        _conv.GRAD_STORE = None
+    def _forget_bank(self):
+        """The next step records and builds the weight bank anew (a phase that runs other modules)."""
+        if self.bank is not None:
+            self.bank.stop_recording()
+        self.bank = None
+
+    def _abandon_step(self):
+        """What a step that was given up (a late gradient, a failed graph capture) leaves behind for the rerun: queued weight-gradient
+        jobs that point at its tensors, pending collectives, gradients that point into an aborted pool.  (The step globals are put
+        back by their scopes; the arena cursor and the weight bank are re-armed by the next step's _begin_step.)"""
+        _conv.drop_wgrads()
+        if self.store is not None:
+            self.store.forget_pending()
         self.optimizer.zero_grad(set_to_none=True)
 
     @contextlib.contextmanager
@@ -316,85 +318,58 @@ class Trainer(object):
         when data-parallel (segments.py), releasing every complete gradient bucket between two segments: the bucket's
         weight-gradient launches, its small gradients copied into the store, its all-reduce (asynchronous, on the
         communication stream: the next segment's backward kernels overlap it); then the remaining buckets the same way; Adam
-        waits for the last all-reduce."""
-        from . import segments
-        from . import nn as _nn
+        waits for the last all-reduce.  Every global of another module that the step switches is held by that module's scope."""
         st = self.store
-        prev_blocks, _nn.ONEPASS_MAX_BLOCKS = _nn.ONEPASS_MAX_BLOCKS, getattr(self, 'onepass_blocks', 0)
-        _nn.SIDE_LIVE = 0                      # (a backward pass that raised inside a side-stream window leaves it open)
-        try:
-            return self._core_body(batch, reduce, with_optimizer, segments, st)
-        finally:
-            _nn.ONEPASS_MAX_BLOCKS = prev_blocks
-
-    def _core_body(self, batch, reduce, with_optimizer, segments, st):
-        self._begin_step()
-        if st is not None:
-            st.begin_step()
-        BatchNorm2d.count_batches = False
         reduce_now = bool(self.distributed and reduce)
         overlap = bool(WGRAD_OVERLAP and DEFER_WGRAD and st is not None and not self.distributed and self.wgrad_stream is not None)
-        segments.begin((self.segmented or overlap) and st is not None)
-        try:
-            try:
-                out = self.model(batch)
-            finally:
-                BatchNorm2d.count_batches = True
-            bump_batch_counters(self.model)
-            losses = out['losses']
-            self.optimizer.zero_grad(set_to_none=True)
-            _conv.GRAD_STORE = st
-            _conv.DEFER_WGRAD = DEFER_WGRAD
+        with _nn.onepass_blocks(self.onepass_blocks):
+            self._begin_step()
             if st is not None:
-                st.backward_scope(True, early=reduce_now)
-            try:
-                if segments.level() > 0:
-                    segments.backward(losses, (lambda k: st.release_ready_group(self._release_buckets)) if reduce_now else
-                                      ((lambda k: self._flush_on_side_stream()) if overlap else None))
-                else:
-                    # (every loss is a 1-element tensor, models/danet/danet.py:359-364: views + one cat + one sum)
-                    torch.cat([v.reshape(-1) for v in losses.values()]).sum().backward()
-            finally:
-                # first disarm the module globals, then close the scope (which may raise on a late gradient): an aborted step
-                # must not leave queued weight-gradient jobs or pending collectives behind for the rerun
-                _conv.DEFER_WGRAD = False
-                _conv.GRAD_STORE = None
-                if st is not None:
+                st.begin_step()
+            # (the store is named from the forward pass on, which does not ask for it: ONE scope for the backward pass and the tail
+            # flush, around the segment registry's, which ends before the tail so that the cut tensors are gone by then)
+            with _conv.grad_store(st):
+                with segments.recording((self.segmented or overlap) and st is not None):
+                    with _nn.deferred_batch_counts():
+                        out = self.model(batch)
+                    losses = out['losses']
+                    self.optimizer.zero_grad(set_to_none=True)
+                    if st is not None:
+                        st.backward_scope(True, early=reduce_now)
                     try:
-                        st.backward_scope(False)
-                        st.stamp_poison()
-                    except RuntimeError:
-                        _conv._WQ.clear()
-                        _conv._WQG.clear()
-                        st._works = []
-                        raise
-        finally:
-            segments.end()
-        if st is None:
-            _conv.flush_wgrads()
-        else:
-            _conv.GRAD_STORE = st
-            try:
+                        with _conv.deferred_wgrads(DEFER_WGRAD):
+                            if segments.level() > 0:
+                                segments.backward(losses, (lambda k: st.release_ready_group(self._release_buckets)) if reduce_now else
+                                                  ((lambda k: self._flush_on_side_stream()) if overlap else None))
+                            else:
+                                # (every loss is a 1-element tensor, models/danet/danet.py:359-364: views + one cat + one sum)
+                                torch.cat([v.reshape(-1) for v in losses.values()]).sum().backward()
+                    finally:
+                        # close the store's scope behind a backward pass that raised as well; it may raise itself, on a late gradient
+                        if st is not None:
+                            try:
+                                st.backward_scope(False)
+                                st.stamp_poison()
+                            except RuntimeError:
+                                self._abandon_step()
+                                raise
                 if reduce_now:
                     if st.next_bucket() < len(st.buckets):                   # what the backward pass did not release, as one run
                         self._release_buckets(st.next_bucket(), len(st.buckets))
-                else:
-                    # one process: no all-reduce to overlap with, so all queued weight gradients go out in the fewest, largest
-                    # multi-problem launches (-0.15 ms against 13 bucket-sized flushes) -- or, with WGRAD_OVERLAP, segment by segment on
-                    # the side stream, which joins the step's stream here
-                    if overlap:
-                        self._flush_on_side_stream()
-                        torch.cuda.current_stream(self.device).wait_stream(self.wgrad_stream)
-                        del self._held[:]
-                    _conv.flush_wgrads()
+                elif overlap:                                                # segment by segment on the side stream, which joins the step's here
+                    self._flush_on_side_stream()
+                    torch.cuda.current_stream(self.device).wait_stream(self.wgrad_stream)
+                    del self._held[:]
+                # one process: no all-reduce to overlap with, so all queued weight gradients go out in the fewest, largest
+                # multi-problem launches (-0.15 ms against 13 bucket-sized flushes); data-parallel: nothing left, every parameter
+                # belongs to a bucket
+                _conv.flush_wgrads()
+                if reduce_now:
+                    st.wait()
+                elif st is not None:
                     st.collect()
-                _conv.flush_wgrads()                     # (nothing left: every parameter belongs to a bucket)
-            finally:
-                _conv.GRAD_STORE = None
-            if reduce_now:
-                st.wait()
-        if with_optimizer:
-            self.optimizer.step()
+            if with_optimizer:
+                self.optimizer.step()
         return out, losses
 
     def _flush_on_side_stream(self):
@@ -405,43 +380,33 @@ class Trainer(object):
         with torch.cuda.stream(self.wgrad_stream):
             _conv.flush_wgrads(hold=self._held)
 
-    def _release_bucket(self, bi):
-        """A complete gradient bucket: its queued weight gradients are launched, its other gradients copied into the store, and
-        its all-reduce started (GradStore.release_ready between two backward segments, or the tail loop)."""
-        st = self.store
-        prev, _conv.GRAD_STORE = _conv.GRAD_STORE, st
-        try:
-            _conv.flush_wgrads(bucket=bi)
-        finally:
-            _conv.GRAD_STORE = prev
-        st.collect(bi)
-        st.reduce_bucket(bi)
-
     def _release_buckets(self, b0, b1):
-        """_release_bucket for the consecutive complete buckets b0 .. b1 - 1 at once: one flush of their queued weight gradients
-        (fewer, larger multi-problem launches), one multi-tensor copy, one all-reduce over their contiguous slice of the store."""
-        if not GROUP_RELEASE:
+        """The consecutive complete gradient buckets b0 .. b1 - 1 (GradStore.release_ready_group between two backward segments, or the
+        tail): their queued weight gradients are launched in one flush (fewer, larger multi-problem launches), their other gradients
+        copied into the store by one multi-tensor copy, and one all-reduce started over their contiguous slice of the store.
+        DANET_GROUP_RELEASE=0: the same, bucket by bucket."""
+        if not GROUP_RELEASE and b1 - b0 > 1:
             for bi in range(b0, b1):
-                self._release_bucket(bi)
+                self._release_buckets(bi, bi + 1)
             return
         st = self.store
         run = range(b0, b1)
-        prev, _conv.GRAD_STORE = _conv.GRAD_STORE, st
-        try:
+        with _conv.grad_store(st):
             _conv.flush_wgrads(bucket=run)
-        finally:
-            _conv.GRAD_STORE = prev
         st.collect(run)
         st.reduce_buckets(b0, b1)
+
+    def _end_step(self):
+        self.step_count += 1
+        if self.step_count % self.ONEPASS_CHECK_EVERY == 0:
+            self.check_onepass()
 
     def train_step(self, in_dict):
         self.model.train()
         self._decay_lr()
         with self._on_stream():
             out, losses = self._core(in_dict)
-        self.step_count += 1
-        if self.step_count % self.ONEPASS_CHECK_EVERY == 0:
-            self.check_onepass()
+        self._end_step()
         return out, losses
 
     # ------------------------------------------------------------------------------------------
@@ -460,7 +425,6 @@ class Trainer(object):
         captures the four zero losses and none of the work.  warmup: eager steps on `in_dict` before the capture (real optimizer
         steps; 0 when the caller has just run eager steps of this kind itself, as Trainer.fit does).  If the communication
         library cannot be captured the all-reduces and the optimizer run right after each replay instead."""
-        from . import conv
         if self.device.type != 'cuda':
             raise RuntimeError('hipGraph capture needs a GPU')
         self.model.train()
@@ -473,7 +437,6 @@ class Trainer(object):
         torch.cuda.synchronize(self.device)
         if self.store is not None:
             self.store.quiesce()                  # no collective of the eager steps may still be on the watchdog's list (see there)
-        from . import hrnet
         if self.store is not None:
             self.store.prepare_capture(attempts=2 if self.distributed else 1)
         modes = (True,)
@@ -485,18 +448,18 @@ class Trainer(object):
             backend = torch.distributed.get_backend(self.store.group) if torch.distributed.is_initialized() else ''
             modes = (True, False) if 'nccl' in str(backend) else (False,)
         for in_graph in modes:
-            conv._PACK_CACHE.clear()              # weight packing must be part of the captured work
+            _conv._PACK_CACHE.clear()             # weight packing must be part of the captured work
             self.optimizer.zero_grad(set_to_none=True)
             graph = torch.cuda.CUDAGraph()
-            hrnet.BRANCH_STREAMS = bool(int(os.environ.get('DANET_BRANCH_STREAMS', '1')))
-            conv.FUSION.clear()
+            _conv.FUSION.clear()
             try:
                 # thread_local: the communication library's watchdog thread may poll events of earlier collectives while
                 # this thread captures (the default, global mode turns that into a capture error)
-                with torch.cuda.graph(graph, stream=self.stream, capture_error_mode='thread_local' if self.distributed else 'global'):
+                with hrnet.branch_streams(int(os.environ.get('DANET_BRANCH_STREAMS', '1'))), \
+                        torch.cuda.graph(graph, stream=self.stream, capture_error_mode='thread_local' if self.distributed else 'global'):
                     self._static_out = self._core(self._static, reduce=in_graph, with_optimizer=in_graph)
                 self._reduce_in_graph = in_graph
-                self.fusion_counts = dict(conv.FUSION)      # which attribute-carried fusions the captured step contains
+                self.fusion_counts = dict(_conv.FUSION)     # which attribute-carried fusions the captured step contains
                 # the collectives the capture recorded, in issue order, and how many of them from inside the backward pass
                 self.captured_collectives = (list(self.store.issued), self.store.issued_early) if (self.store is not None and in_graph) else ([], 0)
                 break
@@ -505,14 +468,7 @@ class Trainer(object):
                     raise
                 self._end_stray_capture()
                 torch.cuda.synchronize(self.device)
-                # the aborted capture left host-side state behind: queued weight-gradient jobs that point at tensors of its
-                # pool, BatchNorm call counters, the arena cursor, pending collectives
-                self.store._works = []
-                conv._WQ.clear()
-                conv._WQG.clear()
-                self._abort_cleanup()
-            finally:
-                hrnet.BRANCH_STREAMS = False
+                self._abandon_step()
         self._graph = graph
         return self
 
@@ -586,9 +542,7 @@ class Trainer(object):
             with self._on_stream():
                 self.store.reduce_all()
                 self.optimizer.step()
-        self.step_count += 1
-        if self.step_count % self.ONEPASS_CHECK_EVERY == 0:
-            self.check_onepass()
+        self._end_step()
         return self._static_out
 
     # ------------------------------------------------------------------------------------------
@@ -622,9 +576,7 @@ class Trainer(object):
             # a new phase runs other modules: drop the old graph, static batch and pool FIRST, and let the two eager steps record and
             # build the weight bank again (the bank of a pretrain-mode step holds none of the regressor's weights)
             self.drop_graph()
-            self.bank = None
-            if isinstance(_conv.RECORDER, _conv.WeightBank):
-                _conv.RECORDER = None
+            self._forget_bank()
             phase, done = in_dict['pretrain_mode'], 0
         if done < 2:
             out, losses = self.train_step(in_dict)
@@ -743,17 +695,14 @@ class Trainer(object):
         if self.distributed and torch.distributed.get_rank() != 0:
             return {}
         was_training = self.model.training
-        recorder, _conv.RECORDER = _conv.RECORDER, None      # (a weight bank in its recording step notes training requests only)
-        _conv._PACK_CACHE.clear()
-        self.model.eval()
-        try:
-            with self._on_stream():
-                s = evaluate.run_evaluation(self.model, name, dataset, None, batch_size=int(getattr(o, 'batch_size', 32)),
-                                            num_workers=int(getattr(o, 'num_workers', 0) or 0), log_freq=0, options=o, verbose=False)
-        finally:
-            self.model.train(was_training)
-            _conv._PACK_CACHE.clear()
-            _conv.RECORDER = recorder
+        with _conv.fresh_packs():
+            self.model.eval()
+            try:
+                with self._on_stream():
+                    s = evaluate.run_evaluation(self.model, name, dataset, None, batch_size=int(getattr(o, 'batch_size', 32)),
+                                                num_workers=int(getattr(o, 'num_workers', 0) or 0), log_freq=0, options=o, verbose=False)
+            finally:
+                self.model.train(was_training)
         out = {'val_dataset': name, 'val_num_samples': s['num_samples']}
         for k in ('mpjpe', 'recon_err', 'pve', 'pa_pve', 'accuracy', 'f1', 'parts_accuracy', 'parts_f1'):
             if k in s:

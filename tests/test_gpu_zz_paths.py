@@ -278,6 +278,8 @@ def test_data_parallel_graph_path_single_rank():
             'DANET.STN_CENTER_JITTER': 0., 'DANET.STN_SCALE_JITTER': 0.})
     from danet_densepose2smpl_amd.trainer import Trainer, synthetic_in_dict, default_options
     from danet_densepose2smpl_amd.trainer import reserve_comm_channels
+    from danet_densepose2smpl_amd import trainer as trainer_mod
+    group_release = trainer_mod.GROUP_RELEASE
     dev = torch.device('cuda', 0)
     port = 29500 + (os.getpid() % 2000)
     had = os.environ.get('NCCL_MAX_NCHANNELS')
@@ -285,22 +287,24 @@ def test_data_parallel_graph_path_single_rank():
     dist.init_process_group('nccl', init_method='tcp://127.0.0.1:%d' % port, rank=0, world_size=1, device_id=dev)
     try:
         res = {}
-        for mode in ('single', 'ddp'):
+        # 'ddp_by_bucket': DANET_GROUP_RELEASE=0 -- every complete bucket flushed, copied and all-reduced on its own
+        for mode in ('single', 'ddp', 'ddp_by_bucket'):
             torch.manual_seed(0)
-            tr = Trainer(default_options(2), device=dev, distributed=(mode == 'ddp'), lr=1e-30, bucket_mb=8.0)
-            assert (tr.reducer is not None) == (mode == 'ddp') and len(tr.store.buckets) > 8
-            assert tr.onepass_blocks == (2 * (256 - int(os.environ['NCCL_MAX_NCHANNELS'])) if mode == 'ddp' else 0)
+            trainer_mod.GROUP_RELEASE = mode != 'ddp_by_bucket'
+            tr = Trainer(default_options(2), device=dev, distributed=(mode != 'single'), lr=1e-30, bucket_mb=8.0)
+            assert (tr.reducer is not None) == (mode != 'single') and len(tr.store.buckets) > 8
+            assert tr.onepass_blocks == (2 * (256 - int(os.environ['NCCL_MAX_NCHANNELS'])) if mode != 'single' else 0)
             batch = synthetic_in_dict(tr.model, 2, dev, seed=1)
             batch['pretrain_mode'] = True
             tr.train_step(batch)
             _, l_eager = tr.train_step(batch)
-            if mode == 'ddp':       # every bucket once, in bucket order; from the second step on (the first one learns which parameters
+            if mode != 'single':    # every bucket once, in bucket order; from the second step on (the first one learns which parameters
                 nb = len(tr.store.buckets)      # are in use) the backward pass runs in segments and releases complete buckets between them
                 assert tr.segmented and tr.store.issued == list(range(nb)), tr.store.issued
                 assert 1 <= tr.store.issued_early < nb, (tr.store.issued_early, nb)
                 eager_early = tr.store.issued_early
             tr.capture(batch, warmup=1)
-            if mode == 'ddp':
+            if mode != 'single':
                 assert tr._reduce_in_graph, 'the RCCL all-reduces were not captured into the hipGraph'
                 issued, early = tr.captured_collectives      # what the capture recorded: every bucket once, in order, the same ones
                 assert issued == list(range(nb)) and early == eager_early, (issued, early)      # between the backward segments as in the eager step
@@ -321,7 +325,13 @@ def test_data_parallel_graph_path_single_rank():
                 assert a == b, (k, a, b)
         rel = {n: ((res['ddp'][2][n] - res['single'][2][n]).norm() / (res['single'][2][n].norm() + 1e-12)).item() for n in res['single'][2]}
         assert max(rel.values()) < 1e-3, sorted(rel.items(), key=lambda kv: -kv[1])[:3]
+        # released as runs or bucket by bucket: the same collectives' worth of sums (issued == every bucket in order, above, both ways);
+        # the flushes group the queued jobs into other launches, i.e. other partial sums: losses equal, gradients to fp32 rounding
+        assert res['ddp_by_bucket'][0] == res['ddp'][0] and res['ddp_by_bucket'][1] == res['ddp'][1]
+        rel = {n: ((res['ddp_by_bucket'][2][n] - res['ddp'][2][n]).norm() / (res['ddp'][2][n].norm() + 1e-12)).item() for n in res['ddp'][2]}
+        assert max(rel.values()) < 1e-3, sorted(rel.items(), key=lambda kv: -kv[1])[:3]
     finally:
+        trainer_mod.GROUP_RELEASE = group_release
         dist.destroy_process_group()
         if had is None:
             os.environ.pop('NCCL_MAX_NCHANNELS', None)
@@ -612,3 +622,111 @@ def test_side_stream_window_caps_the_barrier_budget_and_closes():
     conv.flush_wgrads()
     torch.cuda.synchronize()
     assert not dnn.onepass_error()
+
+
+def _step_globals():
+    """Every global of another module that a train step switches (trainer.Trainer._core), and what a step may leave queued."""
+    from danet_densepose2smpl_amd import conv, hrnet, nn as dnn, segments
+    return {'GRAD_STORE': conv.GRAD_STORE, 'DEFER_WGRAD': conv.DEFER_WGRAD, 'ONEPASS_MAX_BLOCKS': dnn.ONEPASS_MAX_BLOCKS,
+            'SIDE_LIVE': dnn.SIDE_LIVE, 'count_batches': dnn.BatchNorm2d.count_batches, '_ran': list(dnn.BatchNorm2d._ran),
+            'ACTIVE': segments.ACTIVE, 'level': segments.level(), 'BRANCH_STREAMS': hrnet.BRANCH_STREAMS,
+            'queued': (len(conv._WQ), len(conv._WQG))}
+
+
+AT_REST = {'GRAD_STORE': None, 'DEFER_WGRAD': False, 'ONEPASS_MAX_BLOCKS': 0, 'SIDE_LIVE': 0, 'count_batches': True, '_ran': [],
+           'ACTIVE': False, 'level': 0, 'BRANCH_STREAMS': False, 'queued': (0, 0)}
+_TWIN = {}
+
+
+def _small_trainer():
+    """The configuration of test_graphed_step_matches_eager_step: 128 pixels, B = 2, pretrain mode, learning rate ~0, seed 0."""
+    _cfg(**{'DANET.INIMG_SIZE': 128, 'DANET.HEATMAP_SIZE': 32, 'DANET.PARTDROP_RATE': 0.,
+            'DANET.STN_CENTER_JITTER': 0., 'DANET.STN_SCALE_JITTER': 0.})
+    from danet_densepose2smpl_amd.trainer import Trainer, synthetic_in_dict, default_options
+    dev = torch.device('cuda')
+    torch.manual_seed(0)
+    tr = Trainer(default_options(2), device=dev, distributed=False, lr=1e-30)
+    batch = synthetic_in_dict(tr.model, 2, dev, seed=1)
+    batch['pretrain_mode'] = True
+    return tr, batch
+
+
+def _good_step(tr, batch):
+    """One train_step -> (losses, 4-D weight gradients, num_batches_tracked of every module), as copies."""
+    _, losses = tr.train_step(batch)
+    torch.cuda.synchronize()
+    return ({k: v.detach().float().sum().clone() for k, v in losses.items()},
+            {n: p.grad.detach().clone() for n, p in tr.model.named_parameters() if p.grad is not None and p.dim() == 4},
+            {n: int(b) for n, b in tr.model.named_buffers() if n.endswith('num_batches_tracked')})
+
+
+def _undisturbed_twin():
+    """The first step of a trainer nothing happened to (computed once; the trainer is gone before the disturbed one is built, which
+    then owns the one-pass stream)."""
+    if not _TWIN:
+        tr, batch = _small_trainer()
+        _TWIN['step'] = _good_step(tr, batch)
+    return _TWIN['step']
+
+
+def _assert_same_step(got, want):
+    assert set(got[0]) == set(want[0]) and set(got[1]) == set(want[1]) and len(want[1]) > 100
+    for k in want[0]:
+        assert torch.equal(got[0][k], want[0][k]), (k, float(got[0][k]), float(want[0][k]))
+    for n in want[1]:
+        assert torch.equal(got[1][n], want[1][n]), n
+
+
+def test_failed_forward_does_not_change_the_next_step():
+    """A forward pass that raises (a host exception, after the HRNet stem, layer1 and stage2 have run) is followed by a step that
+    equals an undisturbed trainer's bit for bit, and every BatchNorm has counted ONE batch: the counters the failed pass noted are
+    dropped with it (nn.deferred_batch_counts), every step global is back at rest."""
+    from danet_densepose2smpl_amd import nn as dnn
+    want = _undisturbed_twin()
+    tr, batch = _small_trainer()
+    assert _step_globals() == AT_REST
+    stage = tr.model.img2iuv.iuv_est.stage3[0]
+
+    def fail(xs):
+        raise ValueError('forward failed')
+    stage.forward = fail
+    try:
+        with pytest.raises(ValueError, match='forward failed'):
+            tr.train_step(batch)
+    finally:
+        del stage.forward
+    assert dnn.BatchNorm2d._ran == [] and _step_globals() == AT_REST and tr.step_count == 0
+    got = _good_step(tr, batch)
+    assert _step_globals() == AT_REST and not dnn.onepass_error()
+    _assert_same_step(got, want)
+    assert got[2] == want[2] and set(want[2].values()) == {0, 1} and sum(want[2].values()) > 100
+
+
+def test_late_gradient_failure_is_cleaned_up():
+    """The store refuses a step when it closes the backward pass (a gradient behind an all-reduced bucket): the weight gradients the
+    step queued and its pending collectives are dropped (Trainer._abandon_step), the globals are at rest, and the rerun equals an
+    undisturbed trainer's step bit for bit."""
+    from danet_densepose2smpl_amd import conv
+    want = _undisturbed_twin()
+    tr, batch = _small_trainer()
+    st = tr.store
+    close = st.backward_scope
+    queued = []
+
+    def refuse(active, **kw):
+        close(active, **kw)
+        if not active:
+            queued.append(len(conv._WQ) + len(conv._WQG))
+            raise RuntimeError('GradStore: late gradient')
+    st.backward_scope = refuse
+    try:
+        with pytest.raises(RuntimeError, match='late gradient'):
+            tr.train_step(batch)
+    finally:
+        del st.backward_scope
+    torch.cuda.synchronize()
+    assert queued and queued[0] > 100                         # the step HAD queued its weight gradients
+    assert st._works == [] and _step_globals() == AT_REST and tr.step_count == 0
+    got = _good_step(tr, batch)
+    assert _step_globals() == AT_REST
+    _assert_same_step(got, want)
