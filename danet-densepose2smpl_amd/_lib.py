@@ -170,6 +170,8 @@ _SIGNATURES = {
                                    c_fl, c_fl, c_fl, c_f, c_f]),
     'danet_texture_render': (c_i, [c_f, c_f, c_i, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_f,
                                    ctypes.POINTER(ctypes.c_int32), c_f, c_fl, c_i, ctypes.POINTER(c_fl), c_f, c_f, c_f]),
+    'danet_kp_fit_ws_floats': (c_sz, [c_i, c_i]),
+    'danet_kp_fit': (c_i, [c_f, c_sz, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations
@@ -238,6 +240,15 @@ class LstmTreeArgs(ctypes.Structure):
     _fields_ = [('pos', ctypes.c_void_p)] + [(k, _PTR5x2) for k in ('w_ih', 'w_hh', 'b_ih', 'b_hh')] + \
                [(k, ctypes.c_void_p) for k in ('out', 'ws', 'g_out', 'scratch', 'g_pos')] + \
                [(k, _PTR5x2) for k in ('g_w_ih', 'g_w_hh', 'g_b_ih', 'g_b_hh')] + [('B', c_i)]
+
+
+class KpFitArgs(ctypes.Structure):
+    """struct danet_kp_fit_args (include/danet_hip.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ('para', 'kp', 'J_template', 'J_shapedirs', 'parents', 'v_template', 'basis', 'basisT', 'weights',
+                                               'jx', 'lm', 'jmap', 'ws', 'para_fit', 'history', 'best_iter', 'status', 'grad0')] + \
+               [('stage_iters', ctypes.c_int32 * 4), ('stage_mask', ctypes.c_int32 * 4)] + \
+               [(k, ctypes.c_int32) for k in ('P', 'NB', 'S', 'Sp', 'NL', 'NE', 'nstages', 'T')] + \
+               [(k, ctypes.c_float) for k in ('focal', 'res', 'kappa', 'sigma', 'w_orient', 'w_pose', 'w_shape', 'lr')]
 
 
 class ConvJob(ctypes.Structure):

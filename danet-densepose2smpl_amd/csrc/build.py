@@ -57,6 +57,7 @@ UNITS = {
     'train_vis.hip': ['-ffp-contract=off'],   # x * std + mean and the min / max normalisation are the written operations
     'scene_ops.hip': ['-ffp-contract=off'],   # the scene rule's arithmetic is restated operation by operation in the tests
     'texture_ops.hip': ['-ffp-contract=off'],  # the texture rule likewise; its map is bit-equal to a float64 restatement
+    'kp_fit.hip': [],
 }
 INCLUDES = {'norm_act_f32.hip': ['norm_act.hip']}
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-I' + os.path.join(ROOT, 'include'), '-I' + HERE,

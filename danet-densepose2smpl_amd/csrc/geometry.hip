@@ -1,6 +1,7 @@
 // Rotation helpers of /root/reference/utils/geometry.py as single-launch HIP kernels
 // (the reference issues ~10 tiny torch kernels for each of these).
 #include "common.h"
+#include "rot6d.h"
 
 namespace {
 
@@ -52,54 +53,15 @@ __global__ void rodrigues_smplx_kernel(const float* __restrict__ theta, int N, f
 }
 
 __global__ void rot6d_fwd_kernel(const float* __restrict__ x, int N, float* __restrict__ R) {
-    // geometry.py:55-61: x viewed [3,2]; a1 = x[:,0], a2 = x[:,1]; F.normalize eps = 1e-12
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const float* p = x + (size_t)i * 6;
-    const float a1[3] = {p[0], p[2], p[4]}, a2[3] = {p[1], p[3], p[5]};
-    const float n1 = fmaxf(sqrtf(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]), 1e-12f);
-    const float b1[3] = {a1[0] / n1, a1[1] / n1, a1[2] / n1};
-    const float d = b1[0] * a2[0] + b1[1] * a2[1] + b1[2] * a2[2];
-    const float u[3] = {a2[0] - d * b1[0], a2[1] - d * b1[1], a2[2] - d * b1[2]};
-    const float n2 = fmaxf(sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), 1e-12f);
-    const float b2[3] = {u[0] / n2, u[1] / n2, u[2] / n2};
-    const float b3[3] = {b1[1] * b2[2] - b1[2] * b2[1], b1[2] * b2[0] - b1[0] * b2[2], b1[0] * b2[1] - b1[1] * b2[0]};
-    float* o = R + (size_t)i * 9;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) { o[r * 3 + 0] = b1[r]; o[r * 3 + 1] = b2[r]; o[r * 3 + 2] = b3[r]; }
+    danet::rot6d_fwd(x + (size_t)i * 6, R + (size_t)i * 9);        // (rot6d.h: shared with the keypoint fit)
 }
 
 __global__ void rot6d_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gR, int N, float* __restrict__ gx) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const float* p = x + (size_t)i * 6;
-    const float* g = gR + (size_t)i * 9;
-    const float a1[3] = {p[0], p[2], p[4]}, a2[3] = {p[1], p[3], p[5]};
-    const float n1 = fmaxf(sqrtf(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]), 1e-12f);
-    const float b1[3] = {a1[0] / n1, a1[1] / n1, a1[2] / n1};
-    const float d = b1[0] * a2[0] + b1[1] * a2[1] + b1[2] * a2[2];
-    const float u[3] = {a2[0] - d * b1[0], a2[1] - d * b1[1], a2[2] - d * b1[2]};
-    const float n2 = fmaxf(sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), 1e-12f);
-    const float b2[3] = {u[0] / n2, u[1] / n2, u[2] / n2};
-    float gb1[3] = {g[0], g[3], g[6]}, gb2[3] = {g[1], g[4], g[7]};
-    const float gb3[3] = {g[2], g[5], g[8]};
-    // b3 = b1 x b2
-    gb1[0] += b2[1] * gb3[2] - b2[2] * gb3[1]; gb1[1] += b2[2] * gb3[0] - b2[0] * gb3[2]; gb1[2] += b2[0] * gb3[1] - b2[1] * gb3[0];
-    gb2[0] += gb3[1] * b1[2] - gb3[2] * b1[1]; gb2[1] += gb3[2] * b1[0] - gb3[0] * b1[2]; gb2[2] += gb3[0] * b1[1] - gb3[1] * b1[0];
-    // b2 = u / |u|
-    const float t2 = b2[0] * gb2[0] + b2[1] * gb2[1] + b2[2] * gb2[2];
-    const float gu[3] = {(gb2[0] - b2[0] * t2) / n2, (gb2[1] - b2[1] * t2) / n2, (gb2[2] - b2[2] * t2) / n2};
-    // u = a2 - (b1.a2) b1
-    const float gub1 = gu[0] * b1[0] + gu[1] * b1[1] + gu[2] * b1[2];
-    const float ga2[3] = {gu[0] - gub1 * b1[0], gu[1] - gub1 * b1[1], gu[2] - gub1 * b1[2]};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) gb1[k] += -d * gu[k] - gub1 * a2[k];
-    // b1 = a1 / |a1|
-    const float t1 = b1[0] * gb1[0] + b1[1] * gb1[1] + b1[2] * gb1[2];
-    const float ga1[3] = {(gb1[0] - b1[0] * t1) / n1, (gb1[1] - b1[1] * t1) / n1, (gb1[2] - b1[2] * t1) / n1};
-    float* o = gx + (size_t)i * 6;
-    o[0] = ga1[0]; o[2] = ga1[1]; o[4] = ga1[2];
-    o[1] = ga2[0]; o[3] = ga2[1]; o[5] = ga2[2];
+    danet::rot6d_bwd(x + (size_t)i * 6, gR + (size_t)i * 9, gx + (size_t)i * 6);
 }
 
 }  // namespace

@@ -83,6 +83,21 @@ def person_cameras(cam, tinv, frame_shapes, person_frame, res, focal=5000., foca
     return {'proj': proj, 'cam_t': cam_t, 'dscale': dscale, 'cam_t_full': cam_t_full, 'focal_full': F0}
 
 
+def keypoints_to_crop(kps_frame, t, res):
+    """Keypoints in frame pixels -> normalised crop coordinates, the keypoint convention of the fit rule: kps_frame
+    [..,K,3] (x, y, confidence), `t` [..,3,3] (or [..,2,3]) the forward crop transform of datasets.crop_transforms, frame pixel
+    indices -> crop pixel indices.  With c = res / 2 - 0.5 the result is ((t (x, y, 1) - c) / (res / 2), confidence): person_cameras'
+    `proj` of a point (x_n, y_n) comes back as 2 focal / 224 (x_n, y_n).  float64 on the host."""
+    k = np.asarray(kps_frame, np.float64)
+    t = np.asarray(t, np.float64)[..., :2, :]
+    res = float(res)
+    c = res / 2.0 - 0.5
+    out = k.copy()
+    for r in range(2):
+        out[..., r] = (t[..., None, r, 0] * k[..., 0] + t[..., None, r, 1] * k[..., 1] + t[..., None, r, 2] - c) / (res / 2.0)
+    return out
+
+
 def write_obj(path, vertices, faces):
     """A Wavefront .obj: one `v x y z` line per vertex (9 significant digits: a float32 survives), one `f a b c` line per face
     (1-based)."""
@@ -122,12 +137,17 @@ class SceneDemo(object):
     """SceneDemo(model_or_engine, smpl, batch): a DaNet in eval mode on the GPU (its infer_net runs) or an InferenceEngine built at
     batch size `batch`; `smpl` the SMPL layer of the model (model.iuv2smpl.smpl).
 
+    With `fitter` (a kp_fit.KeypointFitter over the same SMPL layer) and `keypoints` -- per frame one [49,3] (or BODY_25 [25,3]) array
+    per box, frame pixels and confidences -- the network's rows are refined against the keypoints before they are drawn (DESIGN.md
+    "fit rule", scene kappa = 2 focal / 224); every people dict then also holds 'para_init' [k,229], 'fit_loss' [k,2] (initial and final
+    E) and 'fit_iter' [k].  Without either, every output is what it is without the fitter.
+
     __call__(frames, boxes) -> (rendered frames: list of uint8 [H,W,3], people: one dict per frame with 'para' [k,229], 'cam' [k,3],
     'cam_t_full' [k,3], 'focal_full' [k], 'center' [k,2], 'scale' [k] and 'vertices' [k,V,3], k the number of boxes of the frame).
     The three stages are methods of their own: prepare (host: packing, crop and camera parameters; device: uploads), infer (crops and
     the network -> para [P,229]) and render (para -> the rendered bytes; capturable for fixed shapes)."""
 
-    def __init__(self, model_or_engine, smpl, batch, res=None, focal=constants.FOCAL_LENGTH, focal_full=None):
+    def __init__(self, model_or_engine, smpl, batch, res=None, focal=constants.FOCAL_LENGTH, focal_full=None, fitter=None):
         from .config import cfg
         from .inference import InferenceEngine
         self.engine = model_or_engine if isinstance(model_or_engine, InferenceEngine) else None
@@ -141,6 +161,7 @@ class SceneDemo(object):
         if self.batch < 1:
             raise ValueError('SceneDemo: batch %d' % self.batch)
         self.mesh = MeshRenderer(smpl.faces, focal_length=self.focal, img_res=self.res)      # its face tables and lights
+        self.fitter = fitter
 
     def prepare(self, frames, boxes):
         """Everything that does not depend on the network's answer.  -> plan (a dict): the packed frames and the per-person crop and
@@ -184,6 +205,23 @@ class SceneDemo(object):
             paras.append(out['para'][:n].detach().clone())                 # (the engine's buffers live until its next call)
         return torch.cat(paras, 0)
 
+    def crop_keypoints(self, plan, keypoints):
+        """Per frame one [49,3] or [25,3] array per box (frame pixels) -> [P,49,3] f32 on the device, normalised crop coordinates."""
+        from .kp_fit import openpose_to_j49
+        if len(keypoints) != plan['N'] or [len(k) for k in keypoints] != np.bincount(plan['person_frame'], minlength=plan['N']).tolist():
+            raise ValueError('SceneDemo: keypoints must hold one array per box of every frame')
+        flat = [np.asarray(k, np.float64) for ks in keypoints for k in ks]
+        flat = np.stack([openpose_to_j49(k).astype(np.float64) if k.shape == (25, 3) else k for k in flat]).reshape(plan['P'], 49, 3)
+        t, _ = datasets.crop_transforms(plan['center'], plan['scale'], np.zeros(plan['P']), self.res)
+        return torch.from_numpy(keypoints_to_crop(flat, t, self.res).astype(np.float32)).to(self.device)
+
+    def fit(self, para, plan, keypoints):
+        """para [P,229] refined against the plan's people's keypoints -> (para_fit, info), the scene camera's kappa = 2 focal / 224."""
+        if self.fitter.res != self.res or self.fitter.focal != self.focal:
+            raise ValueError('SceneDemo: the fitter was built for res %g, focal %g; the demo runs at res %d, focal %g'
+                             % (self.fitter.res, self.fitter.focal, self.res, self.focal))
+        return self.fitter.fit(para, self.crop_keypoints(plan, keypoints), return_history=True, kappa=2.0 * self.focal / 224.0)
+
     def vertices(self, para):
         return from_para(self.smpl, para).vertices.detach()
 
@@ -208,10 +246,16 @@ class SceneDemo(object):
         return ops.scene_render(rverts, vcol, t.faces2, cam_t, plan['d_proj'], plan['d_dscale'], plan['d_person_frame'], plan['d_src'],
                                 plan['d_offsets'], plan['d_shapes'], return_aux=return_aux, host=host)
 
-    def __call__(self, frames, boxes):
+    def __call__(self, frames, boxes, keypoints=None):
         plan = self.prepare(frames, boxes)
         P = plan['P']
         para = self.infer(plan) if P else torch.zeros(0, 229, device=self.device)
+        fitted = None
+        if self.fitter is not None and keypoints is not None:
+            fitted = (para, None)
+            if P:
+                para_fit, info = self.fit(para, plan, keypoints)
+                fitted, para = (para, info), para_fit
         verts = self.vertices(para) if P else None
         out = self.render(para, plan, vertices=verts)
         rendered = unpack_frames(out.cpu().numpy(), plan['offsets'], plan['shapes'])
@@ -225,4 +269,14 @@ class SceneDemo(object):
             people.append({'para': para_h[m], 'cam': para_h[m, 0:3], 'cam_t_full': k['cam_t_full'][m] if P else np.zeros((0, 3)),
                            'focal_full': k['focal_full'][m] if P else np.zeros(0), 'center': plan['center'][m], 'scale': plan['scale'][m],
                            'vertices': verts_h[m]})
+        if fitted is not None:
+            init = fitted[0].cpu().numpy()
+            if P:
+                hist, it = fitted[1]['history'].cpu().numpy(), fitted[1]['best_iter'].cpu().numpy()
+                loss = np.stack([hist[:, 0], hist[np.arange(P), it]], 1)
+            else:
+                loss, it = np.zeros((0, 2), np.float32), np.zeros(0, np.int32)
+            for n in range(plan['N']):
+                m = plan['person_frame'] == n
+                people[n].update({'para_init': init[m], 'fit_loss': loss[m], 'fit_iter': it[m]})
         return rendered, people

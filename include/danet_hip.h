@@ -918,6 +918,42 @@ int danet_texture_render(const float* rverts, const float* cam, int N, int NV, c
                          const int32_t* host_atlas_index, const float* images, float focal, int S, const float* fill,
                          float* rgb, float* alpha, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Keypoint fit (csrc/kp_fit.hip; kp_fit.py is the caller; DESIGN.md "fit rule"): P people's (cam, betas, 24 rotations) refined
+ * against 2D keypoints by staged Adam on the fit energy.  ONE launch, one workgroup per person, every iteration inside the
+ * kernel; no atomics, fixed-order reductions: a row's result does not depend on the other rows, two runs give the same bits.
+ *
+ * para [P, 3 + NB + 216] f32 = (s, tx, ty, betas, 24 row-major rotation matrices), kp [P,49,3] f32 = (u, v, confidence).
+ * The tables are the SMPL layer's restricted to the support set of S vertices (the landmark vertices and the columns where
+ * J_regressor_extra is non-zero), every vertex axis zero-padded to Sp, a multiple of 128 (the kernel walks tiles of 128):
+ *   J_template [72], J_shapedirs [72,NB], parents [24] i32            as the SMPL layer holds them
+ *   v_template [Sp*3]
+ *   basis      [207+NB, Sp*3]   rows 0..206 posedirs, rows 207.. shapedirs (transposed), restricted to the support
+ *   basisT     [Sp*3, 224]      its transpose, columns past 207+NB zero
+ *   weights    [Sp,24]          lbs_weights rows of the support
+ *   jx         [NE,Sp]          J_regressor_extra columns of the support
+ *   lm         [NL] i32         position of each landmark vertex in the support, in [0, S)
+ *   jmap       [49] i32         the 49 joints as indices into the 24 + NL + NE joints
+ * The caller vouches for the extents of the tables and the ranges of lm / jmap / parents.
+ * stage_iters / stage_mask [nstages <= 4]: iterations and groups (bit 0 cam, 1 orient, 2 body, 3 shape); T = their sum.
+ * ws: danet_kp_fit_ws_floats(P, Sp) floats (v_posed of the support per person), owned by the launch while it runs.
+ * Outputs: para_fit [P, 3+NB+216]; history [P,T+1]; best_iter [P] i32; status [P] i32 (0 ok, 1: E(x_0) not finite -- the row
+ * comes back unchanged, history[1..] is NaN); grad0 [P, 3+NB+144] or NULL: dE/dx at x_0 (zeros for a status-1 row).
+ */
+struct danet_kp_fit_args {
+    const float* para; const float* kp;
+    const float* J_template; const float* J_shapedirs; const int32_t* parents;
+    const float* v_template; const float* basis; const float* basisT; const float* weights; const float* jx;
+    const int32_t* lm; const int32_t* jmap;
+    float* ws;
+    float* para_fit; float* history; int32_t* best_iter; int32_t* status; float* grad0;
+    int32_t stage_iters[4]; int32_t stage_mask[4];
+    int32_t P, NB, S, Sp, NL, NE, nstages, T;
+    float focal, res, kappa, sigma, w_orient, w_pose, w_shape, lr;
+};
+size_t danet_kp_fit_ws_floats(int P, int Sp);
+int danet_kp_fit(const struct danet_kp_fit_args* args, size_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,11 +5,14 @@ triple per person, <name>_<k>.obj + <name>_<k>.mtl + <name>_<k>_texture.png: the
 through the crop camera (texture.TextureAtlas, texture.write_textured_obj).  The scene picture is the same either way.
 
   python tools/demo_scene.py --img_dir DIR --out_dir DIR [--boxes FILE.json] [--keypoints_dir DIR] [--checkpoint FILE] [--cfg YAML]
-                             [--engine] [--batch N] [--obj [--texture [--texture_size T]]]
+                             [--engine] [--batch N] [--obj [--texture [--texture_size T]]] [--fit [--fit_iters N]]
 
 Boxes: --boxes maps an image's file name to a list of [x, y, w, h]; --keypoints_dir holds <name>_keypoints.json in OpenPose's layout
 (one person per people[] entry, pose_keypoints_2d = x, y, confidence, ...); with neither, the whole image is one box.  There is no
-person detector here.  Images: .npy arrays always (uint8 [H,W,3]); .jpg / .png if PIL is installed.  Without --checkpoint the model
+person detector here.  --fit (needs --keypoints_dir; refused with --boxes, there is no rule here for matching boxes to people) refines
+every person's predicted row against the person's BODY_25 keypoints before it is drawn (kp_fit.KeypointFitter, DESIGN.md "fit rule";
+--fit_iters N iterations, 30 % of them on camera and global orientation alone); the _people.npz then also holds para_init, fit_loss
+(initial and final energy) and fit_iter.  Images: .npy arrays always (uint8 [H,W,3]); .jpg / .png if PIL is installed.  Without --checkpoint the model
 has seeded random weights and the synthetic SMPL / DensePose tables, so the tool runs on a clean checkout.  The PNG files are written
 by train_vis.write_png.  Last line: one JSON object with the milliseconds per frame of the three device stages (crop: ops.batch_crop;
 infer: the network; render: SMPL forward, shading and ops.scene_render) on the last group of frames, HIP events, the median and
@@ -65,6 +68,18 @@ def boxes_of(name, frame, box_table, keypoints_dir):
     return [scene.whole_image_box(frame.shape)]
 
 
+def keypoints_of(name, keypoints_dir):
+    """The BODY_25 arrays [25,3] of the people boxes_of makes boxes for, in the same order."""
+    path = os.path.join(keypoints_dir, os.path.splitext(name)[0] + '_keypoints.json')
+    if not os.path.exists(path):
+        return []
+    kps = [np.asarray(person['pose_keypoints_2d'], np.float64).reshape(-1, 3) for person in json.load(open(path)).get('people', [])]
+    for k in kps:
+        if k.shape != (25, 3):
+            raise SystemExit('%s: --fit needs BODY_25 keypoints (25 rows), got %d' % (path, k.shape[0]))
+    return [k for k in kps if (k[:, 2] > 0.2).any()]
+
+
 def _stats(ts, n):
     ts = np.asarray(ts) / n
     return {'ms_per_frame': round(float(np.median(ts)), 4), 'p10': round(float(np.percentile(ts, 10)), 4), 'p90': round(float(np.percentile(ts, 90)), 4)}
@@ -84,7 +99,15 @@ def main(argv=None):
     ap.add_argument('--texture', action='store_true', help='with --obj: textured .obj + .mtl + _texture.png per person')
     ap.add_argument('--texture_size', type=int, default=64, help='texels per side of a chart')
     ap.add_argument('--reps', type=int, default=20, help='timed repetitions of the three stages (0: no timing)')
+    ap.add_argument('--fit', action='store_true', help='refine every person against the keypoints of --keypoints_dir before drawing')
+    ap.add_argument('--fit_iters', type=int, default=100, help='with --fit: iterations of the fit')
     a = ap.parse_args(argv)
+    if a.fit and a.boxes:
+        raise SystemExit('--fit cannot be combined with --boxes: there is no rule here for matching boxes to the people of the keypoint files')
+    if a.fit and not a.keypoints_dir:
+        raise SystemExit('--fit needs --keypoints_dir')
+    if a.fit and a.fit_iters < 1:
+        raise SystemExit('--fit_iters %d' % a.fit_iters)
 
     import torch
     from danet_densepose2smpl_amd import checkpoint, constants, scene, texture
@@ -111,6 +134,10 @@ def main(argv=None):
     smpl = model.iuv2smpl.smpl
     engine = model.inference_engine(a.batch) if a.engine else None
     demo = scene.SceneDemo(engine if engine is not None else model, smpl, a.batch)
+    if a.fit:
+        from danet_densepose2smpl_amd.kp_fit import KeypointFitter
+        n0 = (3 * a.fit_iters) // 10
+        demo.fitter = KeypointFitter(smpl, stages=((n0, 'cam+orient'), (a.fit_iters - n0, 'all')), focal=demo.focal, res=demo.res)
     tex = texture.TextureAtlas(size=a.texture_size, focal_length=demo.focal) if a.texture else None
 
     last, people_total = None, 0
@@ -118,7 +145,7 @@ def main(argv=None):
         group = names[i:i + GROUP]
         frames = [load_frame(os.path.join(a.img_dir, n)) for n in group]
         boxes = [boxes_of(n, f, box_table, a.keypoints_dir) for n, f in zip(group, frames)]
-        rendered, people = demo(frames, boxes)
+        rendered, people = demo(frames, boxes, [keypoints_of(n, a.keypoints_dir) for n in group] if a.fit else None)
         sheets = None
         if tex is not None and any(boxes):                          # every person's crop, de-normalised, through the crop camera
             mean, std = (torch.tensor(c, device=demo.device).view(1, 3, 1, 1) for c in (constants.IMG_NORM_MEAN, constants.IMG_NORM_STD))
