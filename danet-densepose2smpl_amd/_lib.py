@@ -172,6 +172,7 @@ _SIGNATURES = {
                                    ctypes.POINTER(ctypes.c_int32), c_f, c_fl, c_i, ctypes.POINTER(c_fl), c_f, c_f, c_f]),
     'danet_kp_fit_ws_floats': (c_sz, [c_i, c_i]),
     'danet_kp_fit': (c_i, [c_f, c_sz, c_f]),
+    'danet_fits_accept': (c_i, [c_f, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations
@@ -249,6 +250,13 @@ class KpFitArgs(ctypes.Structure):
                [('stage_iters', ctypes.c_int32 * 4), ('stage_mask', ctypes.c_int32 * 4)] + \
                [(k, ctypes.c_int32) for k in ('P', 'NB', 'S', 'Sp', 'NL', 'NE', 'nstages', 'T')] + \
                [(k, ctypes.c_float) for k in ('focal', 'res', 'kappa', 'sigma', 'w_orient', 'w_pose', 'w_shape', 'lr')]
+
+
+class FitsAcceptArgs(ctypes.Structure):
+    """struct danet_fits_accept_args (include/danet_hip.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ('para_fit', 'e_new', 'e_old', 'status_fit', 'status_eval', 'has_smpl', 'rows', 'rot_flip', 'kp',
+                                               'table', 'valid', 'updated')] + \
+               [('N', ctypes.c_int64), ('B', ctypes.c_int32), ('NB', ctypes.c_int32), ('tau', ctypes.c_float)]
 
 
 class ConvJob(ctypes.Structure):

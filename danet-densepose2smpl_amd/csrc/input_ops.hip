@@ -13,7 +13,7 @@
 //
 // Compiled with -ffp-contract=off: the tests restate the arithmetic operation by operation.
 #include "common.h"
-#include "rotation.h"
+#include "pose_aug.h"
 
 namespace {
 
@@ -86,59 +86,6 @@ __device__ __forceinline__ void j2d_point(const double* __restrict__ t, const do
     o[2] = kp[2];
 }
 
-// imutils.py:115-127 (augment.rot_aa): the axis-angle vector aa rotated by `rad` about the camera axis
-__device__ void rotate_global_orient(double* __restrict__ aa, double cs, double sn) {
-    double ang = sqrt(aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2]);
-    if (ang < 1e-12) ang = 1e-12;
-    const double ax = aa[0] / ang, ay = aa[1] / ang, az = aa[2] / ang;
-    const double s = sin(ang), c1 = 1.0 - cos(ang);
-    double R[9];                                                                      // I + s K + (1 - c) K K
-    R[0] = 1.0 + c1 * (-az * az - ay * ay); R[1] = -s * az + c1 * (ax * ay);         R[2] = s * ay + c1 * (ax * az);
-    R[3] = s * az + c1 * (ax * ay);         R[4] = 1.0 + c1 * (-az * az - ax * ax);  R[5] = -s * ax + c1 * (ay * az);
-    R[6] = -s * ay + c1 * (ax * az);        R[7] = s * ax + c1 * (ay * az);          R[8] = 1.0 + c1 * (-ay * ay - ax * ax);
-    double Q[9];                                                                      // Rz R
-    for (int k = 0; k < 3; ++k) {
-        Q[k] = cs * R[k] - sn * R[3 + k];
-        Q[3 + k] = sn * R[k] + cs * R[3 + k];
-        Q[6 + k] = R[6 + k];
-    }
-    danet::rotmat_to_angle_axis<double>(Q, aa);
-}
-
-// pose_processing (inverse = 0: rotate, then flip) or FitsDict.__setitem__'s undo (inverse = 1: flip, then rotate back);
-// `in` 72 numbers of type T, `sh` 72 doubles of LDS scratch, out fp32
-template <typename T>
-__device__ void pose_row(const T* __restrict__ in, double* __restrict__ sh, const Perms& pm, bool flip, bool inverse, double cs, double sn,
-                         float* __restrict__ out)
-{
-    for (int k = threadIdx.x; k < 72; k += kLabelThreads) {
-        double v;
-        if (inverse && flip) {
-            const int j = k / 3, a = k - j * 3;
-            v = (double)in[pm.smpl[j] * 3 + a];
-            if (a > 0) v = -v;
-        } else {
-            v = (double)in[k];
-        }
-        sh[k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) rotate_global_orient(sh, cs, sn);
-    __syncthreads();
-    for (int k = threadIdx.x; k < 72; k += kLabelThreads) {
-        double v;
-        if (!inverse && flip) {
-            const int j = k / 3, a = k - j * 3;
-            v = sh[pm.smpl[j] * 3 + a];
-            if (a > 0) v = -v;
-        } else {
-            v = sh[k];
-        }
-        out[k] = (float)v;
-    }
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(kLabelThreads) void label_augment_kernel(
     const double* __restrict__ xform, const double* __restrict__ rot_flip, const double* __restrict__ keypoints,
     const double* __restrict__ smpl_2dkps, const double* __restrict__ pose_3d, const double* __restrict__ pose,
@@ -185,16 +132,15 @@ __global__ __launch_bounds__(kLabelThreads) void label_augment_kernel(
             dst[0] = (float)x; dst[1] = (float)y; dst[2] = (float)S[2]; dst[3] = (float)S[3];
         }
     }
-    if (pose) pose_row<double>(pose + (size_t)b * 72, sh, pm, flip, inverse != 0, cs, sn, pose_out + (size_t)b * 72);
+    if (pose) danet::pose_row<double, kLabelThreads>(pose + (size_t)b * 72, sh, pm.smpl, flip, inverse != 0, cs, sn, pose_out + (size_t)b * 72);
     if (fits) {
-        pose_row<float>(fits + (size_t)b * 82, sh, pm, flip, inverse != 0, cs, sn, fits_pose_out + (size_t)b * 72);
+        danet::pose_row<float, kLabelThreads>(fits + (size_t)b * 82, sh, pm.smpl, flip, inverse != 0, cs, sn, fits_pose_out + (size_t)b * 72);
         if (tid < 10) fits_betas_out[(size_t)b * 10 + tid] = fits[(size_t)b * 82 + 72 + tid];
     }
 }
 
 const unsigned char kJ24Flip[24] = {5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13, 14, 15, 16, 17, 18, 19, 21, 20, 23, 22};
 const unsigned char kJ25Flip[25] = {0, 1, 5, 6, 7, 2, 3, 4, 8, 12, 13, 14, 9, 10, 11, 16, 15, 18, 17, 22, 23, 24, 19, 20, 21};
-const unsigned char kSmplFlip[24] = {0, 2, 1, 3, 5, 4, 6, 8, 7, 9, 11, 10, 12, 14, 13, 15, 17, 16, 19, 18, 21, 20, 23, 22};
 
 }  // namespace
 
@@ -225,7 +171,7 @@ extern "C" int danet_label_augment(const double* xform, const double* rot_flip, 
     DANET_CHECK_ARG(keypoints || smpl_2dkps || pose_3d || pose || fits, "label_augment: nothing to do");
     Perms pm;
     for (int j = 0; j < 25; ++j) pm.j49[j] = kJ25Flip[j];
-    for (int j = 0; j < 24; ++j) { pm.j49[25 + j] = (unsigned char)(25 + kJ24Flip[j]); pm.j24[j] = kJ24Flip[j]; pm.smpl[j] = kSmplFlip[j]; }
+    for (int j = 0; j < 24; ++j) { pm.j49[25 + j] = (unsigned char)(25 + kJ24Flip[j]); pm.j24[j] = kJ24Flip[j]; pm.smpl[j] = danet::kSmplFlip[j]; }
     hipLaunchKernelGGL(label_augment_kernel, dim3(B), dim3(kLabelThreads), 0, (hipStream_t)stream, xform, rot_flip, keypoints, smpl_2dkps,
                        pose_3d, pose, fits, pm, res, inverse, keypoints_out, smpl_2dkps_out, pose_3d_out, pose_out, fits_pose_out, fits_betas_out);
     DANET_CHECK_LAUNCH("label_augment_kernel");

@@ -1,6 +1,6 @@
 // Rotation matrix -> axis-angle under the rule of DESIGN.md ("axis-angle rule"; the convention of cv2.Rodrigues: angle in
-// [0, pi]), ONE device function for every caller: eval_ops.hip (fp32, danet_rotmat_to_angle_axis) and input_ops.hip (fp64,
-// the global orientation of an augmented pose).
+// [0, pi]), ONE device function for every caller: eval_ops.hip (fp32, danet_rotmat_to_angle_axis), pose_aug.h (fp64, the
+// global orientation of an augmented pose: input_ops.hip, fit_loop.hip) and fit_loop.hip (fp64, the 24 fitted matrices).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -14,7 +14,8 @@ class FitsDict(object):
     """FitsDict(options, train_dataset, final_fits_dir, static_fits_dir, device).  File rules of fits_dict.py:23-43: for every dataset
     of train_dataset.dataset_dict, <final_fits_dir>/<ds>.npy for 'h36m' (ground truth: every fit valid), <ds>.npz with pose, betas,
     valid_fit otherwise; if that file is missing <static_fits_dir>/<ds>_fits.npy (no fit of it counts as valid).  save() writes
-    <options.checkpoint_dir>/<ds>_fits.npy."""
+    <options.checkpoint_dir>/<ds>_fits.npy.  A run that refreshes the table (fit_loop.InLoopFit, options.run_smplify) keeps it with
+    its valid flags through save_state / load_state."""
 
     def __init__(self, options, train_dataset, final_fits_dir, static_fits_dir, device):
         self.options, self.train_dataset, self.device = options, train_dataset, torch.device(device)
@@ -63,6 +64,34 @@ class FitsDict(object):
         os.makedirs(self.options.checkpoint_dir, exist_ok=True)
         for ds_name, rows in self.fits_dict.items():
             np.save(os.path.join(self.options.checkpoint_dir, ds_name + '_fits.npy'), rows.cpu().numpy())
+
+    def save_state(self, directory):
+        """The table AND its valid flags, for a run that refreshes them (DESIGN.md 4d "the refresh rule"): <directory>/<ds>_fits.npy
+        as save() writes it, plus <ds>_valid_fit.npy (uint8 [N]).  Each call overwrites the last: only the newest state is kept."""
+        os.makedirs(directory, exist_ok=True)
+        flags = self.valid_fit_state
+        for ds_name, rows in self.fits_dict.items():
+            np.save(os.path.join(directory, ds_name + '_fits.npy'), rows.cpu().numpy())
+            np.save(os.path.join(directory, ds_name + '_valid_fit.npy'), flags[ds_name].cpu().numpy())
+
+    def load_state(self, directory):
+        """What save_state wrote, back into the table in place: a dataset is read where BOTH its files exist (the others keep what
+        the constructor read), a file of another shape raises ValueError before anything is changed.  -> the names read."""
+        found = {}
+        for ds_name, n in self.length.items():
+            ft, fv = (os.path.join(directory, ds_name + s) for s in ('_fits.npy', '_valid_fit.npy'))
+            if not (os.path.isfile(ft) and os.path.isfile(fv)):
+                continue
+            t, v = np.load(ft), np.load(fv)
+            if t.shape != (n, 82) or v.shape != (n,):
+                raise ValueError('fits state of %r in %s: expected [%d,82] parameters and [%d] flags, got %s and %s'
+                                 % (ds_name, directory, n, n, t.shape, v.shape))
+            found[ds_name] = (np.ascontiguousarray(t, dtype=np.float32), np.ascontiguousarray(v).astype(np.uint8))
+        for ds_name, (t, v) in found.items():
+            b = self.base[ds_name]
+            self.table[b:b + t.shape[0]].copy_(torch.from_numpy(t))
+            self.valid[b:b + v.shape[0]].copy_(torch.from_numpy(v))
+        return sorted(found)
 
     def rows(self, dataset_name, ind):
         """Row numbers in the one table (device int64 [B]); the dataset names are host strings, the indices may be on either side."""

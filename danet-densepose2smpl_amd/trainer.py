@@ -549,10 +549,13 @@ class Trainer(object):
     # The training loop: base_trainer.py:53-106 around the step prologue of train/trainer.py:134-212.  Steps run eagerly unless
     # options.graph asks for captured steps: `pretrain_mode` and `dp_active` are host switches that a captured graph freezes, so a
     # graphed run holds one graph per pretrain_mode phase and decides dp_active once, from the datasets of the run (_fit_step).
-    def build_in_dict(self, host_batch, fits_dict, train_data='h36m_dp', pretrain_mode=False, vis_on=False):
+    def build_in_dict(self, host_batch, fits_dict, train_data='h36m_dp', pretrain_mode=False, vis_on=False, run_smplify=None):
         """A collated loader batch (datasets.collate) -> the in_dict of train_step, all on the step's own stream: upload + the two
         input ops (datasets.to_device), the fits (fits_dict[...], one gather + the label op), valid_fit, prepare_batch.  vis_on: the
-        step's output will be looked at (base_trainer.py:73; fit sets it on visualisation steps)."""
+        step's output will be looked at (base_trainer.py:73; fit sets it on visualisation steps).  run_smplify (None:
+        self.options.run_smplify, absent = off): the in_dict also carries what the refresh stage needs to find each sample's table
+        row again -- 'fit_rows' int64 [B], 'fit_rot_flip' float64 [B,2] (degrees, flip: what the fetch was asked with) and
+        'fit_has_smpl' [B]; off, the key set is unchanged."""
         from . import datasets
         with self._on_stream():
             batch = datasets.to_device(host_batch, self.device, cfg.DANET.INIMG_SIZE)
@@ -566,7 +569,37 @@ class Trainer(object):
             batch['pretrain_mode'] = bool(pretrain_mode)
             in_dict = self.prepare_batch(batch, opt_pose, opt_betas)
             in_dict['dp_dict']['dp_active'] = bool(host_batch['dp_active'])
+            if getattr(self.options, 'run_smplify', False) if run_smplify is None else run_smplify:
+                in_dict['fit_rows'] = fits_dict.rows(batch['dataset_name'], batch['sample_index'])
+                in_dict['fit_rot_flip'] = fits_dict._rot_flip(batch['rot_angle'], batch['is_flipped'])
+                in_dict['fit_has_smpl'] = batch['has_smpl'].clone()
         return in_dict
+
+    def refresh_fits(self, looper, in_dict, output):
+        """The refresh stage of a step that has run (fit_loop.InLoopFit.refresh; DESIGN.md 4d "the refresh rule"), eagerly on the step's
+        stream: in_dict as the step saw it (of a replayed step the graph's static batch) and the step's output, both read before the
+        next step overwrites them.  The training output carries the predicted row in three pieces (output['prediction']: cam, shape,
+        pose), which are put back together here; an output with 'para' is taken as it is.  -> refresh's device tensors; nothing is
+        read on the host."""
+        with self._on_stream():
+            if 'para' in output:
+                para = output['para'].detach()
+            else:
+                pred = output['prediction']
+                para = torch.cat([pred['cam'].detach(), pred['shape'].detach(), pred['pose'].detach().reshape(-1, 216)], dim=1)
+            return looper.refresh(para, in_dict, in_dict['fit_rows'], in_dict['fit_rot_flip'], in_dict['fit_has_smpl'])
+
+    @staticmethod
+    def fit_summary(stats):
+        """refresh's tensors -> the four numbers of a summary line (ONE host read): fit_eligible and fit_updated are counts, fit_e_old
+        and fit_e_new means over the eligible samples (None with none, or where the mean is not finite)."""
+        el = stats['eligible']
+        elf = el.to(torch.float64)
+        zero = torch.zeros((), device=el.device, dtype=torch.float64)
+        mean = lambda e: torch.where(el, e.to(torch.float64), zero).sum() / elf.sum().clamp(min=1)      # noqa: E731
+        n, up, eo, en = torch.stack([elf.sum(), stats['updated'].to(torch.float64).sum(), mean(stats['e_old']), mean(stats['e_new'])]).tolist()
+        ok = lambda v: float(v) if n > 0 and np.isfinite(v) else None                                # noqa: E731
+        return {'fit_eligible': int(n), 'fit_updated': int(up), 'fit_e_old': ok(eo), 'fit_e_new': ok(en)}
 
     def _fit_step(self, in_dict):
         """One step of a graphed fit (see fit): eager for the first two steps of a pretrain_mode phase, a capture before the third,
@@ -737,7 +770,17 @@ class Trainer(object):
         options.test_steps (absent, None or 0: off; the reference's default is 1000) with val = (dataset_name, dataset): every step
         with step_count % test_steps == 0 (base_trainer.py:90) is followed, after its checkpoint, by self.test(val, options); the
         val_* numbers go into the step's JSON line (a line of its own where the summary schedule has none).  test_steps > 0 without
-        `val` raises ValueError before the first step.  Validation runs eagerly between replays and leaves the run alone (test)."""
+        `val` raises ValueError before the first step.  Validation runs eagerly between replays and leaves the run alone (test).
+        options.run_smplify (absent or False: off; DESIGN.md 4d "the refresh rule"): every step outside pretrain_mode is followed by
+        refresh_fits -- the prediction is fitted to the batch's keypoints (options.num_smplify_iters iterations; None: the fitter's
+        default) and replaces the stored pseudo-label where it explains them better; a refreshed row's valid flag follows
+        options.smplify_threshold.  The step trains on what the table held when its batch was built; the refreshed label is seen at
+        the sample's next visit.  Under options.graph the stage is a handful of eager launches after the replay, on the step's
+        stream, reading the graph's static batch and output; it is not part of the graph.  Summary lines gain fit_eligible,
+        fit_updated, fit_e_old, fit_e_new (fit_summary; the only host reads of the stage).  The table and its valid flags are
+        written to checkpoint_dir (FitsDict.save_state) with every checkpoint and when fit returns, and read back from there on
+        `resume`; only the newest state is kept, so resuming an older step_<n>.pt continues with the newest table.  With
+        world_size > 1 the option raises before the first step: each rank holds its own table and nothing reconciles them."""
         import json
         import time
         from . import checkpoint, datasets, evaluate, train_vis
@@ -745,6 +788,9 @@ class Trainer(object):
         test_steps = int(opt('test_steps', 0))
         if test_steps > 0 and val is None:
             raise ValueError('fit: options.test_steps = %d needs a validation set: pass val=(dataset_name, dataset)' % test_steps)
+        run_smplify = bool(opt('run_smplify', False))
+        if run_smplify and self.distributed:
+            raise RuntimeError('fit: options.run_smplify with world_size > 1: each rank holds its own FitsDict table and nothing reconciles them')
         bs, ckpt_dir, log_dir = int(options.batch_size), opt('checkpoint_dir', 'checkpoints'), opt('log_dir', 'logs')
         endtime = time.time() + float(opt('time_to_run', np.inf))
         book, epoch0 = None, 0
@@ -754,6 +800,8 @@ class Trainer(object):
             if path is not None:
                 book = self.resume(path, trusted=True)
                 epoch0 = int(book.get('epoch') or 0)
+            if run_smplify:
+                fits_dict.load_state(ckpt_dir)
         elif opt('pretrained_checkpoint', None):
             checkpoint.load_pretrained(self.model, options.pretrained_checkpoint)
         os.makedirs(log_dir, exist_ok=True)
@@ -768,7 +816,14 @@ class Trainer(object):
             self.drop_graph()                                              # (a graph of an earlier run: its phase is unknown here)
             self._fit_phase = (None, 0, 'dp_coco' in datasets.TRAIN_SETS.get(train_data, ()))
 
+        looper = None
+        if run_smplify:
+            from .fit_loop import InLoopFit
+            looper = InLoopFit(self.smpl, fits_dict, tau=opt('smplify_threshold', None), iters=opt('num_smplify_iters', None))
+
         def save(epoch, batch_idx, perm):
+            if run_smplify:
+                fits_dict.save_state(ckpt_dir)
             return self.save(os.path.join(ckpt_dir, 'step_%08d.pt' % self.step_count), epoch=epoch, batch_idx=batch_idx, batch_size=bs, dataset_perm=perm)
 
         with open(os.path.join(log_dir, 'train_log.jsonl'), 'a') as log:
@@ -777,11 +832,12 @@ class Trainer(object):
                                               num_workers=int(opt('num_workers', 0)), seed=int(opt('seed', 0)), epoch=epoch, res=cfg.DANET.INIMG_SIZE)
                 for step, host in enumerate(loader, loader.checkpoint_batch_idx):
                     if time.time() >= endtime:
-                        save(epoch, step, loader.sampler.dataset_perm)
+                        save(epoch, step, loader.sampler.dataset_perm)       # (with the table's state, when it is refreshed)
                         return ran
                     count = self.step_count + 1                            # (base_trainer.py:70-74: the step about to run)
                     vis_on = vis_interval > 0 if graphed else train_vis.vis_due(count, vis_interval)
-                    in_dict = self.build_in_dict(host, fits_dict, train_data, pretrain_mode=count <= int(opt('pretr_step', 0)), vis_on=vis_on)
+                    in_dict = self.build_in_dict(host, fits_dict, train_data, pretrain_mode=count <= int(opt('pretr_step', 0)), vis_on=vis_on,
+                                                 run_smplify=run_smplify)
                     if graphed:
                         output, losses, seen = self._fit_step(in_dict)
                     else:
@@ -789,11 +845,14 @@ class Trainer(object):
                         seen = in_dict
                         self.fit_stats['eager_steps'] += 1
                     ran += 1
+                    refreshed = None if looper is None or seen['pretrain_mode'] else self.refresh_fits(looper, seen, output)
                     line = None
                     if (self.step_count - 1) % int(opt('summary_steps', 100)) == 0:
                         vals = {'loss_' + k: float(v.detach()) for k, v in losses.items()}      # ('loss_{}'.format(key), train/trainer.py:221)
                         vals['loss_tatal'] = float(sum(vals.values()))
                         line = {'step': self.step_count, 'epoch': epoch, 'batch_idx': step, **vals}
+                        if refreshed is not None:
+                            line.update(self.fit_summary(refreshed))
                     if train_vis.vis_due(self.step_count, vis_interval):
                         line = line or {'step': self.step_count, 'epoch': epoch, 'batch_idx': step}
                         line.update(self.write_sheets(os.path.join(log_dir, 'vis', 'step_%08d' % self.step_count), self.visualize(seen, output, losses)))
@@ -813,4 +872,6 @@ class Trainer(object):
                 book = None                                                # (a checkpoint positions the first epoch only)
                 if (epoch + 1) % 10 == 0:
                     save(epoch + 1, 0, None)
+        if run_smplify:
+            fits_dict.save_state(ckpt_dir)
         return ran

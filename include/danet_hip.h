@@ -954,6 +954,33 @@ struct danet_kp_fit_args {
 size_t danet_kp_fit_ws_floats(int P, int Sp);
 int danet_kp_fit(const struct danet_kp_fit_args* args, size_t ws_floats, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The accept step of the in-loop fit (csrc/fit_loop.hip; fit_loop.py is the caller; DESIGN.md 4d "the refresh rule"): which of
+ * B fitted rows replace their pseudo-label in FitsDict's table, and the replacement.  ONE launch, one workgroup per sample, no
+ * atomics; a table row is written by at most one workgroup, so two runs give the same bits.
+ *
+ * para_fit [B, 3 + NB + 216] f32 as danet_kp_fit writes it (NB must be 10: the table's rows are 72 pose + 10 betas);
+ * e_new, e_old [B] f32: the data energies of the fitted row and of the stored label on the same keypoints; status_fit,
+ * status_eval [B] i32: danet_kp_fit's status of the fit and of the evaluation of the fitted row; has_smpl [B] f32; rows [B]
+ * i64: the table row of each sample (a row outside [0, N) is never written); rot_flip [B,2] f64 (degrees, flip) of the
+ * sample's augmentation; kp [B,49,3] f32 (the confidences are read).
+ * Sample b is accepted iff has_smpl == 0, both status words are 0, e_new is finite, !(e_old <= e_new), every |beta| <= 3 and
+ * the 82 values to be stored are finite; among the accepted samples of one row the lowest e_new wins, the lowest b on ties.
+ * A winner's row takes (rotate_pose(flip_pose(axis-angle of the 24 matrices, flip), -rot), betas), fp64 inside, and
+ * valid[row] = e_new < tau * sum_k confidence_k^2.  Everything else in table [N,82] f32 / valid [N] u8 keeps its bits.
+ * updated [B] i32: 1 where the sample's row was written.  The inputs must not overlap table / valid.
+ */
+struct danet_fits_accept_args {
+    const float* para_fit; const float* e_new; const float* e_old;
+    const int32_t* status_fit; const int32_t* status_eval;
+    const float* has_smpl; const int64_t* rows; const double* rot_flip; const float* kp;
+    float* table; uint8_t* valid; int32_t* updated;
+    int64_t N;
+    int32_t B, NB;
+    float tau;
+};
+int danet_fits_accept(const struct danet_fits_accept_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """Steady-state step time of Trainer.fit, eager and with options.graph, and the DensePose point-loss branch alone (HIP op against
 the tensor-op form).
 
-  python tools/fit_bench.py [--steps N] [--batch_size B] [--samples K] [--modes dp,eager,graph,vis] [--vis_interval K] [--out FILE]
+  python tools/fit_bench.py [--steps N] [--batch_size B] [--samples K] [--modes dp,eager,graph,vis] [--vis_interval K] [--run_smplify]
+                            [--out FILE]
 
 A synthetic 'h36m_dp' set (K + K samples, written to a scratch directory from a seed) is trained on at 256 x 256 with batch B, one
 process.  Each fit runs N steps after its warm-up (graphed: two eager steps and the capture; eager: three steps); the step time is the
@@ -9,7 +10,8 @@ difference of host timestamps taken in on_step after a device synchronise, so it
 build_in_dict alone is timed the same way.  The DensePose branch (forward + backward at B x 64 x 64) is timed with device events:
 median of 50 after 10 warm-up rounds.  --vis_interval K is passed on to the fits (a graphed fit then runs every step with the frozen
 vis_on = True); their step times are then reported separately for the steps that end in a visualisation.  Mode 'vis' times
-Trainer.visualize alone on one eager step's output: sheets built (device events), the copy to the host, the PNG encoding.  Last line: one JSON object.  Nothing outside the repository is read."""
+Trainer.visualize alone on one eager step's output: sheets built (device events), the copy to the host, the PNG encoding.
+--run_smplify switches the refresh stage of the fits on (options.run_smplify: the in-loop keypoint fit after every step).  Last line: one JSON object.  Nothing outside the repository is read."""
 import argparse
 import json
 import os
@@ -36,7 +38,7 @@ def fit_times(torch, train_ds, paths, a, graph, root):
     o = types.SimpleNamespace(batch_size=a.batch_size, openpose_train_weight=0., gt_train_weight=1., train_data='h36m_dp',
                               num_epochs=-(-(a.steps + warm) // per_epoch), pretr_step=0, checkpoint_steps=10 ** 9, summary_steps=10 ** 9, num_workers=8,
                               seed=3, shuffle_train=True, time_to_run=None, resume=None, pretrained_checkpoint=None, graph=graph,
-                              vis_interval=a.vis_interval,
+                              vis_interval=a.vis_interval, run_smplify=a.run_smplify,
                               log_dir=os.path.join(root, 'log_' + tag), checkpoint_dir=os.path.join(root, 'ck_' + tag))
     torch.manual_seed(0)
     tr = Trainer(o)
@@ -149,6 +151,7 @@ def main(argv=None):
     ap.add_argument('--out', default=None)
     ap.add_argument('--modes', default='dp,eager,graph', help="what to time: 'dp' (the DensePose branch alone), 'eager' / 'graph' (fit), 'vis' (Trainer.visualize)")
     ap.add_argument('--vis_interval', type=int, default=0, help='options.vis_interval of the fits (0: no visualisation)')
+    ap.add_argument('--run_smplify', action='store_true', help='options.run_smplify of the fits: the in-loop keypoint fit after every step')
     a = ap.parse_args(argv)
     import torch
     from danet_densepose2smpl_amd import datasets
@@ -158,7 +161,7 @@ def main(argv=None):
     reset_cfg()
     cfg_from_dict({'DANET.INIMG_SIZE': 256, 'DANET.HEATMAP_SIZE': 64})
     modes = a.modes.split(',')
-    res = {'batch_size': a.batch_size, 'steps': a.steps, 'vis_interval': a.vis_interval}
+    res = {'batch_size': a.batch_size, 'steps': a.steps, 'vis_interval': a.vis_interval, 'run_smplify': a.run_smplify}
     if 'dp' in modes:
         res['dp_branch'] = dp_branch_times(torch, a.batch_size)
     if 'eager' in modes or 'graph' in modes or 'vis' in modes:

@@ -4,6 +4,7 @@
                         [--checkpoint_steps K] [--summary_steps K] [--pretr_step K] [--resume] [--pretrained_checkpoint FILE]
                         [--num_workers W] [--ignore_3d] [--time_to_run SECONDS] [--cfg YAML] [--log_dir DIR] [--graph]
                         [--vis_interval K] [--test_steps K [--val_dataset NAME] [--val_annot FILE.npz --val_img_dir DIR] [--eval_pve]]
+                        [--run_smplify [--smplify_threshold TAU] [--num_smplify_iters N]]
 
 --data_root holds, for every dataset <ds> of --train_data, <ds>_train.npz (the reference's annotation layout), the image folder <ds>/
 and the fits folders final_fits/ and static_fits/.  Without it a small synthetic 'h36m_dp' set is written to a scratch directory and
@@ -12,7 +13,11 @@ one capture per pretrain_mode phase).  --vis_interval K (default 0 = off; the re
 Trainer.visualize to <log_dir>/<name>/vis/step_<n>/<tag>.png after every K-th step.  --test_steps K (default 0 = off; the reference's
 default is 1000, and its test() is empty) runs the evaluation loop of tools/eval.py on --val_dataset (default h36m-p2) after every K-th
 step and writes val_mpjpe, val_recon_err and, with --eval_pve, val_pve / val_pa_pve (mm) into that step's line of train_log.jsonl;
-without --val_annot a small synthetic validation set is written to the run's scratch directory.  Logs (train_log.jsonl) and checkpoints
+without --val_annot a small synthetic validation set is written to the run's scratch directory.  --run_smplify (default off) refreshes
+the pseudo-labels inside training (DESIGN.md 4d "the refresh rule"): after every step outside pretrain_mode the prediction is fitted to
+the batch's keypoints for --num_smplify_iters iterations (default 100) and replaces the stored fit where it explains them better; a
+refreshed row counts as a valid fit when its data energy is below --smplify_threshold (default sigma^2 / 5 of the fitter) times the
+summed squared confidences.  The table and its valid flags are kept beside the checkpoints and read back by --resume.  Logs (train_log.jsonl) and checkpoints
 go to <log_dir>/<name>/.
 Last line: one JSON object (steps run, last losses)."""
 import argparse
@@ -50,6 +55,10 @@ def build_parser():
     ap.add_argument('--val_annot', default=None, help='annotation .npz of the validation set (default: a synthetic one)')
     ap.add_argument('--val_img_dir', default=None)
     ap.add_argument('--eval_pve', action='store_true', help='validation also reports the per-vertex errors PVE / PA-PVE')
+    ap.add_argument('--run_smplify', action='store_true', help='refresh the pseudo-labels from keypoint fits of the predictions (one process only)')
+    ap.add_argument('--smplify_threshold', type=float, default=None,
+                    help='a refreshed fit is valid below this data energy per unit of squared confidence (default: sigma^2 / 5)')
+    ap.add_argument('--num_smplify_iters', type=int, default=100, help='iterations of the in-loop fit: 30 %% camera and orientation, then all')
     return ap
 
 
