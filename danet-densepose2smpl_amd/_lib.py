@@ -173,6 +173,9 @@ _SIGNATURES = {
     'danet_kp_fit_ws_floats': (c_sz, [c_i, c_i]),
     'danet_kp_fit': (c_i, [c_f, c_sz, c_f]),
     'danet_fits_accept': (c_i, [c_f, c_f]),
+    'danet_dense_landmarks': (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_f, c_f, c_f]),
+    'danet_dense_fit_ws_floats': (c_sz, [c_i, c_i]),
+    'danet_dense_fit': (c_i, [c_f, c_sz, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations
@@ -250,6 +253,17 @@ class KpFitArgs(ctypes.Structure):
                [('stage_iters', ctypes.c_int32 * 4), ('stage_mask', ctypes.c_int32 * 4)] + \
                [(k, ctypes.c_int32) for k in ('P', 'NB', 'S', 'Sp', 'NL', 'NE', 'nstages', 'T')] + \
                [(k, ctypes.c_float) for k in ('focal', 'res', 'kappa', 'sigma', 'w_orient', 'w_pose', 'w_shape', 'lr')]
+
+
+class DenseFitArgs(ctypes.Structure):
+    """struct danet_dense_fit_args (include/danet_hip.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ('para', 'kp', 'J_template', 'J_shapedirs', 'parents', 'v_template', 'basis', 'basisT', 'weights',
+                                               'jx', 'lm', 'jmap', 'ws', 'para_fit', 'history', 'best_iter', 'status', 'grad0',
+                                               'lm_corner', 'lm_w', 'csr_off', 'csr_lm', 'csr_w', 'obs', 'gate')] + \
+               [('stage_iters', ctypes.c_int32 * 4), ('stage_mask', ctypes.c_int32 * 4)] + \
+               [(k, ctypes.c_int32) for k in ('P', 'NB', 'S', 'Sp', 'NL', 'NE', 'nstages', 'T', 'M')] + \
+               [(k, ctypes.c_float) for k in ('focal', 'res', 'kappa', 'sigma', 'w_orient', 'w_pose', 'w_shape', 'lr',
+                                              'w_dense', 'sigma_dense', 'min_cos')]
 
 
 class FitsAcceptArgs(ctypes.Structure):

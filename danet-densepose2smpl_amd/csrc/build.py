@@ -58,6 +58,7 @@ UNITS = {
     'scene_ops.hip': ['-ffp-contract=off'],   # the scene rule's arithmetic is restated operation by operation in the tests
     'texture_ops.hip': ['-ffp-contract=off'],  # the texture rule likewise; its map is bit-equal to a float64 restatement
     'kp_fit.hip': [],
+    'dense_fit.hip': [],
     'fit_loop.hip': ['-ffp-contract=off'],    # the pose undo is input_ops.hip's (pose_aug.h): the same bits in both units
 }
 INCLUDES = {'norm_act_f32.hip': ['norm_act.hip']}

@@ -50,17 +50,20 @@ def parse_stages(stages):
     return iters, masks
 
 
-def fit_tables(smpl):
+def fit_tables(smpl, extra_verts=None):
     """The support sub-tables of an SMPL layer, as float64 / int32 numpy arrays (the layout csrc/kp_fit.hip reads, include/danet_hip.h):
     'support' [S] the vertex indices (ascending), 'S', 'Sp' (S padded to the tile), 'v_template' [Sp*3], 'basis' [207+NB, Sp*3]
     (posedirs rows, then shapedirs transposed), 'basisT' [Sp*3, 224], 'weights' [Sp,24], 'jx' [NE,Sp], 'lm' [NL] (position of each
-    landmark vertex in the support) and 'jmap' [49].  Padding is zero."""
+    landmark vertex in the support) and 'jmap' [49].  Padding is zero.  extra_verts: further mesh vertices for the support (the
+    dense fit's landmark corners)."""
     g = lambda n: getattr(smpl, n).detach().cpu().numpy()           # noqa: E731
     jx_full = g('J_regressor_extra').astype(np.float64)             # [NE,V]
     lmv = g('landmark_verts').astype(np.int64)
     V = g('v_template').shape[0]
     NB = smpl.num_betas
     support = np.union1d(lmv, np.nonzero((jx_full != 0).any(0))[0]).astype(np.int64)
+    if extra_verts is not None:
+        support = np.union1d(support, np.asarray(extra_verts, np.int64).reshape(-1))
     S = support.size
     Sp = -(-S // TILE) * TILE
     coords = (support[:, None] * 3 + np.arange(3)[None, :]).reshape(-1)

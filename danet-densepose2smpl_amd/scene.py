@@ -14,8 +14,9 @@ There is no CPU path: the ops raise on CPU tensors like every other op of the pa
 import numpy as np
 import torch
 
-from . import constants, datasets, ops
+from . import constants, datasets, iuvmap, ops
 from ._lib import GPU_ONLY
+from .dense_fit import DenseFitter
 from .renderer import ALBEDO, MeshRenderer
 from .smpl import from_para
 
@@ -137,6 +138,8 @@ class SceneDemo(object):
     """SceneDemo(model_or_engine, smpl, batch): a DaNet in eval mode on the GPU (its infer_net runs) or an InferenceEngine built at
     batch size `batch`; `smpl` the SMPL layer of the model (model.iuv2smpl.smpl).
 
+    With a dense_fit.DenseFitter as `fitter` the rows are refined on the network's own decoded IUV image (DESIGN.md "the dense fit
+    rule"), with no keypoints at all or with both terms where keypoints are given; the people dicts gain the same keys.
     With `fitter` (a kp_fit.KeypointFitter over the same SMPL layer) and `keypoints` -- per frame one [49,3] (or BODY_25 [25,3]) array
     per box, frame pixels and confidences -- the network's rows are refined against the keypoints before they are drawn (DESIGN.md
     "fit rule", scene kappa = 2 focal / 224); every people dict then also holds 'para_init' [k,229], 'fit_loss' [k,2] (initial and final
@@ -162,6 +165,11 @@ class SceneDemo(object):
             raise ValueError('SceneDemo: batch %d' % self.batch)
         self.mesh = MeshRenderer(smpl.faces, focal_length=self.focal, img_res=self.res)      # its face tables and lights
         self.fitter = fitter
+
+    @property
+    def dense(self):
+        """True where the fitter works on the predicted IUV image: no keypoints needed."""
+        return isinstance(self.fitter, DenseFitter)
 
     def prepare(self, frames, boxes):
         """Everything that does not depend on the network's answer.  -> plan (a dict): the packed frames and the per-person crop and
@@ -192,10 +200,11 @@ class SceneDemo(object):
         """The res x res network inputs of the plan's people [P,3,res,res] f32 (ImageNet-normalised, as the training input)."""
         return ops.batch_crop(*plan['crop'], self.res)
 
-    def infer(self, plan, crops=None):
-        """-> para [P,229] f32: the network on the crops in chunks of `batch`, a short last chunk padded with its last crop."""
+    def infer(self, plan, crops=None, return_iuv=False):
+        """-> para [P,229] f32: the network on the crops in chunks of `batch`, a short last chunk padded with its last crop.
+        return_iuv: -> (para, the decoded global IUV image of every person [P,3,S,S] f32, iuvmap.iuv_map2img of the prediction)."""
         crops = self.crops(plan) if crops is None else crops
-        paras = []
+        paras, iuvs = [], []
         for i in range(0, plan['P'], self.batch):
             chunk = crops[i:i + self.batch]
             n = chunk.shape[0]
@@ -203,7 +212,10 @@ class SceneDemo(object):
                 chunk = torch.cat([chunk, chunk[-1:].expand(self.batch - n, -1, -1, -1)], 0)
             out = self.engine(chunk.contiguous()) if self.engine is not None else self.model.infer_net(chunk.contiguous())
             paras.append(out['para'][:n].detach().clone())                 # (the engine's buffers live until its next call)
-        return torch.cat(paras, 0)
+            if return_iuv:
+                vis = out['visualization']['iuv_pred']
+                iuvs.append(iuvmap.iuv_map2img(vis[0], vis[1], vis[2], vis[3] if len(vis) > 3 else None)[:n].detach().clone())
+        return (torch.cat(paras, 0), torch.cat(iuvs, 0)) if return_iuv else torch.cat(paras, 0)
 
     def crop_keypoints(self, plan, keypoints):
         """Per frame one [49,3] or [25,3] array per box (frame pixels) -> [P,49,3] f32 on the device, normalised crop coordinates."""
@@ -215,12 +227,17 @@ class SceneDemo(object):
         t, _ = datasets.crop_transforms(plan['center'], plan['scale'], np.zeros(plan['P']), self.res)
         return torch.from_numpy(keypoints_to_crop(flat, t, self.res).astype(np.float32)).to(self.device)
 
-    def fit(self, para, plan, keypoints):
-        """para [P,229] refined against the plan's people's keypoints -> (para_fit, info), the scene camera's kappa = 2 focal / 224."""
+    def fit(self, para, plan, keypoints, iuv=None):
+        """para [P,229] refined against the plan's people's keypoints -> (para_fit, info), the scene camera's kappa = 2 focal / 224.
+        With a DenseFitter: against `iuv` (infer's decoded IUV images), and the keypoints too where there are some (or None)."""
         if self.fitter.res != self.res or self.fitter.focal != self.focal:
             raise ValueError('SceneDemo: the fitter was built for res %g, focal %g; the demo runs at res %d, focal %g'
                              % (self.fitter.res, self.fitter.focal, self.res, self.focal))
-        return self.fitter.fit(para, self.crop_keypoints(plan, keypoints), return_history=True, kappa=2.0 * self.focal / 224.0)
+        kappa = 2.0 * self.focal / 224.0
+        if self.dense:
+            kp = None if keypoints is None else self.crop_keypoints(plan, keypoints)
+            return self.fitter.fit(para, iuv, keypoints=kp, return_history=True, kappa=kappa)
+        return self.fitter.fit(para, self.crop_keypoints(plan, keypoints), return_history=True, kappa=kappa)
 
     def vertices(self, para):
         return from_para(self.smpl, para).vertices.detach()
@@ -249,12 +266,16 @@ class SceneDemo(object):
     def __call__(self, frames, boxes, keypoints=None):
         plan = self.prepare(frames, boxes)
         P = plan['P']
-        para = self.infer(plan) if P else torch.zeros(0, 229, device=self.device)
+        iuv = None
+        if P and self.dense:
+            para, iuv = self.infer(plan, return_iuv=True)
+        else:
+            para = self.infer(plan) if P else torch.zeros(0, 229, device=self.device)
         fitted = None
-        if self.fitter is not None and keypoints is not None:
+        if self.fitter is not None and (self.dense or keypoints is not None):
             fitted = (para, None)
             if P:
-                para_fit, info = self.fit(para, plan, keypoints)
+                para_fit, info = self.fit(para, plan, keypoints, iuv)
                 fitted, para = (para, info), para_fit
         verts = self.vertices(para) if P else None
         out = self.render(para, plan, vertices=verts)

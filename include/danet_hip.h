@@ -981,6 +981,46 @@ struct danet_fits_accept_args {
 };
 int danet_fits_accept(const struct danet_fits_accept_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Dense fit (csrc/dense_fit.hip; dense_fit.py is the caller; DESIGN.md "the dense fit rule"): the keypoint fit with a second data
+ * term that makes the mesh agree with an IUV image.  Landmarks are the M <= 24 G^2 mapped texels of the texel map at T = G.
+ *
+ * danet_dense_landmarks -- the observation, one launch, one wave per (person, landmark), double arithmetic in a fixed order:
+ *   iuv [P,3,S,S] f32 (plane 0 part / 24, planes 1, 2 U, V); cell [M,3] i32 = (part 1..24, i, j) of each landmark, its chart
+ *   coordinate being ((j + .5) / G, (i + .5) / G).  obs [P,M,3] f32 = (x, y, c): the mean of the pixel centres
+ *   ((col + .5) 2 / S - 1, (row + .5) 2 / S - 1) of the landmark's part under w = exp(-d2 / (2 tau^2)), d2 <= 9 tau^2, and
+ *   c = min(1, W), W the summed weight; a row with W < w_min is (0, 0, 0).  wsum [P,M] f32 or NULL receives W.
+ *
+ * danet_dense_fit -- the fit, ONE launch, one workgroup per person.  The fields of danet_kp_fit_args mean what they mean there,
+ * with the support enlarged by the landmarks' corners.  Added:
+ *   lm_corner [M,3] i32   position in the support of the three corners of the landmark's face, in the face's own order
+ *   lm_w      [M,3] f32   their barycentric weights
+ *   csr_off [Sp+1] i32, csr_lm [3M] i32, csr_w [3M] f32   the inverse: for every support vertex its (landmark, weight) pairs,
+ *                         ascending landmark
+ *   obs [P,M,3] f32       danet_dense_landmarks' output (or any (x, y, c) in the fit's image coordinates)
+ *   gate [P,M] i32        OUTPUT: 1 where the landmark's face looks at the camera at x_0 (cosine > min_cos); held for the whole fit
+ *   w_dense, sigma_dense, min_cos
+ * kp is required; a fit without keypoints passes zeros.  ws: danet_dense_fit_ws_floats(P, Sp) floats.
+ * The caller vouches for the extents of the tables and the ranges of their indices.
+ */
+int danet_dense_landmarks(const float* iuv, const int32_t* cell, int P, int M, int S, int G, double tau, double w_min,
+                          float* obs, float* wsum, void* stream);
+struct danet_dense_fit_args {
+    const float* para; const float* kp;
+    const float* J_template; const float* J_shapedirs; const int32_t* parents;
+    const float* v_template; const float* basis; const float* basisT; const float* weights; const float* jx;
+    const int32_t* lm; const int32_t* jmap;
+    float* ws;
+    float* para_fit; float* history; int32_t* best_iter; int32_t* status; float* grad0;
+    const int32_t* lm_corner; const float* lm_w; const int32_t* csr_off; const int32_t* csr_lm; const float* csr_w;
+    const float* obs; int32_t* gate;
+    int32_t stage_iters[4]; int32_t stage_mask[4];
+    int32_t P, NB, S, Sp, NL, NE, nstages, T, M;
+    float focal, res, kappa, sigma, w_orient, w_pose, w_shape, lr, w_dense, sigma_dense, min_cos;
+};
+size_t danet_dense_fit_ws_floats(int P, int Sp);
+int danet_dense_fit(const struct danet_dense_fit_args* args, size_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,11 @@ plus one <name>_texture.png, the 4 x 6 sheet of the 24 DensePose charts the phot
 With --fuse all images of the folder are views of ONE person: one atlas, fused_texture.png, drawn in every strip.
 
   python tools/demo.py --img_dir DIR --out_dir DIR [--checkpoint FILE] [--cfg YAML] [--mesh] [--engine] [--batch N]
-                       [--texture [--fuse] [--texture_size T]]
+                       [--texture [--fuse] [--texture_size T]] [--fit_iuv [--fit_iters N]]
+
+--fit_iuv refines every predicted row on the network's own decoded global IUV image before anything is drawn (dense_fit.DenseFitter,
+DESIGN.md "the dense fit rule", the training camera): the mesh panels, the IUV rendering and the textures come from the fitted row;
+the decoded IUV panels stay the network's.
 
 Images: .npy arrays always ([S,S,3] or [3,S,S], uint8 or float in [0,1]); .jpg / .png if PIL is installed.  They must be square
 at DANET.INIMG_SIZE (cropping is augment.py's job).  Without --checkpoint the model has seeded random weights and the synthetic
@@ -87,7 +91,11 @@ def main(argv=None):
     ap.add_argument('--engine', action='store_true', help='run the BatchNorm-folded InferenceEngine instead of infer_net')
     ap.add_argument('--batch', type=int, default=1)
     ap.add_argument('--reps', type=int, default=20, help='timed repetitions of the panel stage (0: no timing)')
+    ap.add_argument('--fit_iuv', action='store_true', help='refine every row on the predicted IUV image before drawing')
+    ap.add_argument('--fit_iters', type=int, default=100, help='with --fit_iuv: iterations of the fit')
     a = ap.parse_args(argv)
+    if a.fit_iuv and a.fit_iters < 1:
+        raise SystemExit('--fit_iters %d' % a.fit_iters)
 
     import torch
     from danet_densepose2smpl_amd import checkpoint, demo
@@ -118,6 +126,12 @@ def main(argv=None):
     if a.fuse and not a.texture:
         raise SystemExit('--fuse needs --texture')
     tex = TextureAtlas(size=a.texture_size) if a.texture else None
+    fitter = None
+    if a.fit_iuv:
+        from danet_densepose2smpl_amd import iuvmap
+        from danet_densepose2smpl_amd.dense_fit import DenseFitter
+        n0 = (3 * a.fit_iters) // 10
+        fitter = DenseFitter(smpl, stages=((n0, 'cam+orient'), (a.fit_iters - n0, 'all')), res=S)
     sheet_png = lambda atlas: to_uint8(tex.sheet(atlas).permute(0, 2, 3, 1).cpu().numpy())           # noqa: E731
 
     def batches():
@@ -127,6 +141,11 @@ def main(argv=None):
             chunk = chunk + [chunk[-1]] * (a.batch - n)            # a short last batch is padded, its extra strips dropped
             image = torch.from_numpy(np.stack(chunk)).cuda()
             out = engine(image) if engine is not None else model.infer_net(image)
+            if fitter is not None:                                 # the fitted row replaces the network's; its vertices are made anew
+                vis = out['visualization']['iuv_pred']
+                iuv = iuvmap.iuv_map2img(vis[0], vis[1], vis[2], vis[3] if len(vis) > 3 else None)
+                out = dict(out, para=fitter.fit(out['para'].detach().float(), iuv))
+                out.pop('vertices', None)
             yield i, n, image, out
 
     texture = tex

@@ -5,14 +5,16 @@ triple per person, <name>_<k>.obj + <name>_<k>.mtl + <name>_<k>_texture.png: the
 through the crop camera (texture.TextureAtlas, texture.write_textured_obj).  The scene picture is the same either way.
 
   python tools/demo_scene.py --img_dir DIR --out_dir DIR [--boxes FILE.json] [--keypoints_dir DIR] [--checkpoint FILE] [--cfg YAML]
-                             [--engine] [--batch N] [--obj [--texture [--texture_size T]]] [--fit [--fit_iters N]]
+                             [--engine] [--batch N] [--obj [--texture [--texture_size T]]] [--fit | --fit_iuv [--fit_iters N]]
 
 Boxes: --boxes maps an image's file name to a list of [x, y, w, h]; --keypoints_dir holds <name>_keypoints.json in OpenPose's layout
 (one person per people[] entry, pose_keypoints_2d = x, y, confidence, ...); with neither, the whole image is one box.  There is no
 person detector here.  --fit (needs --keypoints_dir; refused with --boxes, there is no rule here for matching boxes to people) refines
 every person's predicted row against the person's BODY_25 keypoints before it is drawn (kp_fit.KeypointFitter, DESIGN.md "fit rule";
 --fit_iters N iterations, 30 % of them on camera and global orientation alone); the _people.npz then also holds para_init, fit_loss
-(initial and final energy) and fit_iter.  Images: .npy arrays always (uint8 [H,W,3]); .jpg / .png if PIL is installed.  Without --checkpoint the model
+(initial and final energy) and fit_iter.  --fit_iuv refines every person on the network's own decoded IUV image instead
+(dense_fit.DenseFitter, DESIGN.md "the dense fit rule"): it needs no keypoints, and with --keypoints_dir (again not with --boxes) both
+terms are fitted together; the _people.npz gains the same three arrays.  Images: .npy arrays always (uint8 [H,W,3]); .jpg / .png if PIL is installed.  Without --checkpoint the model
 has seeded random weights and the synthetic SMPL / DensePose tables, so the tool runs on a clean checkout.  The PNG files are written
 by train_vis.write_png.  Last line: one JSON object with the milliseconds per frame of the three device stages (crop: ops.batch_crop;
 infer: the network; render: SMPL forward, shading and ops.scene_render) on the last group of frames, HIP events, the median and
@@ -100,8 +102,17 @@ def main(argv=None):
     ap.add_argument('--texture_size', type=int, default=64, help='texels per side of a chart')
     ap.add_argument('--reps', type=int, default=20, help='timed repetitions of the three stages (0: no timing)')
     ap.add_argument('--fit', action='store_true', help='refine every person against the keypoints of --keypoints_dir before drawing')
-    ap.add_argument('--fit_iters', type=int, default=100, help='with --fit: iterations of the fit')
+    ap.add_argument('--fit_iuv', action='store_true', help='refine every person on the predicted IUV image before drawing (and on the '
+                    'keypoints of --keypoints_dir, if given)')
+    ap.add_argument('--fit_iters', type=int, default=100, help='with --fit / --fit_iuv: iterations of the fit')
     a = ap.parse_args(argv)
+    if a.fit and a.fit_iuv:
+        raise SystemExit('--fit and --fit_iuv: one of the two (--fit_iuv --keypoints_dir DIR fits both terms)')
+    if a.fit_iuv and a.keypoints_dir and a.boxes:
+        raise SystemExit('--fit_iuv with --keypoints_dir cannot be combined with --boxes: there is no rule here for matching boxes to the '
+                         'people of the keypoint files')
+    if a.fit_iuv and a.fit_iters < 1:
+        raise SystemExit('--fit_iters %d' % a.fit_iters)
     if a.fit and a.boxes:
         raise SystemExit('--fit cannot be combined with --boxes: there is no rule here for matching boxes to the people of the keypoint files')
     if a.fit and not a.keypoints_dir:
@@ -138,6 +149,11 @@ def main(argv=None):
         from danet_densepose2smpl_amd.kp_fit import KeypointFitter
         n0 = (3 * a.fit_iters) // 10
         demo.fitter = KeypointFitter(smpl, stages=((n0, 'cam+orient'), (a.fit_iters - n0, 'all')), focal=demo.focal, res=demo.res)
+    if a.fit_iuv:
+        from danet_densepose2smpl_amd.dense_fit import DenseFitter
+        n0 = (3 * a.fit_iters) // 10
+        demo.fitter = DenseFitter(smpl, stages=((n0, 'cam+orient'), (a.fit_iters - n0, 'all')), focal=demo.focal, res=demo.res)
+    with_kp = a.fit or (a.fit_iuv and a.keypoints_dir is not None)
     tex = texture.TextureAtlas(size=a.texture_size, focal_length=demo.focal) if a.texture else None
 
     last, people_total = None, 0
@@ -145,7 +161,7 @@ def main(argv=None):
         group = names[i:i + GROUP]
         frames = [load_frame(os.path.join(a.img_dir, n)) for n in group]
         boxes = [boxes_of(n, f, box_table, a.keypoints_dir) for n, f in zip(group, frames)]
-        rendered, people = demo(frames, boxes, [keypoints_of(n, a.keypoints_dir) for n in group] if a.fit else None)
+        rendered, people = demo(frames, boxes, [keypoints_of(n, a.keypoints_dir) for n in group] if with_kp else None)
         sheets = None
         if tex is not None and any(boxes):                          # every person's crop, de-normalised, through the crop camera
             mean, std = (torch.tensor(c, device=demo.device).view(1, 3, 1, 1) for c in (constants.IMG_NORM_MEAN, constants.IMG_NORM_STD))
