@@ -1021,6 +1021,36 @@ struct danet_dense_fit_args {
 size_t danet_dense_fit_ws_floats(int P, int Sp);
 int danet_dense_fit(const struct danet_dense_fit_args* args, size_t ws_floats, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Video tracks (csrc/track_ops.hip; tracks.py is the caller; DESIGN.md 4b'-track "the track rule").  Rows are track-major:
+ * track k owns rows track_start[k] .. track_start[k+1]-1, one per frame of its span, in time order.  track_start [K+1] i32 is
+ * passed twice: the device copy the kernels read and the HOST copy the entry point validates (0 .. N, ascending) before anything is
+ * launched.  conf [N] f32, the row weights: the caller vouches that they are finite and not negative.
+ *
+ * danet_track_smooth -- every channel of every track is replaced by the minimiser of
+ *     sum_t (c_t + 1e-6)(x_t - y_t)^2 + lam_vel sum (x_t - x_{t-1})^2 + lam_acc sum (x_{t+1} - 2 x_t + x_{t-1})^2,
+ *   y_t the input where c_t > 0 and the track's weighted mean elsewhere (rows with c_t = 0 are never read), solved by banded
+ *   L D L^T in double and rounded to fp32 once.  values, out [N,C] f32 (out must not be values); status [K] i32: 1 for a track
+ *   without a positive weight, whose rows come back bit for bit.  Two launches.
+ * danet_track_smooth_para -- the same on the 157 unknowns of the fit rule inside para [N,229] rows (cam, betas, the first two
+ *   columns of the 24 matrices), lam [6] HOST = (lam_vel, lam_acc) of cam, betas, rotations.  Afterwards s is clamped to the range
+ *   of the track's observed s, with shared_shape every row of a track gets the weighted mean betas, and the six rounded numbers of
+ *   each joint go through the 6D map: out [N,229] holds (cam, betas, 24 rotation matrices) again.  Three launches.
+ * danet_track_accel -- joints (and joints_ref or NULL) [N,J,3] f32 -> accel [K] f64, the mean over interior rows and joints of
+ *   |x_{t+1} - 2 x_t + x_{t-1}| (of joints - joints_ref with a reference), and count [K] i32 = (T - 2) J, both 0 where T < 3.
+ * ws: danet_track_smooth_ws_bytes(N, C) bytes (C = 157 for the para form), 8-byte aligned, owned by the launches while they run.
+ * No atomics, no grid barrier, fixed orders: two runs give the same bits, and a track's result does not depend on the others.
+ */
+size_t danet_track_smooth_ws_bytes(long N, int C);
+int danet_track_smooth(const float* values, const float* conf, const int32_t* track_start, const int32_t* track_start_host,
+                       long N, int C, int K, double lam_vel, double lam_acc, float* out, int32_t* status, void* ws,
+                       size_t ws_bytes, void* stream);
+int danet_track_smooth_para(const float* para, const float* conf, const int32_t* track_start, const int32_t* track_start_host,
+                            long N, int K, const double* lam, int shared_shape, float* out, int32_t* status, void* ws,
+                            size_t ws_bytes, void* stream);
+int danet_track_accel(const float* joints, const float* joints_ref, const int32_t* track_start, const int32_t* track_start_host,
+                      long N, int J, int K, double* accel, int32_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,145 @@
+"""The frames of a clip plus person boxes per frame in, the frames with every person's mesh drawn in place out -- the people followed
+across frames, their boxes and SMPL rows smoothed along each track, and a person whose box is missing in a frame filled in
+(video.VideoDemo, DESIGN.md 4b'-track "the track rule").  Writes <name>_scene.png per frame and ONE tracks.npz: the TrackSet arrays
+(track_start, frame, det, conf, person_row, row_person), para_raw and para [N,229] (the network's rows and the final ones, track-major),
+boxes_raw and boxes [N,3] (cx, cy, log scale before and after the box smoother), accel_raw and accel [K] (the mean acceleration of
+the SMPL joints per track before and after).
+
+  python tools/demo_video.py --frames_dir DIR --out_dir DIR --boxes FILE.json [--keypoints_dir DIR] [--fit | --fit_iuv] [--rounds R]
+                             [--no_smooth] [--engine] [--batch N] [--checkpoint FILE] [--cfg YAML] [--fit_iters N]
+
+Frames are taken in name order; the input conventions are those of tools/demo_scene.py: .npy arrays always (uint8 [H,W,3]), .jpg / .png
+if PIL is installed; --boxes maps a frame's file name to a list of [x, y, w, h] or [x, y, w, h, confidence]; --keypoints_dir holds
+<name>_keypoints.json in OpenPose's layout, and with it the boxes come from the keypoints (so --fit, which needs it, is refused with
+--boxes, as in the scene tool: there is no rule for matching boxes to the people of the keypoint files).  The whole clip is one call: it must fit on the
+device.  There is no video decoder, no person detector and no causal filter here.  Last line: one JSON object with the counts and the
+milliseconds per frame of every stage (host clock around a device synchronisation, one run: the clip is processed once)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from danet_densepose2smpl_amd.train_vis import write_png       # noqa: E402
+from demo_scene import boxes_of, keypoints_of, load_frame       # noqa: E402
+
+
+def frame_boxes(name, frame, box_table, keypoints_dir):
+    """demo_scene.boxes_of, with a fifth number of a --boxes entry as the box's confidence."""
+    from danet_densepose2smpl_amd import scene
+    if box_table is None:
+        return boxes_of(name, frame, None, keypoints_dir)
+    out = []
+    for b in box_table.get(name, box_table.get(os.path.splitext(name)[0], [])):
+        c, s = scene.boxes_from_xywh(b[:4])
+        out.append((c, s, float(b[4])) if len(b) > 4 else (c, s))
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description='DaNet video demo: tracked, smoothed meshes drawn into the frames of a clip')
+    ap.add_argument('--cfg', dest='cfg_file', default=None)
+    ap.add_argument('--checkpoint', default=None)
+    ap.add_argument('--frames_dir', required=True)
+    ap.add_argument('--out_dir', default='./output')
+    ap.add_argument('--boxes', default=None, help='JSON: frame name -> list of [x, y, w, h] or [x, y, w, h, confidence]')
+    ap.add_argument('--keypoints_dir', default=None)
+    ap.add_argument('--fit', action='store_true', help='refine every row against the keypoints of --keypoints_dir in every round')
+    ap.add_argument('--fit_iuv', action='store_true', help='refine every row on the predicted IUV image in every round')
+    ap.add_argument('--fit_iters', type=int, default=100)
+    ap.add_argument('--rounds', type=int, default=1, help='fit-then-smooth rounds')
+    ap.add_argument('--no_smooth', action='store_true')
+    ap.add_argument('--engine', action='store_true')
+    ap.add_argument('--batch', type=int, default=1)
+    a = ap.parse_args(argv)
+    if a.fit and a.fit_iuv:
+        raise SystemExit('--fit and --fit_iuv: one of the two (--fit_iuv --keypoints_dir DIR fits both terms)')
+    if (a.fit or (a.fit_iuv and a.keypoints_dir)) and a.boxes:
+        raise SystemExit('keypoints cannot be combined with --boxes: there is no rule here for matching boxes to the people of the keypoint files')
+    if a.fit and not a.keypoints_dir:
+        raise SystemExit('--fit needs --keypoints_dir')
+    if not a.boxes and not a.keypoints_dir:
+        raise SystemExit('--boxes or --keypoints_dir: a clip needs person boxes per frame')
+    if a.fit_iters < 1 or a.rounds < 1:
+        raise SystemExit('--fit_iters %d --rounds %d' % (a.fit_iters, a.rounds))
+
+    import torch
+    from danet_densepose2smpl_amd import checkpoint, video
+    from danet_densepose2smpl_amd.config import cfg_from_file
+    from danet_densepose2smpl_amd.danet import DaNet
+    from danet_densepose2smpl_amd.trainer import default_options
+    if not torch.cuda.is_available():
+        raise SystemExit('tools/demo_video.py needs a GPU (there is no CPU path)')
+    if a.cfg_file:
+        cfg_from_file(a.cfg_file)
+    names = sorted(n for n in os.listdir(a.frames_dir) if n.lower().endswith(('.npy', '.jpg', '.jpeg', '.png')) and not n.endswith('_scene.png'))
+    if not names:
+        raise SystemExit('no .npy / .jpg / .png frames in %s' % a.frames_dir)
+    box_table = json.load(open(a.boxes)) if a.boxes else None
+    os.makedirs(a.out_dir, exist_ok=True)
+
+    torch.manual_seed(0)
+    model = DaNet(default_options(a.batch), None, pretrained=False)
+    if a.checkpoint:
+        checkpoint.load_pretrained(model, a.checkpoint)
+    model = model.cuda().eval()
+    smpl = model.iuv2smpl.smpl
+    engine = model.inference_engine(a.batch) if a.engine else None
+    demo = video.VideoDemo(engine if engine is not None else model, smpl, a.batch, smooth=not a.no_smooth, rounds=a.rounds)
+    n0 = (3 * a.fit_iters) // 10
+    stages = ((n0, 'cam+orient'), (a.fit_iters - n0, 'all'))
+    if a.fit:
+        from danet_densepose2smpl_amd.kp_fit import KeypointFitter
+        demo.scene.fitter = KeypointFitter(smpl, stages=stages, focal=demo.scene.focal, res=demo.scene.res)
+    if a.fit_iuv:
+        from danet_densepose2smpl_amd.dense_fit import DenseFitter
+        demo.scene.fitter = DenseFitter(smpl, stages=stages, focal=demo.scene.focal, res=demo.scene.res)
+    with_kp = a.fit or (a.fit_iuv and a.keypoints_dir is not None)
+
+    frames = [load_frame(os.path.join(a.frames_dir, n)) for n in names]
+    boxes = [frame_boxes(n, f, box_table, a.keypoints_dir) for n, f in zip(names, frames)]
+    keypoints = [keypoints_of(n, a.keypoints_dir) for n in names] if with_kp else None
+
+    # the stages once by hand for the clock; the results come from the one call below
+    ms = {}
+
+    def timed(key, f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = f()
+        torch.cuda.synchronize()
+        ms[key] = ms.get(key, 0.0) + (time.perf_counter() - t0) * 1e3
+        return r
+
+    from danet_densepose2smpl_amd import tracks as tr
+    ts = timed('associate', lambda: tr.associate(boxes, demo.max_gap, demo.min_iou))
+    _, _, _, per_frame = timed('boxes', lambda: demo.track_boxes(boxes))
+    plan = timed('prepare', lambda: demo.scene.prepare(frames, per_frame))
+    if plan['P']:
+        para = timed('infer', lambda: demo.scene.infer(plan))
+        rows = para[torch.from_numpy(ts.row_person).to(para.device)]
+        timed('smooth', lambda: tr.smooth_para(rows, ts, demo.lam, demo.shared_shape))
+        timed('render', lambda: demo.scene.render(para, plan))
+    rendered, people, summary = timed('total', lambda: demo(frames, boxes, keypoints))
+    for n, img in zip(names, rendered):
+        write_png(os.path.join(a.out_dir, os.path.splitext(n)[0] + '_scene.png'), img)
+    last = demo.last
+    np.savez(os.path.join(a.out_dir, 'tracks.npz'), para_raw=last['para_raw'], para=last['para'], boxes_raw=last['boxes_raw'], boxes=last['boxes'],
+             accel_raw=summary['accel_raw_tracks'], accel=summary['accel_tracks'], **last['tracks'].arrays())
+    print('Video demo results (%d frames, %d tracks, %d rows) have been saved in %s.' % (len(names), summary['tracks'], summary['rows'], a.out_dir))
+    res = {'tool': 'demo_video', 'frames': len(frames), 'tracks': summary['tracks'], 'rows': summary['rows'], 'gap_rows': summary['gap_rows'],
+           'accel_raw': summary['accel_raw'], 'accel': summary['accel'], 'batch': a.batch, 'engine': bool(a.engine), 'smooth': not a.no_smooth,
+           'rounds': a.rounds, 'fit': 'keypoints' if a.fit else ('iuv' if a.fit_iuv else None),
+           'ms_per_frame': {k: round(v / len(frames), 4) for k, v in ms.items()}}
+    print(json.dumps(res), flush=True)
+    if engine is not None:
+        engine.close()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
