@@ -182,6 +182,9 @@ _SIGNATURES = {
     'danet_track_smooth_para': (c_i, [c_f, c_f, c_f, ctypes.POINTER(ctypes.c_int32), ctypes.c_long, c_i, ctypes.POINTER(ctypes.c_double), c_i,
                                       c_f, c_f, c_f, c_sz, c_f]),
     'danet_track_accel': (c_i, [c_f, c_f, c_f, ctypes.POINTER(ctypes.c_int32), ctypes.c_long, c_i, c_i, c_f, c_f, c_f]),
+    'danet_track_stream_state_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
+    'danet_track_stream_step': (c_i, [c_f, c_sz, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, ctypes.c_double, ctypes.c_double, c_f, c_f, c_f]),
+    'danet_track_stream_step_para': (c_i, [c_f, c_sz, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, ctypes.POINTER(ctypes.c_double), c_i, c_f, c_f, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations

@@ -6,8 +6,10 @@ DESIGN.md 4b'-track "the track rule") and the frames in which a person has no bo
     rendered, people, summary = demo(frames, boxes, keypoints=None)
 
 A VideoDemo wraps a scene.SceneDemo and calls its stages; the scene demo itself is what it was.  The whole clip is one call: every
-row of every track is on the device at once.  Not here: video decoding, a person detector, online or causal filtering, clips that do
-not fit on the device.  There is no CPU path."""
+row of every track is on the device at once.  StreamDemo (below) is the same pipeline fed one frame at a time: online association, an
+exact fixed-lag smoother (tracks.StreamSmoother, DESIGN.md 4b'-stream "the stream rule") and a bounded number of frames held, for
+clips that do not fit on the device and for live sources.  Not here: video decoding, a person detector, re-identification, motion
+prediction, several ranks.  There is no CPU path."""
 import numpy as np
 import torch
 
@@ -143,3 +145,245 @@ class VideoDemo(object):
         self.last = {'tracks': ts, 'plan': plan, 'render_aux': aux, 'boxes_raw': boxes_raw, 'boxes': boxes_s,
                      'para_raw': raw_h[ts.row_person] if P else raw_h, 'para': para_h[ts.row_person] if P else para_h}
         return rendered, people, summary
+
+
+STREAM_LAG = 8          # the default lag and box_lag of StreamDemo: DESIGN.md 4b'-stream, the lag table
+
+
+class StreamDemo(object):
+    """StreamDemo(model_or_engine, smpl, batch, fitter=None, smooth=True, lag=8, box_lag=8, slots=32, shared_shape=True, max_gap=5,
+    min_iou=0.3, gap_conf=0., lam=tracks.DEFAULT_LAM, box_lam=tracks.BOX_LAM, **scene_kw): VideoDemo's pipeline fed one frame at a
+    time (DESIGN.md 4b'-stream "the stream rule").
+
+        done = demo.push(frame, boxes, keypoints=None)       # [] or [(frame_index, rendered, people)]
+        rest, summary = demo.flush()
+
+    Frame f enters the association (tracks.OnlineAssociator) and the box stream; frame g = f - box_lag gets its smoothed boxes, gap
+    rows included (box_lag >= max_gap is what makes "gap row or ended track" decidable for it), is cropped, inferred and, where there is
+    a fitter, fitted once; its rows enter the para stream (tracks.StreamSmoother, one launch per frame for every track), and frame
+    g - lag is drawn: a delay of box_lag + lag frames, at most box_lag + lag + 1 frames held.  Every value drawn is the offline rule on
+    the track's committed prefix; people dicts carry VideoDemo's keys plus 'prefix_end' [k], the last frame of the prefix each row was
+    computed from.  With shared_shape a track's shape is its prefix's mean and so moves over time.  A track holds one of `slots` slots
+    from its first box until its last row is drawn.  There is no `rounds`: the fit / smooth alternation needs whole tracks and stays
+    VideoDemo's.  With smooth = False observed rows keep their own box and row, and gap rows get the box stream's box.  Wraps a
+    scene.SceneDemo and does not change it; there is no CPU path."""
+
+    @staticmethod
+    def check_arguments(lag, box_lag, slots, max_gap, gap_conf):
+        for name, v, low in (('lag', lag, 0), ('box_lag', box_lag, 0), ('slots', slots, 1), ('max_gap', max_gap, 1)):
+            if isinstance(v, bool) or int(v) != v or v < low:
+                raise ValueError('StreamDemo: %s %r (an integer >= %d)' % (name, v, low))
+        if box_lag < max_gap:
+            raise ValueError('StreamDemo: box_lag %d is below max_gap %d: a frame would be emitted before its gap rows are known' % (box_lag, max_gap))
+        if not (np.isfinite(gap_conf) and 0.0 <= gap_conf <= 1.0):
+            raise ValueError('StreamDemo: gap_conf %r (in [0, 1])' % (gap_conf,))
+
+    def __init__(self, model_or_engine, smpl, batch, fitter=None, smooth=True, lag=STREAM_LAG, box_lag=STREAM_LAG, slots=32, shared_shape=True,
+                 max_gap=5, min_iou=0.3, gap_conf=0., lam=tr.DEFAULT_LAM, box_lam=tr.BOX_LAM, **scene_kw):
+        self.check_arguments(lag, box_lag, slots, max_gap, gap_conf)
+        self.assoc = tr.OnlineAssociator(max_gap, min_iou, what='StreamDemo')
+        self.smooth, self.lag, self.box_lag, self.slots = bool(smooth), int(lag), int(box_lag), int(slots)
+        self.max_gap, self.gap_conf = int(max_gap), float(gap_conf)
+        self.box_stream = tr.StreamSmoother(self.slots, self.box_lag, max_new=self.max_gap, channels=3, lam=box_lam)
+        self.para_stream = tr.StreamSmoother(self.slots, self.lag, para=True, lam=lam, shared_shape=shared_shape)
+        self.scene = SceneDemo(model_or_engine, smpl, batch, fitter=fitter, **scene_kw)
+        self.free = list(range(self.slots))
+        self.slot = {}                       # track -> slot, while it holds one
+        self.boxed = {}                      # track -> the last frame whose box row went into the box stream
+        self.held = {}                       # frame -> what is kept of it until it is drawn
+        self.rows = {}                       # (track, frame) -> (para_raw [229], para [229]) of every row drawn, for the summary
+        self.box_rows = {}                   # (track, frame) -> (box_raw [3] or None in a gap row, box [3] after the box stream)
+        self.time = 0                        # frames pushed plus the flush's steps
+        self.max_held = 0
+        self.timing, self.ms = False, {}     # timing: a device synchronisation around every stage, milliseconds summed per stage in ms
+        self.last = {}
+
+    def _timed(self, key, f):
+        if not self.timing:
+            return f()
+        import time
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = f()
+        torch.cuda.synchronize()
+        self.ms[key] = self.ms.get(key, 0.0) + (time.perf_counter() - t0) * 1e3
+        return r
+
+    # ---- the three stages of one step ------------------------------------------------------------------------------------------------
+    def _span(self, k):
+        r = self.assoc.tracks[k]['rows']
+        return r[0][0], r[-1][0]
+
+    def _covering(self, frame):
+        return [k for k in sorted(self.slot) if self._span(k)[0] <= frame <= self._span(k)[1]]
+
+    def _box_step(self, matches, g):
+        """The new committed box rows of this frame's matched tracks go in; the boxes of frame g (or None) come out: {track: [3]}."""
+        st, S, M = self.box_stream, self.slots, self.max_gap
+        n_new, emit = np.zeros(S, np.int64), np.full(S, -1, np.int64)
+        rows, conf = np.zeros((S, M, 3), np.float32), np.zeros((S, M), np.float32)
+        f = self.assoc.n_frames - 1
+        for k, d in matches:
+            if k not in self.slot:
+                if not self.free:
+                    raise RuntimeError('StreamDemo: %d tracks hold a slot and frame %d opens another; there are %d slots' % (len(self.slot), f, self.slots))
+                s = self.slot[k] = self.free.pop(0)
+                self.box_stream.reset(s)
+                self.para_stream.reset(s)
+            s = self.slot[k]
+            n = f - self.boxed.get(k, f - 1)                               # the gap rows this detection has resolved, then its own row
+            b = self.held[f]['boxes'][d]
+            c = np.asarray(b[0], np.float64).reshape(2)
+            rows[s, n - 1] = (c[0], c[1], np.log(float(b[1])))
+            self.box_rows[(k, f)] = [rows[s, n - 1].copy(), None]
+            conf[s, n - 1] = self.assoc.tracks[k]['rows'][-1][2]
+            n_new[s], self.boxed[k] = n, f
+        cover = self._covering(g) if g is not None else []
+        for k in cover:
+            emit[self.slot[k]] = g - self._span(k)[0]
+        if not (n_new.any() or cover):
+            return {}
+        out, _ = st.step(n_new, torch.from_numpy(rows).to(self.scene.device), conf, emit)
+        out = out.cpu().numpy()
+        for k in cover:
+            self.box_rows.setdefault((k, g), [None, None])[1] = out[self.slot[k]].copy()
+        return {k: out[self.slot[k]].copy() for k in cover}
+
+    def _process(self, g, sm_boxes):
+        """Frame g with its smoothed boxes: crop, infer, fit; -> its people in VideoDemo's order (detections, then gap rows by track)."""
+        sc, h = self.scene, self.held[g]
+        by_det = {r[1]: k for k in sm_boxes for r in self.assoc.tracks[k]['rows'] if r[0] == g}
+        order = [(by_det[d], d) for d in range(len(h['boxes']))] + [(k, -1) for k in sorted(sm_boxes) if k not in by_det.values()]
+        boxes = []
+        for k, d in order:
+            if d >= 0 and not self.smooth:
+                boxes.append((h['boxes'][d][0], h['boxes'][d][1]))
+            else:
+                b = sm_boxes[k]
+                boxes.append((b[:2].astype(np.float64), float(np.exp(np.float64(b[2])))))
+        plan = sc.prepare([h['frame']], [boxes])
+        P, iuv = plan['P'], None
+        if P and sc.dense:
+            para, iuv = sc.infer(plan, return_iuv=True)
+        else:
+            para = sc.infer(plan) if P else torch.zeros(0, 229, device=sc.device)
+        h.update({'plan': plan, 'order': order, 'para_raw': para, 'para_in': para, 'fitted': None})
+        if sc.fitter is not None and (sc.dense or h['kps'] is not None):
+            h['fitted'] = (para, None)
+            if P:
+                kps = None if h['kps'] is None else [[np.zeros((49, 3)) if d < 0 else h['kps'][d] for _, d in order]]
+                para_fit, info = sc.fit(para, plan, kps, iuv)
+                h['fitted'], h['para_in'] = (para, info), para_fit
+        del h['boxes'], h['kps']
+
+    def _para_step(self, g, d):
+        """The rows of frame g (or None) go into the para stream; the rows of frame d (or None) come out: ({track: [229] on the
+        device}, {track: the prefix's last frame})."""
+        S = self.slots
+        n_new, emit = np.zeros(S, np.int64), np.full(S, -1, np.int64)
+        rows, conf = torch.zeros(S, 1, 229, device=self.scene.device), np.zeros((S, 1), np.float32)
+        if g is not None and self.held[g]['order']:
+            h = self.held[g]
+            slots = [self.slot[k] for k, _ in h['order']]
+            rows[slots, 0] = h['para_in']
+            for s, (k, det) in zip(slots, h['order']):
+                n_new[s] = 1
+                conf[s, 0] = self.gap_conf if det < 0 else [r[2] for r in self.assoc.tracks[k]['rows'] if r[0] == g][0]
+        cover = [k for k, _ in self.held[d]['order']] if d is not None else []
+        for k in cover:
+            emit[self.slot[k]] = d - self._span(k)[0]
+        if not (n_new.any() or cover):
+            return {}, {}
+        out, _ = self.para_stream.step(n_new, rows, conf, emit)
+        out = out.clone()
+        seen = self.assoc.n_frames - 1 if g is None else g                               # the last frame whose rows have gone in
+        return {k: out[self.slot[k]] for k in cover}, {k: min(seen, self._span(k)[1]) for k in cover}
+
+    def _draw(self, d, sm_rows, ends):
+        sc, h = self.scene, self.held.pop(d)
+        plan, order, P = h['plan'], h['order'], h['plan']['P']
+        para = h['para_in']
+        if self.smooth and P:
+            para = torch.stack([sm_rows[k] for k, _ in order])
+        verts = sc.vertices(para) if P else None
+        aux = sc.render(para, plan, return_aux=True, vertices=verts)
+        rendered = unpack_frames(aux[0].cpu().numpy(), plan['offsets'], plan['shapes'])[0]
+        para_h, raw_h = para.cpu().numpy(), h['para_raw'].cpu().numpy()
+        people = {'para': para_h, 'cam': para_h[:, 0:3], 'center': plan['center'], 'scale': plan['scale'],
+                  'vertices': verts.cpu().numpy() if P else np.zeros((0, 0, 3), np.float32),
+                  'track_id': np.array([k for k, _ in order], np.int32), 'observed': np.array([det >= 0 for _, det in order], bool),
+                  'para_raw': raw_h, 'prefix_end': np.array([ends.get(k, d) for k, _ in order], np.int32)}
+        if P:
+            cams = person_cameras(para_h[:, 0:3], plan['tinv'], plan['shapes'], plan['person_frame'], sc.res, sc.focal, sc.focal_full)
+        people.update({'cam_t_full': cams['cam_t_full'] if P else np.zeros((0, 3)), 'focal_full': cams['focal_full'] if P else np.zeros(0)})
+        if h['fitted'] is not None:
+            init = h['fitted'][0].cpu().numpy()
+            if P:
+                hist, it = h['fitted'][1]['history'].cpu().numpy(), h['fitted'][1]['best_iter'].cpu().numpy()
+                loss = np.stack([hist[:, 0], hist[np.arange(P), it]], 1)
+            else:
+                loss, it = np.zeros((0, 2), np.float32), np.zeros(0, np.int32)
+            people.update({'para_init': init, 'fit_loss': loss, 'fit_iter': it})
+        for i, (k, _) in enumerate(order):
+            self.rows[(k, d)] = (raw_h[i], para_h[i])
+            if self._span(k)[1] == d:                                      # the track's last row: its slot is free again
+                self.free.append(self.slot.pop(k))
+                self.free.sort()
+        self.last = {'frame': d, 'plan': plan, 'render_aux': aux}
+        return d, rendered, people
+
+    def _step(self, matches):
+        """One tick of the pipeline's clock: frame time - box_lag is processed, frame time - box_lag - lag is drawn."""
+        F = self.assoc.n_frames
+        g, d = self.time - self.box_lag, self.time - self.box_lag - self.lag
+        g, d = (g if 0 <= g < F else None), (d if 0 <= d < F else None)
+        sm_boxes = self._timed('boxes', lambda: self._box_step(matches, g))
+        if g is not None:
+            self._timed('infer', lambda: self._process(g, sm_boxes))
+        sm_rows, ends = self._timed('smooth', lambda: self._para_step(g, d))
+        self.time += 1
+        return [self._timed('render', lambda: self._draw(d, sm_rows, ends))] if d is not None else []
+
+    # ---- the interface -------------------------------------------------------------------------------------------------------------------
+    def push(self, frame, boxes, keypoints=None):
+        """One frame [H,W,3] uint8 with its boxes (and one keypoint array per box) -> [] or [(frame_index, rendered, people)]."""
+        if self.time != self.assoc.n_frames:
+            raise RuntimeError('StreamDemo: push after flush')
+        if keypoints is not None and len(keypoints) != len(boxes):
+            raise ValueError('StreamDemo: keypoints must hold one array per box')
+        f = self.assoc.n_frames
+        matches, _ = self._timed('associate', lambda: self.assoc.push(boxes))
+        self.held[f] = {'frame': frame, 'boxes': list(boxes), 'kps': keypoints}
+        self.max_held = max(self.max_held, len(self.held))
+        return self._step(matches)
+
+    def joints(self, para, chunk=256):
+        return torch.cat([from_para(self.scene.smpl, para[i:i + chunk]).smpl_joints.detach() for i in range(0, para.shape[0], chunk)], 0)
+
+    def flush(self):
+        """-> (the frames not drawn yet, in order, VideoDemo's summary of the whole stream).  self.tracks / self.para_raw / self.para
+        / self.boxes_raw / self.boxes
+        then hold the TrackSet and the rows of everything drawn, track-major."""
+        F = self.assoc.n_frames
+        rest = []
+        while self.held:
+            rest += self._step([])
+        ts = self.assoc.trackset()
+        summary = {'tracks': ts.K, 'rows': ts.N, 'gap_rows': int((ts.det < 0).sum()), 'frames': F}
+        keys = list(zip(ts.track.tolist(), ts.frame.tolist()))
+        raw = np.stack([self.rows[k][0] for k in keys]) if keys else np.zeros((0, 229), np.float32)
+        out = np.stack([self.rows[k][1] for k in keys]) if keys else np.zeros((0, 229), np.float32)
+        if ts.N:
+            dev = self.scene.device
+            a0, cnt = tr.accel(self.joints(torch.from_numpy(raw).to(dev)), ts)
+            a1, _ = tr.accel(self.joints(torch.from_numpy(out).to(dev)), ts)
+            a0, a1, cnt = a0.cpu().numpy(), a1.cpu().numpy(), cnt.cpu().numpy().astype(np.float64)
+        else:
+            a0 = a1 = cnt = np.zeros(ts.K)
+        w = cnt / cnt.sum() if cnt.sum() > 0 else cnt
+        summary.update({'accel_raw': float((a0 * w).sum()), 'accel': float((a1 * w).sum()), 'accel_raw_tracks': a0, 'accel_tracks': a1})
+        self.tracks, self.para_raw, self.para = ts, raw, out
+        zero = np.zeros(3, np.float32)
+        self.boxes_raw = np.stack([zero if self.box_rows[k][0] is None else self.box_rows[k][0] for k in keys]) if keys else np.zeros((0, 3), np.float32)
+        self.boxes = np.stack([self.box_rows[k][1] for k in keys]) if keys else np.zeros((0, 3), np.float32)
+        return rest, summary

@@ -1051,6 +1051,31 @@ int danet_track_smooth_para(const float* para, const float* conf, const int32_t*
 int danet_track_accel(const float* joints, const float* joints_ref, const int32_t* track_start, const int32_t* track_start_host,
                       long N, int J, int K, double* accel, int32_t* count, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Streaming tracks (csrc/track_stream.hip; tracks.StreamSmoother is the caller; DESIGN.md 4b'-stream "the stream rule").  S slots,
+ * each one track whose rows arrive a few at a time.  The value written for row g of a slot is what danet_track_smooth /
+ * danet_track_smooth_para give on the rows the slot holds so far, read at row g (the same energy, eps, gap-row target, clamp of s,
+ * shared shape and 6D map; double inside, rounded to fp32 once), for g at most `lag` rows behind the newest row.
+ *
+ * state: danet_track_stream_state_bytes(S, C, lag, max_new) bytes (C = 157 for the para form; 0 for bad sizes), 8-byte aligned,
+ *   owned by the caller and passed to every step; all zero = every slot empty.  Per step, all DEVICE and of fixed shape:
+ *   n_new [S] i32 in 0..max_new, the rows appended to each slot; reset [S] i32, not 0: the slot is emptied first;
+ *   rows [S,max_new,C] f32 (para form [S,max_new,229]) and conf [S,max_new] f32, of which the first n_new count; rows with
+ *   conf = 0 are never read; the caller vouches that conf is finite and not negative and that a slot's first row has conf > 0;
+ *   emit [S] i32: the absolute row of the slot to write (counted from the slot's first row), or -1.
+ *   out [S,C] f32 (para form [S,229]) and valid [S] i32: 1 where emit lies in [max(T - 1 - lag, 0), T - 1], T the slot's row count
+ *   after the step; elsewhere valid is 0 and the out row is zero.
+ * One launch per step, one workgroup per slot: no atomics, no grid barrier, nothing read on the host, no allocation; a slot's bits do
+ * not depend on the other slots; capturable for fixed (S, C, lag, max_new).
+ */
+size_t danet_track_stream_state_bytes(int S, int C, int lag, int max_new);
+int danet_track_stream_step(void* state, size_t state_bytes, int S, int C, int lag, int max_new, const int32_t* n_new,
+                            const int32_t* reset, const float* rows, const float* conf, const int32_t* emit, double lam_vel,
+                            double lam_acc, float* out, int32_t* valid, void* stream);
+int danet_track_stream_step_para(void* state, size_t state_bytes, int S, int lag, int max_new, const int32_t* n_new,
+                                 const int32_t* reset, const float* rows, const float* conf, const int32_t* emit,
+                                 const double* lam, int shared_shape, float* out, int32_t* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

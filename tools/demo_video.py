@@ -7,12 +7,16 @@ the SMPL joints per track before and after).
 
   python tools/demo_video.py --frames_dir DIR --out_dir DIR --boxes FILE.json [--keypoints_dir DIR] [--fit | --fit_iuv] [--rounds R]
                              [--no_smooth] [--engine] [--batch N] [--checkpoint FILE] [--cfg YAML] [--fit_iters N]
+                             [--stream [--lag L] [--box_lag L] [--slots S]]
 
 Frames are taken in name order; the input conventions are those of tools/demo_scene.py: .npy arrays always (uint8 [H,W,3]), .jpg / .png
 if PIL is installed; --boxes maps a frame's file name to a list of [x, y, w, h] or [x, y, w, h, confidence]; --keypoints_dir holds
 <name>_keypoints.json in OpenPose's layout, and with it the boxes come from the keypoints (so --fit, which needs it, is refused with
 --boxes, as in the scene tool: there is no rule for matching boxes to the people of the keypoint files).  The whole clip is one call: it must fit on the
-device.  There is no video decoder, no person detector and no causal filter here.  Last line: one JSON object with the counts and the
+device.  With --stream (video.StreamDemo, DESIGN.md 4b'-stream "the stream rule") the frames are read one at a time and never held
+together: every frame is drawn box_lag + lag frames after it was read, from the offline rule on what its tracks have seen by then, and
+its <name>_scene.png is written as it comes out; the JSON line adds delay_frames and max_frames_held.  There is no video decoder and no
+person detector here.  Last line: one JSON object with the counts and the
 milliseconds per frame of every stage (host clock around a device synchronisation, one run: the clip is processed once)."""
 import argparse
 import json
@@ -40,6 +44,35 @@ def frame_boxes(name, frame, box_table, keypoints_dir):
     return out
 
 
+def stream(a, demo, names, box_table, with_kp):
+    """The --stream mode: a frame is loaded, pushed and forgotten; what comes out is written at once.  -> the JSON line's dict."""
+    import torch
+    demo.timing = True
+    written = 0
+
+    def write(done):
+        for n, img, _ in done:
+            write_png(os.path.join(a.out_dir, os.path.splitext(names[n])[0] + '_scene.png'), img)
+        return len(done)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for n in names:
+        frame = load_frame(os.path.join(a.frames_dir, n))
+        written += write(demo.push(frame, frame_boxes(n, frame, box_table, a.keypoints_dir), keypoints_of(n, a.keypoints_dir) if with_kp else None))
+    rest, summary = demo.flush()
+    written += write(rest)
+    torch.cuda.synchronize()
+    demo.ms['total'] = (time.perf_counter() - t0) * 1e3
+    np.savez(os.path.join(a.out_dir, 'tracks.npz'), para_raw=demo.para_raw, para=demo.para, boxes_raw=demo.boxes_raw, boxes=demo.boxes,
+             accel_raw=summary['accel_raw_tracks'], accel=summary['accel_tracks'], **demo.tracks.arrays())
+    print('Video demo results (%d frames, %d tracks, %d rows) have been saved in %s.' % (written, summary['tracks'], summary['rows'], a.out_dir))
+    return {'tool': 'demo_video', 'stream': True, 'frames': written, 'tracks': summary['tracks'], 'rows': summary['rows'],
+            'gap_rows': summary['gap_rows'], 'accel_raw': summary['accel_raw'], 'accel': summary['accel'], 'batch': a.batch,
+            'engine': bool(a.engine), 'smooth': not a.no_smooth, 'fit': 'keypoints' if a.fit else ('iuv' if a.fit_iuv else None),
+            'lag': demo.lag, 'box_lag': demo.box_lag, 'max_gap': demo.max_gap, 'delay_frames': demo.lag + demo.box_lag,
+            'max_frames_held': demo.max_held, 'ms_per_frame': {k: round(v / max(written, 1), 4) for k, v in demo.ms.items()}}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='DaNet video demo: tracked, smoothed meshes drawn into the frames of a clip')
     ap.add_argument('--cfg', dest='cfg_file', default=None)
@@ -55,7 +88,13 @@ def main(argv=None):
     ap.add_argument('--no_smooth', action='store_true')
     ap.add_argument('--engine', action='store_true')
     ap.add_argument('--batch', type=int, default=1)
+    ap.add_argument('--stream', action='store_true', help='one frame at a time: online tracks and the fixed-lag smoother')
+    ap.add_argument('--lag', type=int, default=8, help='--stream: rows behind the newest at which a row is drawn')
+    ap.add_argument('--box_lag', type=int, default=8, help='--stream: the same for the boxes; tracks bridge gaps of up to min(5, box_lag) frames')
+    ap.add_argument('--slots', type=int, default=32, help='--stream: tracks alive at once')
     a = ap.parse_args(argv)
+    if a.stream and a.rounds != 1:
+        raise SystemExit('--stream has no --rounds: the fit / smooth alternation needs whole tracks')
     if a.fit and a.fit_iuv:
         raise SystemExit('--fit and --fit_iuv: one of the two (--fit_iuv --keypoints_dir DIR fits both terms)')
     if (a.fit or (a.fit_iuv and a.keypoints_dir)) and a.boxes:
@@ -89,7 +128,11 @@ def main(argv=None):
     model = model.cuda().eval()
     smpl = model.iuv2smpl.smpl
     engine = model.inference_engine(a.batch) if a.engine else None
-    demo = video.VideoDemo(engine if engine is not None else model, smpl, a.batch, smooth=not a.no_smooth, rounds=a.rounds)
+    if a.stream:
+        demo = video.StreamDemo(engine if engine is not None else model, smpl, a.batch, smooth=not a.no_smooth, lag=a.lag, box_lag=a.box_lag,
+                                slots=a.slots, max_gap=min(5, a.box_lag) if a.box_lag >= 1 else 5)
+    else:
+        demo = video.VideoDemo(engine if engine is not None else model, smpl, a.batch, smooth=not a.no_smooth, rounds=a.rounds)
     n0 = (3 * a.fit_iters) // 10
     stages = ((n0, 'cam+orient'), (a.fit_iters - n0, 'all'))
     if a.fit:
@@ -99,6 +142,12 @@ def main(argv=None):
         from danet_densepose2smpl_amd.dense_fit import DenseFitter
         demo.scene.fitter = DenseFitter(smpl, stages=stages, focal=demo.scene.focal, res=demo.scene.res)
     with_kp = a.fit or (a.fit_iuv and a.keypoints_dir is not None)
+    if a.stream:
+        res = stream(a, demo, names, box_table, with_kp)
+        print(json.dumps(res), flush=True)
+        if engine is not None:
+            engine.close()
+        return 0
 
     frames = [load_frame(os.path.join(a.frames_dir, n)) for n in names]
     boxes = [frame_boxes(n, f, box_table, a.keypoints_dir) for n, f in zip(names, frames)]

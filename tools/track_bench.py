@@ -5,7 +5,15 @@ call, 20 repetitions after 3 warm-ups, the two ways alternating; median and p10 
 (default profiles/track_smooth_bench.jsonl).  There is no threshold on these numbers: the op is a dependent chain of T steps, latency-
 bound by construction, and nothing before it to compare with.
 
-  python tools/track_bench.py [--out FILE] [--reps 20] [--warmup 3]"""
+  python tools/track_bench.py [--out FILE] [--reps 20] [--warmup 3]
+
+With --stream: one para-form step of tracks.StreamSmoother (csrc/track_stream.hip, one launch: every slot takes a row and emits the row
+`lag` behind) at S in {8, 32} slots and lag in {8, 32}, against the two ways to a streaming estimate without it: tracks.smooth_para
+re-run on every slot's whole prefix of T = 256 rows (exact), and re-run on a window of the last lag + 16 rows (not exact).  The same
+protocol; the step's commands are uploaded outside the events, as a captured pipeline would have them.  Appended to
+profiles/track_stream_bench.jsonl.
+
+  python tools/track_bench.py --stream [--out FILE] [--reps 20] [--warmup 3]"""
 import argparse
 import json
 import os
@@ -73,17 +81,84 @@ def composed(para, conf, K, T, lam, VV, AA):
     return torch.cat([o32[:, :13], geometry.rot6d_to_rotmat(o32[:, 13:].reshape(-1, 6)).view(N, 216)], 1)
 
 
+def measure(ways, reps, warmup, before=None):
+    """HIP events around one call of each way, the ways alternating; `before(k)` runs outside the events.  -> {way: [ms]}"""
+    import torch
+    times = {k: [] for k in ways}
+    for i in range(warmup + reps):
+        for k, f in ways.items():
+            if before is not None:
+                before(k)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= warmup:
+                times[k].append(e0.elapsed_time(e1))
+    return times
+
+
+def stream_bench(a, dev):
+    import torch
+    from danet_densepose2smpl_amd import tracks
+    T = 256
+    for S in (8, 32):
+        para, ts = make_rows(S, T, T + S, dev)
+        rows = para.view(S, T, 229)
+        conf = ts.conf.reshape(S, T)
+        for lag in (8, 32):
+            sm = tracks.StreamSmoother(S, lag, para=True)
+            one = np.ones(S, np.int64)
+            for t in range(T):                                                 # the prefix goes in, a row per step
+                out, _ = sm.step(one, rows[:, t:t + 1].contiguous(), conf[:, t:t + 1], np.full(S, max(t - lag, 0)))
+            exact, _ = tracks.smooth_para(para, ts)
+            diff = float((out - exact.view(S, T, 229)[:, T - 1 - lag]).abs().max())
+            W = lag + 16
+            win = rows[:, T - W:].reshape(S * W, 229).contiguous()
+            cw = conf[:, T - W:].copy()
+            cw[:, 0] = np.maximum(cw[:, 0], 1.0)
+            tw = tracks.TrackSet(np.arange(S + 1) * W, np.tile(np.arange(W), S), np.where(cw.reshape(-1) > 0, 0, -1), cw.reshape(-1), W)
+            tw.device(dev)
+            step_rows = rows[:, T - 1:T].contiguous()
+            state = {'t': T}
+
+            def before(k):
+                if k == 'op':                                                  # the next row's commands: checked and uploaded outside the events
+                    sm.commands(one, conf[:, T - 1:T], np.full(S, state['t'] - lag))
+                    state['t'] += 1
+            ways = {'op': lambda: sm.launch(step_rows), 'prefix': lambda: tracks.smooth_para(para, ts)[0],
+                    'window': lambda: tracks.smooth_para(win, tw)[0]}
+            times = measure(ways, a.reps, a.warmup, before)
+            res = {'tool': 'track_bench', 'mode': 'stream', 'S': S, 'lag': lag, 'T': T, 'window': W, 'reps': a.reps, 'warmup': a.warmup,
+                   'max_abs_diff_to_offline': diff}
+            for k, v in times.items():
+                res[k] = {'median_ms': round(float(np.median(v)), 4), 'p10': round(float(np.percentile(v, 10)), 4), 'p90': round(float(np.percentile(v, 90)), 4)}
+            line = json.dumps(res)
+            print(line, flush=True)
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'a') as fh:
+                fh.write(line + '\n')
+    return 0
+
+
 def main(argv=None):
+    profiles = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles')
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'track_smooth_bench.jsonl'))
+    ap.add_argument('--out', default=None)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--stream', action='store_true', help='time one step of the stream smoother instead')
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = os.path.join(profiles, 'track_stream_bench.jsonl' if a.stream else 'track_smooth_bench.jsonl')
     import torch
     from danet_densepose2smpl_amd import tracks
     if not torch.cuda.is_available():
         raise SystemExit('tools/track_bench.py needs a GPU')
     dev = torch.device('cuda', 0)
+    if a.stream:
+        return stream_bench(a, dev)
     K = 8
     for T in (64, 256):
         para, ts = make_rows(K, T, T, dev)
