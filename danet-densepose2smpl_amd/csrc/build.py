@@ -62,6 +62,7 @@ UNITS = {
     'fit_loop.hip': ['-ffp-contract=off'],    # the pose undo is input_ops.hip's (pose_aug.h): the same bits in both units
     'track_ops.hip': ['-ffp-contract=off'],   # the track rule's factor and substitutions are restated operation by operation in the tests
     'track_stream.hip': ['-ffp-contract=off'],  # the same operations as track_ops.hip, one row at a time
+    'track_link.hip': ['-ffp-contract=off'],  # the identity rule's sums are restated in the tests and rounded once
 }
 INCLUDES = {'norm_act_f32.hip': ['norm_act.hip']}
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-I' + os.path.join(ROOT, 'include'), '-I' + HERE,

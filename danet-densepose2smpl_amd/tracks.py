@@ -14,7 +14,15 @@ The same fed one frame at a time (DESIGN.md 4b'-stream "the stream rule"):
 
     a = OnlineAssociator(); matches, died = a.push(dets); a.trackset()     # associate(), a frame at a time
     sm = StreamSmoother(slots, lag, para=True)                              # csrc/track_stream.hip, one launch per step
-    out, valid = sm.step(n_new, rows, conf, emit)                           # the offline rule on each slot's rows so far, read at row emit"""
+    out, valid = sm.step(n_new, rows, conf, emit)                           # the offline rule on each slot's rows so far, read at row emit
+
+Identities (DESIGN.md 4b'-link "the identity rule"; csrc/track_link.hip): the tracks of one person linked by shape and fused texture:
+
+    shape, atlas, _ = descriptors(para_s, ts, atlas_builder)               # [K,10] mean betas (one launch), [K,24,T,T,4] fused texture
+    pairs = candidates(ts, max_absence)                                     # host: b begins 1 .. max_absence frames after a ends
+    dist = affinity(shape, atlas, pairs)                                    # [C,4] = (d_shape, d_app, overlap, S), one launch
+    res = link(ts, dist, pairs)                                             # host, float64: identity [K], links [L,2], link_cost [L]
+    para_i, mean, status = share_shape(para_s, ts, res['identity'])        # one shape per identity, one launch"""
 import ctypes
 
 import numpy as np
@@ -274,6 +282,306 @@ def accel(joints, tracks, joints_ref=None):
     check(_lib.lib().danet_track_accel(ptr(x), ptr(r), ptr(d_start), _host_i32(ts.track_start), N, J, ts.K, ptr(a), ptr(n), stream()),
           'danet_track_accel')
     return a, n
+
+
+# ---- identities (DESIGN.md 4b'-link "the identity rule"; csrc/track_link.hip) -------------------------------------------------------
+PARTS = 24
+W_MIN = 1e-3
+# (max_absence, sigma_s, sigma_a, min_overlap, no_app): DESIGN.md 4b'-link, the default table on link_oracle.recovery_case
+LINK_DEFAULTS = {'max_absence': 150, 'sigma_s': 0.3, 'sigma_a': 0.15, 'min_overlap': 0.1, 'no_app': 0.5}
+ID_TEXTURE_SIZE = 8
+
+
+class PairSet(object):
+    """C ordered pairs (a, b) of track ids in [0, K): pairs [C,2] int32 on the host, checked here, uploaded at the first use on a
+    device and kept (no copy inside a captured region afterwards)."""
+
+    def __init__(self, pairs, K):
+        p = np.asarray(pairs)
+        if p.size == 0:
+            p = np.zeros((0, 2), np.int32)
+        if p.ndim != 2 or p.shape[1] != 2 or not np.issubdtype(p.dtype, np.integer):
+            raise ValueError('tracks.PairSet: pairs must be [C,2] integers, got %s %s' % (p.dtype, p.shape))
+        if isinstance(K, bool) or int(K) != K or K < 0:
+            raise ValueError('tracks.PairSet: K %r (an integer >= 0)' % (K,))
+        if ((p < 0) | (p >= K)).any():
+            c = int(np.nonzero(((p < 0) | (p >= K)).any(1))[0][0])
+            raise ValueError('tracks.PairSet: pair %d = %s names a track outside [0, %d)' % (c, p[c].tolist(), K))
+        self.pairs, self.K = np.ascontiguousarray(p, np.int32), int(K)
+        self._dev = {}
+
+    @property
+    def C(self):
+        return self.pairs.shape[0]
+
+    def device(self, device):
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.pairs).to(device)
+        return t
+
+
+def _span(ts):
+    """(first frame [K], last frame [K]) of the tracks of a TrackSet; every track must hold a row."""
+    if (np.diff(ts.track_start) < 1).any():
+        raise ValueError('tracks: a track without a row')
+    return ts.frame[ts.track_start[:-1]].astype(np.int64), ts.frame[ts.track_start[1:] - 1].astype(np.int64)
+
+
+def _absence(v, what):
+    if isinstance(v, bool) or int(v) != v or v < 1:
+        raise ValueError('%s: max_absence %r (an integer >= 1)' % (what, v))
+    return int(v)
+
+
+def link_arguments(what, max_absence, sigma_s, sigma_a, min_overlap, no_app):
+    """The checked thresholds of the identity rule as a dict: max_absence an integer >= 1, sigma_s and sigma_a finite and positive,
+    min_overlap and no_app finite and not negative."""
+    thr = {'max_absence': _absence(max_absence, what)}
+    for name, v, positive in (('sigma_s', sigma_s, True), ('sigma_a', sigma_a, True), ('min_overlap', min_overlap, False), ('no_app', no_app, False)):
+        v = float(v)
+        if not np.isfinite(v) or v < 0 or (positive and v == 0):
+            raise ValueError('%s: %s %r (finite and %s)' % (what, name, v, 'positive' if positive else 'not negative'))
+        thr[name] = v
+    return thr
+
+
+def candidates(ts, max_absence=LINK_DEFAULTS['max_absence']):
+    """The ordered pairs (a, b) with 1 <= first_frame(b) - last_frame(a) <= max_absence, ascending in (a, b): [C,2] int32 (host)."""
+    if not isinstance(ts, TrackSet):
+        raise ValueError('tracks.candidates: a TrackSet expected, got %s' % type(ts).__name__)
+    A = _absence(max_absence, 'tracks.candidates')
+    if ts.K == 0:
+        return np.zeros((0, 2), np.int32)
+    first, last = _span(ts)
+    d = first[None, :] - last[:, None]
+    a, b = np.nonzero((d >= 1) & (d <= A))
+    return np.stack([a, b], 1).astype(np.int32)
+
+
+class RowGroups(object):
+    """G groups over N rows as a CSR: group_start [G+1] ascending from 0 to N, group_rows [N] a permutation of 0 .. N-1 (host int32,
+    checked here); uploaded at the first use on a device and kept."""
+
+    def __init__(self, group_start, group_rows):
+        order = np.asarray(group_rows).reshape(-1)
+        start = np.asarray(group_start).reshape(-1)
+        N = order.size
+        if not np.issubdtype(order.dtype, np.integer) or not np.issubdtype(start.dtype, np.integer) or start.size < 1:
+            raise ValueError('tracks.RowGroups: group_start [G+1] and group_rows [N] must be integers')
+        if start.size > 1:
+            _ascending(start, N, 'tracks.RowGroups: group_start', integers=True)
+        elif N or start[0] != 0:
+            raise ValueError('tracks.RowGroups: rows without a group')
+        if N and not np.array_equal(np.sort(order), np.arange(N)):
+            raise ValueError('tracks.RowGroups: group_rows must be a permutation of 0 .. %d' % (N - 1))
+        self.start, self.rows = np.ascontiguousarray(start, np.int32), np.ascontiguousarray(order, np.int32)
+        self._dev = {}
+
+    @property
+    def G(self):
+        return self.start.size - 1
+
+    @property
+    def N(self):
+        return self.rows.size
+
+    def device(self, device):
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = (torch.from_numpy(self.start).to(device), torch.from_numpy(self.rows).to(device))
+        return t
+
+
+def group_mean(para_rows, conf, groups, col0=3, ncol=10, write_back=False):
+    """para_rows [N,229] f32 and conf [N] f32 on the GPU (the caller vouches that conf is finite and not negative), groups a
+    RowGroups -> (mean [G,ncol] f32 of the columns col0 .. col0 + ncol - 1: sum c x / sum c over the group's rows with c > 0 in the
+    CSR's order, double inside, rounded once; status [G] int32: 1 and mean 0 for a group without weight).  With write_back para_rows
+    must be a contiguous fp32 tensor and is changed IN PLACE: every row of a group with status 0 gets the mean in those columns.
+    One launch (csrc/track_link.hip); G = 0 or N = 0 launches nothing."""
+    what = 'tracks.group_mean'
+    N = _rows(para_rows, (None, PARA), what + ': para_rows').shape[0]
+    _rows(conf, (N,), what + ': conf')
+    if not isinstance(groups, RowGroups):
+        raise ValueError('%s: a RowGroups expected, got %s' % (what, type(groups).__name__))
+    if groups.N != N:
+        raise ValueError('%s: %d rows, the groups hold %d' % (what, N, groups.N))
+    for name, v in (('col0', col0), ('ncol', ncol)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError('%s: %s %r (an integer)' % (what, name, v))
+    if col0 < 0 or ncol < 1 or col0 + ncol > PARA:
+        raise ValueError('%s: columns %d .. %d of %d' % (what, col0, col0 + ncol, PARA))
+    require_gpu(para_rows, what)
+    require_gpu(conf, what + ': conf')
+    if write_back:
+        from .ops import _typed
+        rows = _typed(para_rows, torch.float32, (N, PARA), what + ': para_rows (write_back)')
+    else:
+        rows = _f32(para_rows, (N, PARA), what + ': para_rows')
+    c = _f32(conf, (N,), what + ': conf')
+    if c.device != rows.device:
+        raise ValueError('%s: para_rows and conf must be on one device' % what)
+    G = groups.G
+    mean = torch.zeros(G, int(ncol), device=rows.device, dtype=torch.float32)
+    status = torch.ones(G, device=rows.device, dtype=torch.int32)
+    if N == 0 or G == 0:
+        return mean, status
+    d_start, d_rows = groups.device(rows.device)
+    check(_lib.lib().danet_track_group_mean(ptr(rows), ptr(c), ptr(d_start), _host_i32(groups.start), ptr(d_rows), _host_i32(groups.rows), G, N,
+                                            int(col0), int(ncol), ptr(mean), ptr(status), 1 if write_back else 0, stream()),
+          'danet_track_group_mean')
+    return mean, status
+
+
+def track_groups(ts):
+    """Every track a group, its rows in ascending t (made once per TrackSet)."""
+    g = ts._dev.get('track_groups')
+    if g is None:
+        g = ts._dev['track_groups'] = RowGroups(ts.track_start, np.arange(ts.N, dtype=np.int32))
+    return g
+
+
+def descriptors(para_rows, tracks, atlas_builder=None, texture_size=ID_TEXTURE_SIZE):
+    """The descriptor of every track: para_rows [N,229] on the GPU, track-major -> (shape [K,10] f32: sum c betas / sum c over the
+    track's rows with c > 0, c the TrackSet's conf, one launch; atlas [K,24,T,T,4] f32).  atlas_builder(rows, view_offsets) -> the
+    atlas: `rows` the observed rows (det >= 0) of all tracks, track-major and ascending in t (host int64), view_offsets [K+1] host
+    int32, the views of track k being rows[view_offsets[k] : view_offsets[k+1]] (texture.TextureAtlas.unwrap's convention).  None:
+    no skin, an all-zero atlas of side `texture_size`, which shares no texel with anything.  -> (shape, atlas, status [K] int32)."""
+    N = _rows(para_rows, (None, PARA), 'tracks.descriptors: para_rows').shape[0]
+    ts = _tracks(tracks, N, 'tracks.descriptors')
+    if ts.K and ((np.diff(ts.track_start) < 1).any() or (np.add.reduceat(ts.observed.astype(np.int64), ts.track_start[:-1]) < 1).any()):
+        raise ValueError('tracks.descriptors: a track without an observed row')
+    require_gpu(para_rows, 'tracks.descriptors')
+    p = _f32(para_rows, (N, PARA), 'tracks.descriptors: para_rows')
+    shape, status = group_mean(p, ts.device(p.device)[1], track_groups(ts), 3, 10, False)
+    obs = np.nonzero(ts.observed)[0].astype(np.int64)
+    off = np.concatenate([[0], np.cumsum(np.add.reduceat(ts.observed.astype(np.int64), ts.track_start[:-1]))]).astype(np.int32) if ts.K \
+        else np.zeros(1, np.int32)
+    if atlas_builder is None:
+        from .ops import _texture_size
+        T = _texture_size(texture_size)
+        atlas = torch.zeros(ts.K, PARTS, T, T, 4, device=p.device, dtype=torch.float32)
+    else:
+        atlas = atlas_builder(obs, off)
+        if not torch.is_tensor(atlas) or atlas.dim() != 5 or tuple(atlas.shape[:2]) != (ts.K, PARTS) or atlas.shape[2] != atlas.shape[3] \
+                or atlas.shape[4] != 4:
+            raise ValueError('tracks.descriptors: the builder gave %s, expected [%d,24,T,T,4]' % (tuple(getattr(atlas, 'shape', ())), ts.K))
+        atlas = _f32(atlas, None, 'tracks.descriptors: atlas')
+    return shape, atlas, status
+
+
+def affinity(shape, atlas, pairs):
+    """shape [K,10], atlas [K,24,T,T,4] on the GPU, pairs: [C,2] host integers in [0, K) or a PairSet -> dist [C,4] f32 on the GPU:
+    (d_shape, d_app, overlap, S) of every ordered pair (DESIGN.md 4b'-link).  One launch; C = 0 launches nothing."""
+    K = _rows(shape, (None, 10), 'tracks.affinity: shape').shape[0]
+    _rows(atlas, (K, PARTS, None, None, 4), 'tracks.affinity: atlas')
+    T = atlas.shape[2]
+    if atlas.shape[3] != T or T < 2 or T > 4096:
+        raise ValueError('tracks.affinity: atlas %s, expected [K,24,T,T,4] with T in [2, 4096]' % (tuple(atlas.shape),))
+    ps = pairs if isinstance(pairs, PairSet) else PairSet(pairs, K)
+    if ps.K != K:
+        raise ValueError('tracks.affinity: the PairSet was made for %d tracks, there are %d' % (ps.K, K))
+    require_gpu(shape, 'tracks.affinity')
+    require_gpu(atlas, 'tracks.affinity: atlas')
+    s = _f32(shape, (K, 10), 'tracks.affinity: shape')
+    a = _f32(atlas, (K, PARTS, T, T, 4), 'tracks.affinity: atlas')
+    if a.device != s.device:
+        raise ValueError('tracks.affinity: shape and atlas must be on one device')
+    out = torch.empty(ps.C, 4, device=s.device, dtype=torch.float32)
+    if ps.C == 0:
+        return out
+    check(_lib.lib().danet_track_affinity(ptr(s), ptr(a), K, T, ptr(ps.device(s.device)), _host_i32(ps.pairs), ps.C, ptr(out), stream()),
+          'danet_track_affinity')
+    return out
+
+
+def link(tracks, dist, pairs, max_absence=LINK_DEFAULTS['max_absence'], sigma_s=LINK_DEFAULTS['sigma_s'], sigma_a=LINK_DEFAULTS['sigma_a'],
+         min_overlap=LINK_DEFAULTS['min_overlap'], no_app=LINK_DEFAULTS['no_app']):
+    """The linking of DESIGN.md 4b'-link, host, float64, deterministic.  dist [C,4] (affinity's rows; a tensor or an array) of the
+    pairs [C,2].  A pair is a candidate where 1 <= first_frame(b) - last_frame(a) <= max_absence; its cost is d_shape / sigma_s^2 +
+    d_app / sigma_a^2 where overlap >= min_overlap and d_shape / sigma_s^2 + no_app elsewhere; candidates with cost <= 1, sorted by
+    (cost, a, b), are accepted greedily while a has no successor and b no predecessor.  -> dict: 'identity' [K] int32 (chains numbered
+    by their first track's id), 'links' [L,2] int32 in acceptance order, 'link_cost' [L] float64, 'pairs' [C,2] int32, 'cost' [C]
+    float64 (inf outside the time window) and 'admissible' [C] bool (inside the window)."""
+    what = 'tracks.link'
+    if not isinstance(tracks, TrackSet):
+        raise ValueError('%s: a TrackSet expected, got %s' % (what, type(tracks).__name__))
+    K = tracks.K
+    ps = pairs if isinstance(pairs, PairSet) else PairSet(pairs, K)
+    if ps.K != K:
+        raise ValueError('%s: the PairSet was made for %d tracks, there are %d' % (what, ps.K, K))
+    d = dist.detach().cpu().numpy() if torch.is_tensor(dist) else np.asarray(dist)
+    if d.shape != (ps.C, 4) or not np.issubdtype(d.dtype, np.floating):
+        raise ValueError('%s: dist must be [%d,4] floating point, got %s %s' % (what, ps.C, d.dtype, d.shape))
+    d = d.astype(np.float64)
+    thr = link_arguments(what, max_absence, sigma_s, sigma_a, min_overlap, no_app)
+    A = thr['max_absence']
+    p = ps.pairs.astype(np.int64)
+    if K:
+        first, last = _span(tracks)
+        gap = first[p[:, 1]] - last[p[:, 0]]
+    else:
+        gap = np.zeros(0, np.int64)
+    ok = (gap >= 1) & (gap <= A)
+    if not np.isfinite(d[ok]).all():
+        raise ValueError('%s: a non-finite distance in an admissible pair' % what)
+    with np.errstate(invalid='ignore'):
+        app = np.where(d[:, 2] >= thr['min_overlap'], d[:, 1] / thr['sigma_a'] ** 2, thr['no_app'])
+        cost = np.where(ok, d[:, 0] / thr['sigma_s'] ** 2 + app, np.inf)
+    keep = np.nonzero(cost <= 1.0)[0]
+    keep = keep[np.lexsort((p[keep, 1], p[keep, 0], cost[keep]))]
+    succ, pred, links, link_cost = {}, {}, [], []
+    for c in keep:
+        a, b = int(p[c, 0]), int(p[c, 1])
+        if a in succ or b in pred:
+            continue
+        succ[a], pred[b] = b, a
+        links.append((a, b))
+        link_cost.append(cost[c])
+    identity = np.full(K, -1, np.int32)
+    n = 0
+    for k in range(K):                                                      # chains in the order of their first track's id
+        if k in pred:
+            continue
+        j = k
+        while True:
+            identity[j] = n
+            if j not in succ:
+                break
+            j = succ[j]
+        n += 1
+    return {'identity': identity, 'links': np.array(links, np.int32).reshape(-1, 2), 'link_cost': np.array(link_cost, np.float64),
+            'pairs': ps.pairs, 'cost': cost, 'admissible': ok}
+
+
+def identity_groups(tracks, identity):
+    """The rows of every identity as a RowGroups, ascending in (track id, t) inside an identity."""
+    idn = np.asarray(identity)
+    if idn.shape != (tracks.K,) or not np.issubdtype(idn.dtype, np.integer):
+        raise ValueError('tracks.share_shape: identity must be [%d] integers, got %s %s' % (tracks.K, idn.dtype, idn.shape))
+    G = int(idn.max()) + 1 if idn.size else 0
+    if idn.size and (idn.min() < 0 or np.unique(idn).size != G):
+        raise ValueError('tracks.share_shape: identity must use every number of 0 .. %d' % (G - 1))
+    row_id = idn.astype(np.int64)[tracks.track]
+    order = np.argsort(row_id, kind='stable').astype(np.int32)              # stable: rows stay ascending in (track id, t) inside a group
+    start = np.concatenate([[0], np.cumsum(np.bincount(row_id, minlength=G))]).astype(np.int32)
+    return RowGroups(start, order)
+
+
+def share_shape(para_rows, tracks, identity):
+    """One shape per identity: para_rows [N,229] on the GPU, track-major; identity [K] host integers (link's) -> (rows [N,229] f32, a
+    new tensor whose betas are, per identity, sum c betas / sum c over all rows of its tracks with c > 0, in ascending (track id, t),
+    c the TrackSet's conf; mean [G,10] f32; status [G] int32, 1 for an identity without weight, whose rows come back bit for bit).
+    One launch."""
+    N = _rows(para_rows, (None, PARA), 'tracks.share_shape: para_rows').shape[0]
+    ts = _tracks(tracks, N, 'tracks.share_shape')
+    groups = identity if isinstance(identity, RowGroups) else identity_groups(ts, identity)
+    require_gpu(para_rows, 'tracks.share_shape')
+    out = _f32(para_rows, (N, PARA), 'tracks.share_shape: para_rows').clone()
+    mean, status = group_mean(out, ts.device(out.device)[1], groups, 3, 10, True)
+    return out, mean, status
 
 
 # ---- the stream ------------------------------------------------------------------------------------------------------------------

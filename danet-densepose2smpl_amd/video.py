@@ -8,12 +8,16 @@ DESIGN.md 4b'-track "the track rule") and the frames in which a person has no bo
 A VideoDemo wraps a scene.SceneDemo and calls its stages; the scene demo itself is what it was.  The whole clip is one call: every
 row of every track is on the device at once.  StreamDemo (below) is the same pipeline fed one frame at a time: online association, an
 exact fixed-lag smoother (tracks.StreamSmoother, DESIGN.md 4b'-stream "the stream rule") and a bounded number of frames held, for
-clips that do not fit on the device and for live sources.  Not here: video decoding, a person detector, re-identification, motion
-prediction, several ranks.  There is no CPU path."""
+clips that do not fit on the device and for live sources.  With link=True a VideoDemo also links the tracks of one person into an
+identity by body shape and fused texture (tracks.descriptors / affinity / link / share_shape, DESIGN.md 4b'-link "the identity rule").
+Not here: video decoding, a person detector, identities while streaming, motion prediction, several ranks.
+There is no CPU path."""
 import numpy as np
 import torch
 
 from . import tracks as tr
+from . import constants
+from .ops import _texture_size
 from .scene import SceneDemo, person_cameras, unpack_frames
 from .smpl import from_para
 
@@ -24,10 +28,20 @@ class VideoDemo(object):
     them.  `rounds` times the rows are fitted from their current values (where there is a fitter) and then smoothed: the fitters
     take the start row both as initialisation and as prior, so the alternation is a proximal one.  gap_conf: the weight of a gap
     row's own prediction in the smoother (0: the row is filled from its neighbours alone).  With smooth = False nothing is smoothed
-    (gap rows still get an interpolated box), and a clip without gap rows comes out as SceneDemo draws it, bit for bit."""
+    (gap rows still get an interpolated box), and a clip without gap rows comes out as SceneDemo draws it, bit for bit.
+    link=True (DESIGN.md 4b'-link): after the last round the tracks are linked into identities on the final rows -- a person who
+    was away for up to `max_absence` frames keeps their identity --, with shared_shape every identity gets one shape, and the frames
+    are drawn from those rows; max_absence, sigma_s, sigma_a, min_overlap, no_app default to tracks.LINK_DEFAULTS, id_texture_size
+    (the side of a chart of the skin descriptor) to tracks.ID_TEXTURE_SIZE.  Without it every output is what it was."""
 
     def __init__(self, model_or_engine, smpl, batch, fitter=None, smooth=True, rounds=1, shared_shape=True, max_gap=5, min_iou=0.3,
-                 gap_conf=0., lam=tr.DEFAULT_LAM, box_lam=tr.BOX_LAM, **scene_kw):
+                 gap_conf=0., lam=tr.DEFAULT_LAM, box_lam=tr.BOX_LAM, link=False, max_absence=None, id_texture_size=tr.ID_TEXTURE_SIZE,
+                 sigma_s=None, sigma_a=None, min_overlap=None, no_app=None, **scene_kw):
+        given = {'max_absence': max_absence, 'sigma_s': sigma_s, 'sigma_a': sigma_a, 'min_overlap': min_overlap, 'no_app': no_app}
+        self.link = bool(link)
+        self.link_kw = tr.link_arguments('VideoDemo', **{k: tr.LINK_DEFAULTS[k] if v is None else v for k, v in given.items()})
+        self.id_texture_size = _texture_size(id_texture_size)
+        self._tex = None
         self.scene = SceneDemo(model_or_engine, smpl, batch, fitter=fitter, **scene_kw)
         self.smooth, self.rounds, self.shared_shape = bool(smooth), int(rounds), bool(shared_shape)
         self.max_gap, self.min_iou, self.gap_conf = int(max_gap), float(min_iou), float(gap_conf)
@@ -72,10 +86,35 @@ class VideoDemo(object):
     def joints(self, para):
         return from_para(self.scene.smpl, para).smpl_joints.detach()
 
+    def link_tracks(self, rows, ts, plan):
+        """The identity rule on the rows [N,229] (track-major, on the device) of the TrackSet whose conf weighs the shape: the
+        descriptors (the skin from the de-normalised crops of the observed rows, through the meshes and cameras of those rows), the
+        distances of the time-admissible pairs and the linking.  -> tracks.link's dict plus 'shape' [K,10] and 'atlas' [K,24,T,T,4]
+        (device) and 'dist' [C,4] (host)."""
+        from .texture import TextureAtlas
+        sc = self.scene
+        if self._tex is None:
+            self._tex = TextureAtlas(size=self.id_texture_size, focal_length=sc.focal)
+
+        def skin(obs, view_offsets):
+            mean, std = (torch.tensor(c, device=sc.device).view(1, 3, 1, 1) for c in (constants.IMG_NORM_MEAN, constants.IMG_NORM_STD))
+            crops = (sc.crops(plan) * std + mean).clamp(0.0, 1.0)
+            drawn = rows[torch.from_numpy(obs).to(sc.device)]
+            return self._tex.unwrap(crops[torch.from_numpy(ts.row_person[obs]).to(sc.device)], sc.vertices(drawn), drawn[:, 0:3].contiguous(),
+                                    view_offsets=view_offsets)
+        shape, atlas, _ = tr.descriptors(rows, ts, skin)
+        pairs = tr.PairSet(tr.candidates(ts, self.link_kw['max_absence']), ts.K)
+        dist = tr.affinity(shape, atlas, pairs).cpu().numpy()
+        res = tr.link(ts, dist, pairs, **self.link_kw)
+        res.update({'shape': shape, 'atlas': atlas, 'dist': dist})
+        return res
+
     def __call__(self, frames, boxes, keypoints=None):
         """-> (rendered frames, people: SceneDemo's dict per frame plus 'track_id' [k], 'observed' [k] and 'para_raw' [k,229] (the
         network's rows), summary: 'tracks', 'rows', 'gap_rows', 'accel_raw' and 'accel' (the mean acceleration of the SMPL joints over
-        all tracks' interior rows before and after), 'accel_raw_tracks' / 'accel_tracks' [K])."""
+        all tracks' interior rows before and after), 'accel_raw_tracks' / 'accel_tracks' [K]).  With link=True the people dicts gain
+        'identity' [k], the summary 'identities' and 'links', and self.last 'identity' [K], 'links' [L,2], 'link_cost' [L] and 'link'
+        (link_tracks' dict with 'rows', the rows the descriptors were made from)."""
         sc = self.scene
         if len(frames) != len(boxes) or not frames:
             raise ValueError('VideoDemo: %d frames, %d box lists' % (len(frames), len(boxes)))
@@ -110,6 +149,14 @@ class VideoDemo(object):
             rows, _ = tr.smooth_para(para[to_rows], ts_para, self.lam, self.shared_shape)
             para = rows[to_people]
         summary = {'tracks': ts.K, 'rows': ts.N, 'gap_rows': int((ts.det < 0).sum())}
+        linked = None
+        if self.link:
+            rows = para[to_rows] if P else para
+            linked = self.link_tracks(rows, ts_para, plan) if P else tr.link(ts_para, np.zeros((0, 4)), np.zeros((0, 2), np.int32), **self.link_kw)
+            linked['rows'] = rows
+            if P and self.shared_shape:
+                para = tr.share_shape(rows, ts_para, linked['identity'])[0][to_people]
+            summary.update({'identities': int(linked['identity'].max()) + 1 if ts.K else 0, 'links': int(linked['links'].shape[0])})
         if P:
             a0, cnt = tr.accel(self.joints(para_raw)[to_rows], ts)
             a1, _ = tr.accel(self.joints(para)[to_rows], ts)
@@ -142,12 +189,19 @@ class VideoDemo(object):
             for n in range(plan['N']):
                 m = plan['person_frame'] == n
                 people[n].update({'para_init': init[m], 'fit_loss': loss[m], 'fit_iter': it[m]})
+        if linked is not None:
+            for n in range(plan['N']):
+                people[n]['identity'] = linked['identity'][track_p[plan['person_frame'] == n]]
         self.last = {'tracks': ts, 'plan': plan, 'render_aux': aux, 'boxes_raw': boxes_raw, 'boxes': boxes_s,
                      'para_raw': raw_h[ts.row_person] if P else raw_h, 'para': para_h[ts.row_person] if P else para_h}
+        if linked is not None:
+            self.last.update({'identity': linked['identity'], 'links': linked['links'], 'link_cost': linked['link_cost'], 'link': linked})
         return rendered, people, summary
 
 
 STREAM_LAG = 8          # the default lag and box_lag of StreamDemo: DESIGN.md 4b'-stream, the lag table
+NO_STREAM_LINK = ('StreamDemo: link=True is not available while streaming: the descriptor of the identity rule (DESIGN.md 4b\'-link) needs a '
+                  'finished track, its mean shape and the texture fused over all its observed rows; link the clip with VideoDemo')
 
 
 class StreamDemo(object):
@@ -166,10 +220,13 @@ class StreamDemo(object):
     computed from.  With shared_shape a track's shape is its prefix's mean and so moves over time.  A track holds one of `slots` slots
     from its first box until its last row is drawn.  There is no `rounds`: the fit / smooth alternation needs whole tracks and stays
     VideoDemo's.  With smooth = False observed rows keep their own box and row, and gap rows get the box stream's box.  Wraps a
-    scene.SceneDemo and does not change it; there is no CPU path."""
+    scene.SceneDemo and does not change it; there is no CPU path.  link=True raises ValueError: identities need finished tracks and
+    are VideoDemo's."""
 
     @staticmethod
-    def check_arguments(lag, box_lag, slots, max_gap, gap_conf):
+    def check_arguments(lag, box_lag, slots, max_gap, gap_conf, link=False):
+        if link:
+            raise ValueError(NO_STREAM_LINK)
         for name, v, low in (('lag', lag, 0), ('box_lag', box_lag, 0), ('slots', slots, 1), ('max_gap', max_gap, 1)):
             if isinstance(v, bool) or int(v) != v or v < low:
                 raise ValueError('StreamDemo: %s %r (an integer >= %d)' % (name, v, low))
@@ -179,8 +236,8 @@ class StreamDemo(object):
             raise ValueError('StreamDemo: gap_conf %r (in [0, 1])' % (gap_conf,))
 
     def __init__(self, model_or_engine, smpl, batch, fitter=None, smooth=True, lag=STREAM_LAG, box_lag=STREAM_LAG, slots=32, shared_shape=True,
-                 max_gap=5, min_iou=0.3, gap_conf=0., lam=tr.DEFAULT_LAM, box_lam=tr.BOX_LAM, **scene_kw):
-        self.check_arguments(lag, box_lag, slots, max_gap, gap_conf)
+                 max_gap=5, min_iou=0.3, gap_conf=0., lam=tr.DEFAULT_LAM, box_lam=tr.BOX_LAM, link=False, **scene_kw):
+        self.check_arguments(lag, box_lag, slots, max_gap, gap_conf, link)
         self.assoc = tr.OnlineAssociator(max_gap, min_iou, what='StreamDemo')
         self.smooth, self.lag, self.box_lag, self.slots = bool(smooth), int(lag), int(box_lag), int(slots)
         self.max_gap, self.gap_conf = int(max_gap), float(gap_conf)

@@ -1076,6 +1076,35 @@ int danet_track_stream_step_para(void* state, size_t state_bytes, int S, int lag
                                  const int32_t* reset, const float* rows, const float* conf, const int32_t* emit,
                                  const double* lam, int shared_shape, float* out, int32_t* valid, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Track identities (csrc/track_link.hip; tracks.py is the caller; DESIGN.md 4b'-link "the identity rule").  Two entry points, no
+ * workspace.  Index tables are passed twice, as the track ops pass track_start: the DEVICE copy the kernel reads and the HOST copy
+ * the entry point validates before anything is launched.
+ *
+ * danet_track_affinity -- shape [K,10] f32 and atlas [K,24,T,T,4] f32 (r, g, b, summed weight; 16-byte aligned), the descriptors of
+ *   K tracks; pairs [C,2] i32 in [0, K).  out [C,4] f32 (16-byte aligned) = (d_shape, d_app, overlap, S) per ordered pair (a, b):
+ *     d_shape = sum_i (shape[a,i] - shape[b,i])^2 / 10;
+ *     per texel x, wa and wb the two weights: m_x = min(1, wa) min(1, wb) where both exceed w_min = 1e-3, else 0;
+ *     S = sum m_x, n = #{m_x > 0}, u = #{wa > w_min or wb > w_min};
+ *     d_app = sum_x m_x |rgb_a - rgb_b|^2 / (3 S) where n > 0, else 0; overlap = n / u where u > 0, else 0.
+ *   The colours of a texel with m_x = 0 never enter the arithmetic: a NaN there does not spread.  Sums in double over the texels in
+ *   raster order, lane l of the pair's wave taking texels l, l + 64, ..., the 64 partials combined by a fixed butterfly; rounded to
+ *   fp32 once.  One launch, one wave per pair; C = 0 returns without a launch.
+ * danet_track_group_mean -- rows [N,229] f32 (in / out), conf [N] f32 (the caller vouches: finite, not negative).  G groups of rows
+ *   as a CSR: group_start [G+1] i32 ascending from 0 to N, group_rows [N] i32 a permutation of 0 .. N-1.  For the columns
+ *   col0 .. col0 + ncol - 1: mean [G,ncol] f32 = sum c x / sum c over the group's rows with c > 0 in CSR order (rows with c = 0 are
+ *   never read), in double, rounded once; status [G] i32 = 1 for a group without a positive weight, whose mean is 0.  With
+ *   write_back != 0 every row of a group with status 0 gets the rounded mean in those columns; a group with status 1 keeps its rows
+ *   bit for bit.  One launch, one lane per (group, column); G = 0 or N = 0 returns without a launch.
+ * No atomics, no LDS, no grid barrier, nothing read back on the host, no device allocation: both capture under a graph for fixed
+ * shapes; two runs give the same bits, and a pair's or group's result does not depend on the others of the launch.
+ */
+int danet_track_affinity(const float* shape, const float* atlas, int K, int T, const int32_t* pairs, const int32_t* pairs_host,
+                         long C, float* out, void* stream);
+int danet_track_group_mean(float* rows, const float* conf, const int32_t* group_start, const int32_t* group_start_host,
+                           const int32_t* group_rows, const int32_t* group_rows_host, int G, long N, int col0, int ncol,
+                           float* mean, int32_t* status, int write_back, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
