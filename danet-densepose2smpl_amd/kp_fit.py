@@ -15,7 +15,7 @@ import torch
 
 from . import _lib, constants
 from ._lib import check, ptr, require_gpu, stream
-from .ops import _f32, _typed
+from .ops import _f32, _per_device, _typed
 
 GROUPS = {'cam': 1, 'orient': 2, 'body': 4, 'shape': 8, 'all': 15}
 DEFAULT_STAGES = ((30, 'cam+orient'), (70, 'all'))
@@ -99,10 +99,27 @@ def openpose_to_j49(pose_keypoints_2d):
     return out
 
 
+def fill_args(a, pointers, sizes, stages, floats):
+    """Every field a fit's argument struct (_lib.KpFitArgs, _lib.DenseFitArgs) holds, by name: `pointers` {field: device address or
+    None}, `sizes` {field: int}, `stages` parse_stages' two lists, `floats` {field: float}; nstages and T come from the stages."""
+    for k, v in pointers.items():
+        setattr(a, k, v)
+    for i, (n, m) in enumerate(zip(*stages)):
+        a.stage_iters[i], a.stage_mask[i] = n, m
+    for k, v in dict(sizes, nstages=len(stages[0]), T=sum(stages[0]), **floats).items():
+        setattr(a, k, v)
+    return a
+
+
 class KeypointFitter(object):
     """KeypointFitter(smpl, stages=, lr=, sigma=, w_pose=, w_orient=, w_shape=, focal=, res=, kappa=None): `smpl` the SMPL layer (on the
     GPU when fit is called).  kappa None: 2 focal / res, the training convention; the scene demo passes 2 focal / 224.  The defaults
-    are those of DESIGN.md, chosen on the synthetic recovery case."""
+    are those of DESIGN.md, chosen on the synthetic recovery case.  dense_fit.DenseFitter is this class with its own tables, struct
+    and entry point: what the two fits share is stated here."""
+    ARGS, ENTRY = 'KpFitArgs', 'danet_kp_fit'
+    F32_KEYS, I32_KEYS, HOST_KEYS = ('v_template', 'basis', 'basisT', 'weights', 'jx'), ('lm', 'jmap'), ('S', 'Sp', 'NB')
+    FLOATS = ('focal', 'res', 'sigma', 'w_orient', 'w_pose', 'w_shape', 'lr')
+    ONE_DEVICE = 'para, keypoints, the SMPL layer and the tables'
 
     def __init__(self, smpl, stages=DEFAULT_STAGES, lr=0.02, sigma=0.1, w_pose=0.005, w_orient=0.005, w_shape=0.002,
                  focal=constants.FOCAL_LENGTH, res=constants.IMG_RES, kappa=None):
@@ -120,20 +137,76 @@ class KeypointFitter(object):
     def iterations(self):
         return sum(n for n, _ in self.stages)
 
+    def host_tables(self, device=None):
+        """fit_tables' dict, built at the first call."""
+        if self._host is None:
+            self._host = fit_tables(self.smpl)
+        return self._host
+
     def tables(self, device):
         """The sub-tables on `device` (fp32 / int32), built once and cached per device."""
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        t = self._dev.get(key)
-        if t is None:
-            if self._host is None:
-                self._host = fit_tables(self.smpl)
-            h = self._host
+        def make():
+            h = self.host_tables(device)
             up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(device)          # noqa: E731
-            t = {k: up(h[k], np.float32) for k in ('v_template', 'basis', 'basisT', 'weights', 'jx')}
-            t.update({k: up(h[k], np.int32) for k in ('lm', 'jmap')})
-            t.update({k: h[k] for k in ('S', 'Sp', 'NB')})
-            self._dev[key] = t
-        return t
+            t = {k: up(h[k], np.float32) for k in self.F32_KEYS}
+            t.update({k: up(h[k], np.int32) for k in self.I32_KEYS})
+            t.update({k: h[k] for k in self.HOST_KEYS})
+            return t
+        return _per_device(self._dev, device, make)
+
+    def _table_shapes(self, t):
+        """(key, dtype, shape) of every device table the kernel reads, in the order they are checked."""
+        Sp, NB = int(t['Sp']), int(t['NB'])
+        return (('v_template', torch.float32, (Sp * 3,)), ('basis', torch.float32, (207 + NB, Sp * 3)), ('basisT', torch.float32, (Sp * 3, NKP)),
+                ('weights', torch.float32, (Sp, 24)), ('jx', torch.float32, (t['jx'].shape[0], Sp)), ('lm', torch.int32, (t['lm'].numel(),)),
+                ('jmap', torch.int32, (49,)))
+
+    def _rows(self, para):
+        """-> (the tables on para's device, para as [P,229] f32, P >= 1)."""
+        what = type(self).__name__ + '.fit'
+        tables = self.tables(para.device)
+        p = _f32(para, (None, 3 + int(tables['NB']) + 216), what + ': para')
+        if p.shape[0] < 1:
+            raise ValueError(what + ': an empty batch')
+        return tables, p
+
+    def _own(self, P, tables, dev):
+        """-> (a subclass's own sizes {field: int}, its own output tensors {field: tensor}, which join the info dict)."""
+        return {}, {}
+
+    def _fit(self, tables, p, kp, own, stages, kappa, return_history, return_grad):
+        """The fit of the rows p [P,229] to kp [P,49,3] (both fp32 on the GPU) and to `own`, a subclass's further inputs {field: tensor}
+        (they join the info dict): the table checks, the one-device check, the outputs and the workspace, the struct, ONE launch."""
+        what = type(self).__name__ + '.fit'
+        P, dev, NB = p.shape[0], p.device, int(tables['NB'])
+        held = {k: _typed(tables[k], dt, shape, '%s: %s' % (what, k)) for k, dt, shape in self._table_shapes(tables)}
+        held['J_template'] = _typed(self.smpl.J_template, torch.float32, (24, 3), what + ': J_template')
+        held['J_shapedirs'] = _typed(self.smpl.J_shapedirs, torch.float32, (72, NB), what + ': J_shapedirs')
+        held['parents'] = _typed(self.smpl.parents, torch.int32, (24,), what + ': parents')
+        if any(t.device != dev for t in [kp] + list(own.values()) + list(held.values())):
+            raise ValueError('%s: %s must be on one device' % (what, self.ONE_DEVICE))
+        parsed = parse_stages(self.stages if stages is None else stages)
+        L = _lib.lib()
+        out = {'para_fit': torch.empty_like(p), 'history': torch.empty(P, sum(parsed[0]) + 1, device=dev, dtype=torch.float32),
+               'best_iter': torch.empty(P, device=dev, dtype=torch.int32), 'status': torch.empty(P, device=dev, dtype=torch.int32)}
+        sizes, more = self._own(P, tables, dev)
+        out.update(more)
+        grad = torch.empty(P, 3 + NB + 144, device=dev, dtype=torch.float32) if return_grad else None
+        nws = getattr(L, self.ENTRY + '_ws_floats')(P, int(tables['Sp']))
+        ws = torch.empty(nws, device=dev, dtype=torch.float32)
+        NL, NE = held['lm'].numel(), held['jx'].shape[0]
+        tensors = dict(held, para=p, kp=kp, ws=ws, grad0=grad, jx=held['jx'] if NE else None, lm=held['lm'] if NL else None, **own, **out)
+        floats = dict({k: getattr(self, k) for k in self.FLOATS}, kappa=float(self.kappa if kappa is None else kappa))
+        a = fill_args(getattr(_lib, self.ARGS)(), {k: ptr(t) for k, t in tensors.items()},
+                      dict(sizes, P=P, NB=NB, S=int(tables['S']), Sp=int(tables['Sp']), NL=NL, NE=NE), parsed, floats)
+        check(getattr(L, self.ENTRY)(ctypes.addressof(a), nws, stream()), self.ENTRY)
+        para_fit = out.pop('para_fit')
+        if not (return_history or return_grad):
+            return para_fit
+        info = dict(out, **own)
+        if return_grad:
+            info['grad'] = grad
+        return para_fit, info
 
     def fit(self, para, keypoints, return_history=False, return_grad=False, stages=None, kappa=None):
         """para [P,229], keypoints [P,49,3] on the GPU -> para_fit [P,229]; with return_history / return_grad also a dict with 'history'
@@ -141,54 +214,6 @@ class KeypointFitter(object):
         go through the rules of ops.py (_f32, _typed) and then to danet_kp_fit, one launch."""
         require_gpu(para, 'KeypointFitter.fit')
         require_gpu(keypoints, 'KeypointFitter.fit: keypoints')
-        tables = self.tables(para.device)
-        stages = self.stages if stages is None else stages
-        kappa = self.kappa if kappa is None else kappa
-        S, Sp, NB = int(tables['S']), int(tables['Sp']), int(tables['NB'])
-        p = _f32(para, (None, 3 + NB + 216), 'KeypointFitter.fit: para')
-        P = p.shape[0]
-        if P < 1:
-            raise ValueError('KeypointFitter.fit: an empty batch')
-        kp = _f32(keypoints, (P, 49, 3), 'KeypointFitter.fit: keypoints')
-        dev = p.device
-        NL, NE = tables['lm'].numel(), tables['jx'].shape[0]
-        NK = 207 + NB
-        vt = _typed(tables['v_template'], torch.float32, (Sp * 3,), 'KeypointFitter.fit: v_template')
-        basis = _typed(tables['basis'], torch.float32, (NK, Sp * 3), 'KeypointFitter.fit: basis')
-        basisT = _typed(tables['basisT'], torch.float32, (Sp * 3, NKP), 'KeypointFitter.fit: basisT')
-        wts = _typed(tables['weights'], torch.float32, (Sp, 24), 'KeypointFitter.fit: weights')
-        jx = _typed(tables['jx'], torch.float32, (NE, Sp), 'KeypointFitter.fit: jx')
-        lm = _typed(tables['lm'], torch.int32, (NL,), 'KeypointFitter.fit: lm')
-        jmap = _typed(tables['jmap'], torch.int32, (49,), 'KeypointFitter.fit: jmap')
-        Jt = _typed(self.smpl.J_template, torch.float32, (24, 3), 'KeypointFitter.fit: J_template')
-        Jd = _typed(self.smpl.J_shapedirs, torch.float32, (72, NB), 'KeypointFitter.fit: J_shapedirs')
-        par = _typed(self.smpl.parents, torch.int32, (24,), 'KeypointFitter.fit: parents')
-        if any(t.device != dev for t in (kp, vt, basis, basisT, wts, jx, lm, jmap, Jt, Jd, par)):
-            raise ValueError('KeypointFitter.fit: para, keypoints, the SMPL layer and the tables must be on one device')
-        iters, masks = parse_stages(stages)
-        T = sum(iters)
-        L = _lib.lib()
-        a = _lib.KpFitArgs()
-        para_fit = torch.empty_like(p)
-        history = torch.empty(P, T + 1, device=dev, dtype=torch.float32)
-        best_iter = torch.empty(P, device=dev, dtype=torch.int32)
-        status = torch.empty(P, device=dev, dtype=torch.int32)
-        grad = torch.empty(P, 3 + NB + 144, device=dev, dtype=torch.float32) if return_grad else None
-        nws = L.danet_kp_fit_ws_floats(P, Sp)
-        ws = torch.empty(nws, device=dev, dtype=torch.float32)
-        for k, t in (('para', p), ('kp', kp), ('J_template', Jt), ('J_shapedirs', Jd), ('parents', par), ('v_template', vt), ('basis', basis),
-                     ('basisT', basisT), ('weights', wts), ('jx', jx if NE else None), ('lm', lm if NL else None), ('jmap', jmap), ('ws', ws),
-                     ('para_fit', para_fit), ('history', history), ('best_iter', best_iter), ('status', status), ('grad0', grad)):
-            setattr(a, k, ptr(t))
-        for i, (n, m) in enumerate(zip(iters, masks)):
-            a.stage_iters[i], a.stage_mask[i] = n, m
-        a.P, a.NB, a.S, a.Sp, a.NL, a.NE, a.nstages, a.T = P, NB, S, Sp, NL, NE, len(iters), T
-        a.focal, a.res, a.kappa, a.sigma = self.focal, self.res, float(kappa), self.sigma
-        a.w_orient, a.w_pose, a.w_shape, a.lr = self.w_orient, self.w_pose, self.w_shape, self.lr
-        check(L.danet_kp_fit(ctypes.addressof(a), nws, stream()), 'danet_kp_fit')
-        if not (return_history or return_grad):
-            return para_fit
-        info = {'history': history, 'best_iter': best_iter, 'status': status}
-        if return_grad:
-            info['grad'] = grad
-        return para_fit, info
+        tables, p = self._rows(para)
+        kp = _f32(keypoints, (p.shape[0], 49, 3), 'KeypointFitter.fit: keypoints')
+        return self._fit(tables, p, kp, {}, stages, kappa, return_history, return_grad)

@@ -82,6 +82,29 @@ def _host_i32(a):
     return np.ascontiguousarray(a, np.int32).ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
 
 
+def _int(v, what, name, low=None, high=None):
+    """`v` as an int where it is a whole number (3, 3.0, np.int64(3)) inside [low, high]; a bool is refused."""
+    if isinstance(v, bool) or int(v) != v or (low is not None and v < low) or (high is not None and v > high):
+        bound = '' if low is None and high is None else ' >= %d' % low if high is None else ' <= %d' % high if low is None \
+            else ' in %d..%d' % (low, high)
+        raise ValueError('%s: %s %r (an integer%s)' % (what, name, v, bound))
+    return int(v)
+
+
+def _device_key(device):
+    """(type, index) of a device; a CUDA device without an index is the current one, any other device never asks torch.cuda."""
+    device = torch.device(device)
+    return device.type, torch.cuda.current_device() if device.index is None and device.type == 'cuda' else device.index
+
+
+def _per_device(cache, device, make):
+    """cache[_device_key(device)], made by make() at the first call and kept: no upload inside a captured region afterwards."""
+    key = _device_key(device)
+    if key not in cache:
+        cache[key] = make()
+    return cache[key]
+
+
 def _host_i64(a):
     return np.ascontiguousarray(a, np.int64).ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
 

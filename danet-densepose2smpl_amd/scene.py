@@ -48,6 +48,48 @@ def whole_image_box(shape):
     return np.array([(W - 1) / 2.0, (H - 1) / 2.0]), max(H, W) / 200.0
 
 
+def box_row(box):
+    """A box (center [2], scale, ..) -> the row a box smoother works on: (cx, cy, log scale), float32 [3]."""
+    c = np.asarray(box[0], np.float64).reshape(2)
+    return np.array((c[0], c[1], np.log(float(box[1]))), np.float32)
+
+
+def row_box(row):
+    """The inverse of box_row for a float32 row: (center [2] float64, scale = exp in float64)."""
+    return row[:2].astype(np.float64), float(np.exp(np.float64(row[2])))
+
+
+def timed(ms, key, f):
+    """f() between two device synchronisations; its milliseconds on the host clock are added to ms[key]."""
+    import time
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = f()
+    torch.cuda.synchronize()
+    ms[key] = ms.get(key, 0.0) + (time.perf_counter() - t0) * 1e3
+    return r
+
+
+def fit_record(fitted, P):
+    """fitted = (the start rows [P,229], the fit's info dict or None where P = 0) -> (init [P,229], loss [P,2] f32: E at the start
+    and at the best iterate, it [P] int32: the best iterate), on the host."""
+    init = fitted[0].cpu().numpy()
+    if not P:
+        return init, np.zeros((0, 2), np.float32), np.zeros(0, np.int32)
+    hist, it = fitted[1]['history'].cpu().numpy(), fitted[1]['best_iter'].cpu().numpy()
+    return init, np.stack([hist[:, 0], hist[np.arange(P), it]], 1), it
+
+
+def fit_columns(fitted, P):
+    """The people-dict columns of a fit ({} without one): 'para_init', 'fit_loss', 'fit_iter'."""
+    return {} if fitted is None else dict(zip(('para_init', 'fit_loss', 'fit_iter'), fit_record(fitted, P)))
+
+
+def split_people(people, plan):
+    """One dict over all people of a plan -> one dict per frame, every column split by plan['person_frame']."""
+    return [{k: v[m] for k, v in people.items()} for m in (plan['person_frame'] == n for n in range(plan['N']))]
+
+
 # ---- cameras ---------------------------------------------------------------------------------------------------------------------
 def person_cameras(cam, tinv, frame_shapes, person_frame, res, focal=5000., focal_full=None):
     """The per-person arguments of ops.scene_render, in float64 on the host (the scene cameras).
@@ -263,41 +305,39 @@ class SceneDemo(object):
         return ops.scene_render(rverts, vcol, t.faces2, cam_t, plan['d_proj'], plan['d_dscale'], plan['d_person_frame'], plan['d_src'],
                                 plan['d_offsets'], plan['d_shapes'], return_aux=return_aux, host=host)
 
+    def infer_stage(self, plan):
+        """-> (para [P,229], the decoded IUV images where the fitter is a dense one, else None); nothing runs for P = 0."""
+        if plan['P'] and self.dense:
+            return self.infer(plan, return_iuv=True)
+        return (self.infer(plan) if plan['P'] else torch.zeros(0, 229, device=self.device)), None
+
+    def fit_stage(self, para, plan, keypoints, iuv):
+        """-> (fitted, para): where there is a fitter and something to fit to, fitted = (the start rows, the fit's info; None for
+        P = 0) and para the fitted rows; else (None, para as it came)."""
+        if self.fitter is None or not (self.dense or keypoints is not None):
+            return None, para
+        if not plan['P']:
+            return (para, None), para
+        para_fit, info = self.fit(para, plan, keypoints, iuv)
+        return (para, info), para_fit
+
+    def people(self, para_h, verts_h, plan, **columns):
+        """One dict over all P people of the plan from the rows and vertices on the host, plus further per-person columns."""
+        P = plan['P']
+        if P:
+            k = person_cameras(para_h[:, 0:3], plan['tinv'], plan['shapes'], plan['person_frame'], self.res, self.focal, self.focal_full)
+        return dict({'para': para_h, 'cam': para_h[:, 0:3], 'cam_t_full': k['cam_t_full'] if P else np.zeros((0, 3)),
+                     'focal_full': k['focal_full'] if P else np.zeros(0), 'center': plan['center'], 'scale': plan['scale'], 'vertices': verts_h},
+                    **columns)
+
     def __call__(self, frames, boxes, keypoints=None):
         plan = self.prepare(frames, boxes)
         P = plan['P']
-        iuv = None
-        if P and self.dense:
-            para, iuv = self.infer(plan, return_iuv=True)
-        else:
-            para = self.infer(plan) if P else torch.zeros(0, 229, device=self.device)
-        fitted = None
-        if self.fitter is not None and (self.dense or keypoints is not None):
-            fitted = (para, None)
-            if P:
-                para_fit, info = self.fit(para, plan, keypoints, iuv)
-                fitted, para = (para, info), para_fit
+        para, iuv = self.infer_stage(plan)
+        fitted, para = self.fit_stage(para, plan, keypoints, iuv)
         verts = self.vertices(para) if P else None
         out = self.render(para, plan, vertices=verts)
         rendered = unpack_frames(out.cpu().numpy(), plan['offsets'], plan['shapes'])
         para_h = para.cpu().numpy()
         verts_h = verts.cpu().numpy() if P else np.zeros((0, 0, 3), np.float32)
-        if P:
-            k = person_cameras(para_h[:, 0:3], plan['tinv'], plan['shapes'], plan['person_frame'], self.res, self.focal, self.focal_full)
-        people = []
-        for n in range(plan['N']):
-            m = plan['person_frame'] == n
-            people.append({'para': para_h[m], 'cam': para_h[m, 0:3], 'cam_t_full': k['cam_t_full'][m] if P else np.zeros((0, 3)),
-                           'focal_full': k['focal_full'][m] if P else np.zeros(0), 'center': plan['center'][m], 'scale': plan['scale'][m],
-                           'vertices': verts_h[m]})
-        if fitted is not None:
-            init = fitted[0].cpu().numpy()
-            if P:
-                hist, it = fitted[1]['history'].cpu().numpy(), fitted[1]['best_iter'].cpu().numpy()
-                loss = np.stack([hist[:, 0], hist[np.arange(P), it]], 1)
-            else:
-                loss, it = np.zeros((0, 2), np.float32), np.zeros(0, np.int32)
-            for n in range(plan['N']):
-                m = plan['person_frame'] == n
-                people[n].update({'para_init': init[m], 'fit_loss': loss[m], 'fit_iter': it[m]})
-        return rendered, people
+        return rendered, split_people(self.people(para_h, verts_h, plan, **fit_columns(fitted, P)), plan)

@@ -30,7 +30,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, require_gpu, stream
-from .ops import _ascending, _f32, _host_i32, _shape, _workspace
+from .ops import _ascending, _device_key, _f32, _host_i32, _int, _per_device, _shape, _texture_size, _typed, _workspace
 
 PARA = 229
 CHANNELS = 157
@@ -63,18 +63,23 @@ class TrackSet(object):
         N = self.frame.size
         if self.track_start.ndim != 1 or self.track_start.size < 1 or self.det.shape != (N,) or self.conf.shape != (N,):
             raise ValueError('TrackSet: track_start [K+1], frame / det / conf [N] expected')
-        if self.K:
-            _ascending(self.track_start, N, 'TrackSet: track_start', integers=True)
-        elif N or self.track_start[0] != 0:
-            raise ValueError('TrackSet: rows without a track')
-        if not (np.isfinite(self.conf).all() and (self.conf >= 0).all()):
-            raise ValueError('TrackSet: conf must be finite and not negative')
+        self.check('TrackSet')
         self.track = np.repeat(np.arange(self.K, dtype=np.int32), np.diff(self.track_start))
         gap = self.det < 0
         self.person_row = np.lexsort((np.where(gap, self.track, self.det), gap, self.frame)).astype(np.int64)
         self.row_person = np.empty(N, np.int64)
         self.row_person[self.person_row] = np.arange(N)
         self._dev = {}
+        self._groups = None                                              # track_groups' RowGroups
+
+    def check(self, what):
+        """The invariants of the fields, which are plain arrays anyone can assign to: the constructor and every op ask."""
+        if self.K:
+            _ascending(self.track_start, self.N, what + ': track_start', integers=True)
+        elif self.N or self.track_start[0] != 0:
+            raise ValueError('%s: rows without a track' % what)
+        if not (np.isfinite(self.conf).all() and (self.conf >= 0).all()):
+            raise ValueError('%s: conf must be finite and not negative' % what)
 
     @property
     def K(self):
@@ -94,11 +99,7 @@ class TrackSet(object):
 
     def device(self, device):
         """(track_start, conf) on `device`, uploaded at the first call and kept: no copy inside a captured region afterwards."""
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        t = self._dev.get(key)
-        if t is None:
-            t = self._dev[key] = (torch.from_numpy(self.track_start).to(device), torch.from_numpy(self.conf).to(device))
-        return t
+        return _per_device(self._dev, device, lambda: (torch.from_numpy(self.track_start).to(device), torch.from_numpy(self.conf).to(device)))
 
     def arrays(self):
         return {'track_start': self.track_start, 'frame': self.frame, 'det': self.det, 'conf': self.conf, 'person_row': self.person_row,
@@ -185,15 +186,16 @@ def associate(boxes, max_gap=5, min_iou=0.3):
 
 
 # ---- the ops ---------------------------------------------------------------------------------------------------------------------
+def _trackset(x, what):
+    if not isinstance(x, TrackSet):
+        raise ValueError('%s: a TrackSet expected, got %s' % (what, type(x).__name__))
+    return x
+
+
 def _tracks(tracks, N, what):
-    if not isinstance(tracks, TrackSet):
-        raise ValueError('%s: a TrackSet expected, got %s' % (what, type(tracks).__name__))
-    if tracks.N != N:
+    if _trackset(tracks, what).N != N:
         raise ValueError('%s: %d rows, the TrackSet has %d' % (what, N, tracks.N))
-    if tracks.K:
-        _ascending(tracks.track_start, N, what + ': track_start', integers=True)
-    if not (np.isfinite(tracks.conf).all() and (tracks.conf >= 0).all()):
-        raise ValueError('%s: conf must be finite and not negative' % what)
+    tracks.check(what)
     return tracks
 
 
@@ -211,51 +213,53 @@ def _lam(v, what):
     return v
 
 
-def smooth(values, tracks, lam_vel=BOX_LAM[0], lam_acc=BOX_LAM[1]):
-    """values [N,C] on the GPU -> (smoothed [N,C] f32, status [K] int32: 1 where a track has no positive weight and came back as it
-    was).  Two launches, no synchronisation, no allocation by data."""
-    N, C = _rows(values, (None, None), 'tracks.smooth: values').shape
-    ts = _tracks(tracks, N, 'tracks.smooth')
-    lv, la = _lam(lam_vel, 'tracks.smooth: lam_vel'), _lam(lam_acc, 'tracks.smooth: lam_acc')
+def _lam_pairs(lam, what):
+    """Three (lam_vel, lam_acc) pairs, for cam, betas and the rotations -> the six floats."""
+    lam = [tuple(pair) for pair in lam]
+    if len(lam) != 3 or any(len(pair) != 2 for pair in lam):
+        raise ValueError('%s: lam must hold three (lam_vel, lam_acc) pairs' % what)
+    return [_lam(x, what + ': lam') for pair in lam for x in pair]
+
+
+def _smooth(what, name, rows, width, tracks, lam, channels, call):
+    """smooth and smooth_para up to the entry point: rows [N,width] (None: any), lam() the checked weights (asked for after the rows
+    and the TrackSet, before the device), `channels` what the workspace is sized for (None: the rows' width) and call(L, v, conf,
+    start, host_start, N, C, K, lam, out, status, ws, nws) the launch."""
+    N, C = _rows(rows, (None, width), '%s: %s' % (what, name)).shape
+    ts = _tracks(tracks, N, what)
+    lam = lam()
     if C < 1:
-        raise ValueError('tracks.smooth: no channel')
-    require_gpu(values, 'tracks.smooth')
-    v = _f32(values, (N, C), 'tracks.smooth: values')
+        raise ValueError('%s: no channel' % what)
+    require_gpu(rows, what)
+    v = _f32(rows, (N, C), '%s: %s' % (what, name))
     out = torch.empty_like(v)
     status = torch.empty(ts.K, device=v.device, dtype=torch.int32)
     if N == 0:
         return out, status.fill_(1) if ts.K else status
     d_start, d_conf = ts.device(v.device)
     L = _lib.lib()
-    nws = L.danet_track_smooth_ws_bytes(N, C)
+    nws = L.danet_track_smooth_ws_bytes(N, channels or C)
     ws = _workspace(nws, v.device)
-    check(L.danet_track_smooth(ptr(v), ptr(d_conf), ptr(d_start), _host_i32(ts.track_start), N, C, ts.K, lv, la, ptr(out), ptr(status),
-                               ptr(ws), nws, stream()), 'danet_track_smooth')
+    call(L, ptr(v), ptr(d_conf), ptr(d_start), _host_i32(ts.track_start), N, C, ts.K, lam, ptr(out), ptr(status), ptr(ws), nws)
     return out, status
+
+
+def smooth(values, tracks, lam_vel=BOX_LAM[0], lam_acc=BOX_LAM[1]):
+    """values [N,C] on the GPU -> (smoothed [N,C] f32, status [K] int32: 1 where a track has no positive weight and came back as it
+    was).  Two launches, no synchronisation, no allocation by data."""
+    def call(L, v, conf, start, host_start, N, C, K, lam, out, status, ws, nws):
+        check(L.danet_track_smooth(v, conf, start, host_start, N, C, K, lam[0], lam[1], out, status, ws, nws, stream()), 'danet_track_smooth')
+    return _smooth('tracks.smooth', 'values', values, None, tracks,
+                   lambda: (_lam(lam_vel, 'tracks.smooth: lam_vel'), _lam(lam_acc, 'tracks.smooth: lam_acc')), None, call)
 
 
 def smooth_para(para, tracks, lam=DEFAULT_LAM, shared_shape=True):
     """para [N,229] on the GPU (cam, betas, 24 matrices) -> (smoothed [N,229] f32, status [K] int32).  `lam`: three (lam_vel, lam_acc)
     pairs, for cam, betas and the rotations.  Three launches, no synchronisation, no allocation by data."""
-    N = _rows(para, (None, PARA), 'tracks.smooth_para: para').shape[0]
-    ts = _tracks(tracks, N, 'tracks.smooth_para')
-    lam = [tuple(pair) for pair in lam]
-    if len(lam) != 3 or any(len(pair) != 2 for pair in lam):
-        raise ValueError('tracks.smooth_para: lam must hold three (lam_vel, lam_acc) pairs')
-    flat = [_lam(x, 'tracks.smooth_para: lam') for pair in lam for x in pair]
-    require_gpu(para, 'tracks.smooth_para')
-    p = _f32(para, (N, PARA), 'tracks.smooth_para: para')
-    out = torch.empty_like(p)
-    status = torch.empty(ts.K, device=p.device, dtype=torch.int32)
-    if N == 0:
-        return out, status.fill_(1) if ts.K else status
-    d_start, d_conf = ts.device(p.device)
-    L = _lib.lib()
-    nws = L.danet_track_smooth_ws_bytes(N, CHANNELS)
-    ws = _workspace(nws, p.device)
-    check(L.danet_track_smooth_para(ptr(p), ptr(d_conf), ptr(d_start), _host_i32(ts.track_start), N, ts.K, (ctypes.c_double * 6)(*flat),
-                                    1 if shared_shape else 0, ptr(out), ptr(status), ptr(ws), nws, stream()), 'danet_track_smooth_para')
-    return out, status
+    def call(L, v, conf, start, host_start, N, C, K, lam, out, status, ws, nws):
+        check(L.danet_track_smooth_para(v, conf, start, host_start, N, K, (ctypes.c_double * 6)(*lam), 1 if shared_shape else 0, out, status,
+                                        ws, nws, stream()), 'danet_track_smooth_para')
+    return _smooth('tracks.smooth_para', 'para', para, PARA, tracks, lambda: _lam_pairs(lam, 'tracks.smooth_para'), CHANNELS, call)
 
 
 def accel(joints, tracks, joints_ref=None):
@@ -302,12 +306,11 @@ class PairSet(object):
             p = np.zeros((0, 2), np.int32)
         if p.ndim != 2 or p.shape[1] != 2 or not np.issubdtype(p.dtype, np.integer):
             raise ValueError('tracks.PairSet: pairs must be [C,2] integers, got %s %s' % (p.dtype, p.shape))
-        if isinstance(K, bool) or int(K) != K or K < 0:
-            raise ValueError('tracks.PairSet: K %r (an integer >= 0)' % (K,))
+        K = _int(K, 'tracks.PairSet', 'K', 0)
         if ((p < 0) | (p >= K)).any():
             c = int(np.nonzero(((p < 0) | (p >= K)).any(1))[0][0])
             raise ValueError('tracks.PairSet: pair %d = %s names a track outside [0, %d)' % (c, p[c].tolist(), K))
-        self.pairs, self.K = np.ascontiguousarray(p, np.int32), int(K)
+        self.pairs, self.K = np.ascontiguousarray(p, np.int32), K
         self._dev = {}
 
     @property
@@ -315,11 +318,15 @@ class PairSet(object):
         return self.pairs.shape[0]
 
     def device(self, device):
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        t = self._dev.get(key)
-        if t is None:
-            t = self._dev[key] = torch.from_numpy(self.pairs).to(device)
-        return t
+        return _per_device(self._dev, device, lambda: torch.from_numpy(self.pairs).to(device))
+
+
+def _pairset(pairs, K, what):
+    """pairs [C,2] host integers in [0, K), or a PairSet made for K tracks -> the PairSet."""
+    ps = pairs if isinstance(pairs, PairSet) else PairSet(pairs, K)
+    if ps.K != K:
+        raise ValueError('%s: the PairSet was made for %d tracks, there are %d' % (what, ps.K, K))
+    return ps
 
 
 def _span(ts):
@@ -329,16 +336,10 @@ def _span(ts):
     return ts.frame[ts.track_start[:-1]].astype(np.int64), ts.frame[ts.track_start[1:] - 1].astype(np.int64)
 
 
-def _absence(v, what):
-    if isinstance(v, bool) or int(v) != v or v < 1:
-        raise ValueError('%s: max_absence %r (an integer >= 1)' % (what, v))
-    return int(v)
-
-
 def link_arguments(what, max_absence, sigma_s, sigma_a, min_overlap, no_app):
     """The checked thresholds of the identity rule as a dict: max_absence an integer >= 1, sigma_s and sigma_a finite and positive,
     min_overlap and no_app finite and not negative."""
-    thr = {'max_absence': _absence(max_absence, what)}
+    thr = {'max_absence': _int(max_absence, what, 'max_absence', 1)}
     for name, v, positive in (('sigma_s', sigma_s, True), ('sigma_a', sigma_a, True), ('min_overlap', min_overlap, False), ('no_app', no_app, False)):
         v = float(v)
         if not np.isfinite(v) or v < 0 or (positive and v == 0):
@@ -349,9 +350,8 @@ def link_arguments(what, max_absence, sigma_s, sigma_a, min_overlap, no_app):
 
 def candidates(ts, max_absence=LINK_DEFAULTS['max_absence']):
     """The ordered pairs (a, b) with 1 <= first_frame(b) - last_frame(a) <= max_absence, ascending in (a, b): [C,2] int32 (host)."""
-    if not isinstance(ts, TrackSet):
-        raise ValueError('tracks.candidates: a TrackSet expected, got %s' % type(ts).__name__)
-    A = _absence(max_absence, 'tracks.candidates')
+    _trackset(ts, 'tracks.candidates')
+    A = _int(max_absence, 'tracks.candidates', 'max_absence', 1)
     if ts.K == 0:
         return np.zeros((0, 2), np.int32)
     first, last = _span(ts)
@@ -388,11 +388,7 @@ class RowGroups(object):
         return self.rows.size
 
     def device(self, device):
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        t = self._dev.get(key)
-        if t is None:
-            t = self._dev[key] = (torch.from_numpy(self.start).to(device), torch.from_numpy(self.rows).to(device))
-        return t
+        return _per_device(self._dev, device, lambda: (torch.from_numpy(self.start).to(device), torch.from_numpy(self.rows).to(device)))
 
 
 def group_mean(para_rows, conf, groups, col0=3, ncol=10, write_back=False):
@@ -409,14 +405,12 @@ def group_mean(para_rows, conf, groups, col0=3, ncol=10, write_back=False):
     if groups.N != N:
         raise ValueError('%s: %d rows, the groups hold %d' % (what, N, groups.N))
     for name, v in (('col0', col0), ('ncol', ncol)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError('%s: %s %r (an integer)' % (what, name, v))
+        _int(v, what, name)
     if col0 < 0 or ncol < 1 or col0 + ncol > PARA:
         raise ValueError('%s: columns %d .. %d of %d' % (what, col0, col0 + ncol, PARA))
     require_gpu(para_rows, what)
     require_gpu(conf, what + ': conf')
     if write_back:
-        from .ops import _typed
         rows = _typed(para_rows, torch.float32, (N, PARA), what + ': para_rows (write_back)')
     else:
         rows = _f32(para_rows, (N, PARA), what + ': para_rows')
@@ -437,10 +431,9 @@ def group_mean(para_rows, conf, groups, col0=3, ncol=10, write_back=False):
 
 def track_groups(ts):
     """Every track a group, its rows in ascending t (made once per TrackSet)."""
-    g = ts._dev.get('track_groups')
-    if g is None:
-        g = ts._dev['track_groups'] = RowGroups(ts.track_start, np.arange(ts.N, dtype=np.int32))
-    return g
+    if ts._groups is None:
+        ts._groups = RowGroups(ts.track_start, np.arange(ts.N, dtype=np.int32))
+    return ts._groups
 
 
 def descriptors(para_rows, tracks, atlas_builder=None, texture_size=ID_TEXTURE_SIZE):
@@ -460,7 +453,6 @@ def descriptors(para_rows, tracks, atlas_builder=None, texture_size=ID_TEXTURE_S
     off = np.concatenate([[0], np.cumsum(np.add.reduceat(ts.observed.astype(np.int64), ts.track_start[:-1]))]).astype(np.int32) if ts.K \
         else np.zeros(1, np.int32)
     if atlas_builder is None:
-        from .ops import _texture_size
         T = _texture_size(texture_size)
         atlas = torch.zeros(ts.K, PARTS, T, T, 4, device=p.device, dtype=torch.float32)
     else:
@@ -480,9 +472,7 @@ def affinity(shape, atlas, pairs):
     T = atlas.shape[2]
     if atlas.shape[3] != T or T < 2 or T > 4096:
         raise ValueError('tracks.affinity: atlas %s, expected [K,24,T,T,4] with T in [2, 4096]' % (tuple(atlas.shape),))
-    ps = pairs if isinstance(pairs, PairSet) else PairSet(pairs, K)
-    if ps.K != K:
-        raise ValueError('tracks.affinity: the PairSet was made for %d tracks, there are %d' % (ps.K, K))
+    ps = _pairset(pairs, K, 'tracks.affinity')
     require_gpu(shape, 'tracks.affinity')
     require_gpu(atlas, 'tracks.affinity: atlas')
     s = _f32(shape, (K, 10), 'tracks.affinity: shape')
@@ -506,12 +496,8 @@ def link(tracks, dist, pairs, max_absence=LINK_DEFAULTS['max_absence'], sigma_s=
     by their first track's id), 'links' [L,2] int32 in acceptance order, 'link_cost' [L] float64, 'pairs' [C,2] int32, 'cost' [C]
     float64 (inf outside the time window) and 'admissible' [C] bool (inside the window)."""
     what = 'tracks.link'
-    if not isinstance(tracks, TrackSet):
-        raise ValueError('%s: a TrackSet expected, got %s' % (what, type(tracks).__name__))
-    K = tracks.K
-    ps = pairs if isinstance(pairs, PairSet) else PairSet(pairs, K)
-    if ps.K != K:
-        raise ValueError('%s: the PairSet was made for %d tracks, there are %d' % (what, ps.K, K))
+    K = _trackset(tracks, what).K
+    ps = _pairset(pairs, K, what)
     d = dist.detach().cpu().numpy() if torch.is_tensor(dist) else np.asarray(dist)
     if d.shape != (ps.C, 4) or not np.issubdtype(d.dtype, np.floating):
         raise ValueError('%s: dist must be [%d,4] floating point, got %s %s' % (what, ps.C, d.dtype, d.shape))
@@ -607,20 +593,16 @@ class StreamSmoother(object):
     def __init__(self, slots, lag, max_new=1, channels=None, para=False, lam=None, shared_shape=True, device=None):
         what = 'tracks.StreamSmoother'
         for name, v, low in (('slots', slots, 1), ('lag', lag, 0), ('max_new', max_new, 1)):
-            if isinstance(v, bool) or int(v) != v or v < low:
-                raise ValueError('%s: %s %r (an integer >= %d)' % (what, name, v, low))
+            _int(v, what, name, low)
         if bool(para) == (channels is not None):
             raise ValueError('%s: either channels=C or para=True' % what)
-        if not para and (isinstance(channels, bool) or int(channels) != channels or channels < 1):
-            raise ValueError('%s: channels %r (an integer >= 1)' % (what, channels))
+        if not para:
+            _int(channels, what, 'channels', 1)
         self.S, self.lag, self.max_new, self.para, self.shared_shape = int(slots), int(lag), int(max_new), bool(para), bool(shared_shape)
         self.C = CHANNELS if para else int(channels)
         self.width = PARA if para else self.C
         if para:
-            lam = [tuple(pair) for pair in (DEFAULT_LAM if lam is None else lam)]
-            if len(lam) != 3 or any(len(pair) != 2 for pair in lam):
-                raise ValueError('%s: lam must hold three (lam_vel, lam_acc) pairs' % what)
-            self.lam = [_lam(x, what + ': lam') for pair in lam for x in pair]
+            self.lam = _lam_pairs(DEFAULT_LAM if lam is None else lam, what)
         else:
             lam = tuple(BOX_LAM if lam is None else lam)
             if len(lam) != 2:
@@ -636,10 +618,9 @@ class StreamSmoother(object):
     # ---- host side -----------------------------------------------------------------------------------------------------------------
     def reset(self, slot):
         """Empty a slot: the next step clears it on the device before its rows are appended."""
-        if isinstance(slot, bool) or int(slot) != slot or not 0 <= slot < self.S:
-            raise ValueError('tracks.StreamSmoother.reset: slot %r of %d' % (slot, self.S))
-        self.count[int(slot)] = 0
-        self._reset[int(slot)] = 1
+        slot = _int(slot, 'tracks.StreamSmoother.reset', 'slot', 0, self.S - 1)
+        self.count[slot] = 0
+        self._reset[slot] = 1
 
     def _check(self, n_new, conf, emit):
         what, S, M = 'tracks.StreamSmoother.step', self.S, self.max_new
@@ -665,7 +646,7 @@ class StreamSmoother(object):
             raise ValueError('%s: emit %d of slot %d lies outside [%d, %d]' % (what, emit[s], s, max(T[s] - 1 - self.lag, 0), T[s] - 1))
         return n_new.astype(np.int32), conf, emit.astype(np.int32), T
 
-    def _rows(self, rows):
+    def _check_rows(self, rows):
         _rows(rows, (self.S, self.max_new, self.width), 'tracks.StreamSmoother.step: rows')
 
     def _alloc(self, device):
@@ -673,8 +654,7 @@ class StreamSmoother(object):
             if device != self.state.device:
                 raise ValueError('tracks.StreamSmoother: rows on %s, the state is on %s' % (device, self.state.device))
             return
-        if self.device is not None and torch.device(device) != torch.device(self.device.type, self.device.index if self.device.index is not None
-                                                                             else torch.cuda.current_device()):
+        if self.device is not None and _device_key(device) != _device_key(self.device):
             raise ValueError('tracks.StreamSmoother: rows on %s, the smoother was made for %s' % (device, self.device))
         nb = _lib.lib().danet_track_stream_state_bytes(self.S, self.C, self.lag, self.max_new)
         if nb == 0:
@@ -704,7 +684,7 @@ class StreamSmoother(object):
 
     def launch(self, rows):
         """The launch alone, on the commands last given: -> (out, valid).  The caller vouches for what commands() checked."""
-        self._rows(rows)
+        self._check_rows(rows)
         require_gpu(rows, 'tracks.StreamSmoother')
         self._alloc(rows.device)
         r = _f32(rows, (self.S, self.max_new, self.width), 'tracks.StreamSmoother: rows')
@@ -721,7 +701,7 @@ class StreamSmoother(object):
         return self.out, self.valid
 
     def step(self, n_new, rows, conf, emit):
-        self._rows(rows)
+        self._check_rows(rows)
         n_new, conf, emit, T = self._check(n_new, conf, emit)
         require_gpu(rows, 'tracks.StreamSmoother.step')
         self._commit(n_new, conf, emit, T, rows.device)

@@ -17,9 +17,29 @@ import torch
 
 from . import tracks as tr
 from . import constants
-from .ops import _texture_size
-from .scene import SceneDemo, person_cameras, unpack_frames
+from .ops import _int, _texture_size
+from .scene import SceneDemo, box_row, fit_columns, row_box, split_people, timed, unpack_frames
 from .smpl import from_para
+
+
+def _gap_conf(what, v):
+    """The weight of a gap row's own prediction in the smoother: finite, in [0, 1]."""
+    if not (np.isfinite(v) and 0.0 <= v <= 1.0):
+        raise ValueError('%s: gap_conf %r (in [0, 1])' % (what, v))
+
+
+def accel_summary(joints_fn, para_raw, para, ts):
+    """The four acceleration entries of a summary: joints_fn(rows) gives the SMPL joints [N,J,3] of para_raw and of para on the
+    device, track-major; 'accel_raw_tracks' / 'accel_tracks' [K] are tracks.accel of the two, 'accel_raw' / 'accel' their means
+    weighted by the tracks' interior-row counts."""
+    if ts.N:
+        a0, cnt = tr.accel(joints_fn(para_raw), ts)
+        a1, _ = tr.accel(joints_fn(para), ts)
+        a0, a1, cnt = a0.cpu().numpy(), a1.cpu().numpy(), cnt.cpu().numpy().astype(np.float64)
+    else:
+        a0 = a1 = cnt = np.zeros(ts.K)
+    w = cnt / cnt.sum() if cnt.sum() > 0 else cnt
+    return {'accel_raw': float((a0 * w).sum()), 'accel': float((a1 * w).sum()), 'accel_raw_tracks': a0, 'accel_tracks': a1}
 
 
 class VideoDemo(object):
@@ -46,8 +66,9 @@ class VideoDemo(object):
         self.smooth, self.rounds, self.shared_shape = bool(smooth), int(rounds), bool(shared_shape)
         self.max_gap, self.min_iou, self.gap_conf = int(max_gap), float(min_iou), float(gap_conf)
         self.lam, self.box_lam = tuple(tuple(p) for p in lam), tuple(box_lam)
-        if self.rounds < 1 or not (np.isfinite(self.gap_conf) and 0.0 <= self.gap_conf <= 1.0):
-            raise ValueError('VideoDemo: rounds %d (>= 1), gap_conf %r (in [0, 1])' % (self.rounds, gap_conf))
+        if self.rounds < 1:
+            raise ValueError('VideoDemo: rounds %d (>= 1)' % self.rounds)
+        _gap_conf('VideoDemo', self.gap_conf)
         self.last = {}
 
     # ---- stages ------------------------------------------------------------------------------------------------------------------
@@ -59,9 +80,7 @@ class VideoDemo(object):
         raw = np.zeros((ts.N, 3), np.float32)
         for n in range(ts.N):
             if ts.det[n] >= 0:
-                b = boxes[ts.frame[n]][ts.det[n]]
-                c = np.asarray(b[0], np.float64).reshape(2)
-                raw[n] = (c[0], c[1], np.log(float(b[1])))
+                raw[n] = box_row(boxes[ts.frame[n]][ts.det[n]])
         if ts.N == 0:
             return ts, raw, raw.copy(), [[] for _ in boxes]
         sm, _ = tr.smooth(torch.from_numpy(raw).to(self.scene.device), ts, *self.box_lam)
@@ -72,7 +91,7 @@ class VideoDemo(object):
                 b = boxes[ts.frame[n]][ts.det[n]]
                 per_frame[ts.frame[n]].append((b[0], b[1]))
             else:
-                per_frame[ts.frame[n]].append((sm[n, :2].astype(np.float64), float(np.exp(np.float64(sm[n, 2])))))
+                per_frame[ts.frame[n]].append(row_box(sm[n]))
         return ts, raw, sm, per_frame
 
     def person_keypoints(self, ts, keypoints):
@@ -129,21 +148,11 @@ class VideoDemo(object):
         conf = ts.conf.copy()
         conf[ts.det < 0] = self.gap_conf
         ts_para = ts.with_conf(conf)
-        iuv = None
-        if P and sc.dense:
-            para, iuv = sc.infer(plan, return_iuv=True)
-        else:
-            para = sc.infer(plan) if P else torch.zeros(0, 229, device=dev)
+        para, iuv = sc.infer_stage(plan)
         para_raw = para
-        fitting = sc.fitter is not None and (sc.dense or keypoints is not None)
-        fitted = None
-        kps = self.person_keypoints(ts, keypoints) if (fitting and keypoints is not None) else None
+        kps = self.person_keypoints(ts, keypoints) if (sc.fitter is not None and keypoints is not None) else None
         for _ in range(self.rounds):
-            if fitting:
-                fitted = (para, None)
-                if P:
-                    para_fit, info = sc.fit(para, plan, kps, iuv)
-                    fitted, para = (para, info), para_fit
+            fitted, para = sc.fit_stage(para, plan, kps, iuv)
             if not self.smooth or not P:
                 break
             rows, _ = tr.smooth_para(para[to_rows], ts_para, self.lam, self.shared_shape)
@@ -157,41 +166,17 @@ class VideoDemo(object):
             if P and self.shared_shape:
                 para = tr.share_shape(rows, ts_para, linked['identity'])[0][to_people]
             summary.update({'identities': int(linked['identity'].max()) + 1 if ts.K else 0, 'links': int(linked['links'].shape[0])})
-        if P:
-            a0, cnt = tr.accel(self.joints(para_raw)[to_rows], ts)
-            a1, _ = tr.accel(self.joints(para)[to_rows], ts)
-            a0, a1, cnt = a0.cpu().numpy(), a1.cpu().numpy(), cnt.cpu().numpy().astype(np.float64)
-        else:
-            a0 = a1 = cnt = np.zeros(ts.K)
-        w = cnt / cnt.sum() if cnt.sum() > 0 else cnt
-        summary.update({'accel_raw': float((a0 * w).sum()), 'accel': float((a1 * w).sum()), 'accel_raw_tracks': a0, 'accel_tracks': a1})
+        summary.update(accel_summary(lambda rows: self.joints(rows)[to_rows], para_raw, para, ts))
         verts = sc.vertices(para) if P else None
         aux = sc.render(para, plan, return_aux=True, vertices=verts)
         rendered = unpack_frames(aux[0].cpu().numpy(), plan['offsets'], plan['shapes'])
         para_h, raw_h = para.cpu().numpy(), para_raw.cpu().numpy()
         verts_h = verts.cpu().numpy() if P else np.zeros((0, 0, 3), np.float32)
-        if P:
-            k = person_cameras(para_h[:, 0:3], plan['tinv'], plan['shapes'], plan['person_frame'], sc.res, sc.focal, sc.focal_full)
-        track_p, obs_p = ts.track[ts.person_row], ts.det[ts.person_row] >= 0
-        people = []
-        for n in range(plan['N']):
-            m = plan['person_frame'] == n
-            people.append({'para': para_h[m], 'cam': para_h[m, 0:3], 'cam_t_full': k['cam_t_full'][m] if P else np.zeros((0, 3)),
-                           'focal_full': k['focal_full'][m] if P else np.zeros(0), 'center': plan['center'][m], 'scale': plan['scale'][m],
-                           'vertices': verts_h[m], 'track_id': track_p[m], 'observed': obs_p[m], 'para_raw': raw_h[m]})
-        if fitted is not None:
-            init = fitted[0].cpu().numpy()
-            if P:
-                hist, it = fitted[1]['history'].cpu().numpy(), fitted[1]['best_iter'].cpu().numpy()
-                loss = np.stack([hist[:, 0], hist[np.arange(P), it]], 1)
-            else:
-                loss, it = np.zeros((0, 2), np.float32), np.zeros(0, np.int32)
-            for n in range(plan['N']):
-                m = plan['person_frame'] == n
-                people[n].update({'para_init': init[m], 'fit_loss': loss[m], 'fit_iter': it[m]})
+        track_p = ts.track[ts.person_row]
+        columns = dict({'track_id': track_p, 'observed': ts.det[ts.person_row] >= 0, 'para_raw': raw_h}, **fit_columns(fitted, P))
         if linked is not None:
-            for n in range(plan['N']):
-                people[n]['identity'] = linked['identity'][track_p[plan['person_frame'] == n]]
+            columns['identity'] = linked['identity'][track_p]
+        people = split_people(sc.people(para_h, verts_h, plan, **columns), plan)
         self.last = {'tracks': ts, 'plan': plan, 'render_aux': aux, 'boxes_raw': boxes_raw, 'boxes': boxes_s,
                      'para_raw': raw_h[ts.row_person] if P else raw_h, 'para': para_h[ts.row_person] if P else para_h}
         if linked is not None:
@@ -228,12 +213,10 @@ class StreamDemo(object):
         if link:
             raise ValueError(NO_STREAM_LINK)
         for name, v, low in (('lag', lag, 0), ('box_lag', box_lag, 0), ('slots', slots, 1), ('max_gap', max_gap, 1)):
-            if isinstance(v, bool) or int(v) != v or v < low:
-                raise ValueError('StreamDemo: %s %r (an integer >= %d)' % (name, v, low))
+            _int(v, 'StreamDemo', name, low)
         if box_lag < max_gap:
             raise ValueError('StreamDemo: box_lag %d is below max_gap %d: a frame would be emitted before its gap rows are known' % (box_lag, max_gap))
-        if not (np.isfinite(gap_conf) and 0.0 <= gap_conf <= 1.0):
-            raise ValueError('StreamDemo: gap_conf %r (in [0, 1])' % (gap_conf,))
+        _gap_conf('StreamDemo', gap_conf)
 
     def __init__(self, model_or_engine, smpl, batch, fitter=None, smooth=True, lag=STREAM_LAG, box_lag=STREAM_LAG, slots=32, shared_shape=True,
                  max_gap=5, min_iou=0.3, gap_conf=0., lam=tr.DEFAULT_LAM, box_lam=tr.BOX_LAM, link=False, **scene_kw):
@@ -256,15 +239,7 @@ class StreamDemo(object):
         self.last = {}
 
     def _timed(self, key, f):
-        if not self.timing:
-            return f()
-        import time
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        r = f()
-        torch.cuda.synchronize()
-        self.ms[key] = self.ms.get(key, 0.0) + (time.perf_counter() - t0) * 1e3
-        return r
+        return timed(self.ms, key, f) if self.timing else f()
 
     # ---- the three stages of one step ------------------------------------------------------------------------------------------------
     def _span(self, k):
@@ -289,9 +264,7 @@ class StreamDemo(object):
                 self.para_stream.reset(s)
             s = self.slot[k]
             n = f - self.boxed.get(k, f - 1)                               # the gap rows this detection has resolved, then its own row
-            b = self.held[f]['boxes'][d]
-            c = np.asarray(b[0], np.float64).reshape(2)
-            rows[s, n - 1] = (c[0], c[1], np.log(float(b[1])))
+            rows[s, n - 1] = box_row(self.held[f]['boxes'][d])
             self.box_rows[(k, f)] = [rows[s, n - 1].copy(), None]
             conf[s, n - 1] = self.assoc.tracks[k]['rows'][-1][2]
             n_new[s], self.boxed[k] = n, f
@@ -316,21 +289,12 @@ class StreamDemo(object):
             if d >= 0 and not self.smooth:
                 boxes.append((h['boxes'][d][0], h['boxes'][d][1]))
             else:
-                b = sm_boxes[k]
-                boxes.append((b[:2].astype(np.float64), float(np.exp(np.float64(b[2])))))
+                boxes.append(row_box(sm_boxes[k]))
         plan = sc.prepare([h['frame']], [boxes])
-        P, iuv = plan['P'], None
-        if P and sc.dense:
-            para, iuv = sc.infer(plan, return_iuv=True)
-        else:
-            para = sc.infer(plan) if P else torch.zeros(0, 229, device=sc.device)
-        h.update({'plan': plan, 'order': order, 'para_raw': para, 'para_in': para, 'fitted': None})
-        if sc.fitter is not None and (sc.dense or h['kps'] is not None):
-            h['fitted'] = (para, None)
-            if P:
-                kps = None if h['kps'] is None else [[np.zeros((49, 3)) if d < 0 else h['kps'][d] for _, d in order]]
-                para_fit, info = sc.fit(para, plan, kps, iuv)
-                h['fitted'], h['para_in'] = (para, info), para_fit
+        para, iuv = sc.infer_stage(plan)
+        kps = None if h['kps'] is None else [[np.zeros((49, 3)) if d < 0 else h['kps'][d] for _, d in order]]
+        h.update({'plan': plan, 'order': order, 'para_raw': para})
+        h['fitted'], h['para_in'] = sc.fit_stage(para, plan, kps, iuv)
         del h['boxes'], h['kps']
 
     def _para_step(self, g, d):
@@ -366,21 +330,9 @@ class StreamDemo(object):
         aux = sc.render(para, plan, return_aux=True, vertices=verts)
         rendered = unpack_frames(aux[0].cpu().numpy(), plan['offsets'], plan['shapes'])[0]
         para_h, raw_h = para.cpu().numpy(), h['para_raw'].cpu().numpy()
-        people = {'para': para_h, 'cam': para_h[:, 0:3], 'center': plan['center'], 'scale': plan['scale'],
-                  'vertices': verts.cpu().numpy() if P else np.zeros((0, 0, 3), np.float32),
-                  'track_id': np.array([k for k, _ in order], np.int32), 'observed': np.array([det >= 0 for _, det in order], bool),
-                  'para_raw': raw_h, 'prefix_end': np.array([ends.get(k, d) for k, _ in order], np.int32)}
-        if P:
-            cams = person_cameras(para_h[:, 0:3], plan['tinv'], plan['shapes'], plan['person_frame'], sc.res, sc.focal, sc.focal_full)
-        people.update({'cam_t_full': cams['cam_t_full'] if P else np.zeros((0, 3)), 'focal_full': cams['focal_full'] if P else np.zeros(0)})
-        if h['fitted'] is not None:
-            init = h['fitted'][0].cpu().numpy()
-            if P:
-                hist, it = h['fitted'][1]['history'].cpu().numpy(), h['fitted'][1]['best_iter'].cpu().numpy()
-                loss = np.stack([hist[:, 0], hist[np.arange(P), it]], 1)
-            else:
-                loss, it = np.zeros((0, 2), np.float32), np.zeros(0, np.int32)
-            people.update({'para_init': init, 'fit_loss': loss, 'fit_iter': it})
+        people = sc.people(para_h, verts.cpu().numpy() if P else np.zeros((0, 0, 3), np.float32), plan,
+                           track_id=np.array([k for k, _ in order], np.int32), observed=np.array([det >= 0 for _, det in order], bool),
+                           para_raw=raw_h, prefix_end=np.array([ends.get(k, d) for k, _ in order], np.int32), **fit_columns(h['fitted'], P))
         for i, (k, _) in enumerate(order):
             self.rows[(k, d)] = (raw_h[i], para_h[i])
             if self._span(k)[1] == d:                                      # the track's last row: its slot is free again
@@ -430,15 +382,7 @@ class StreamDemo(object):
         keys = list(zip(ts.track.tolist(), ts.frame.tolist()))
         raw = np.stack([self.rows[k][0] for k in keys]) if keys else np.zeros((0, 229), np.float32)
         out = np.stack([self.rows[k][1] for k in keys]) if keys else np.zeros((0, 229), np.float32)
-        if ts.N:
-            dev = self.scene.device
-            a0, cnt = tr.accel(self.joints(torch.from_numpy(raw).to(dev)), ts)
-            a1, _ = tr.accel(self.joints(torch.from_numpy(out).to(dev)), ts)
-            a0, a1, cnt = a0.cpu().numpy(), a1.cpu().numpy(), cnt.cpu().numpy().astype(np.float64)
-        else:
-            a0 = a1 = cnt = np.zeros(ts.K)
-        w = cnt / cnt.sum() if cnt.sum() > 0 else cnt
-        summary.update({'accel_raw': float((a0 * w).sum()), 'accel': float((a1 * w).sum()), 'accel_raw_tracks': a0, 'accel_tracks': a1})
+        summary.update(accel_summary(lambda rows: self.joints(torch.from_numpy(rows).to(self.scene.device)), raw, out, ts))
         self.tracks, self.para_raw, self.para = ts, raw, out
         zero = np.zeros(3, np.float32)
         self.boxes_raw = np.stack([zero if self.box_rows[k][0] is None else self.box_rows[k][0] for k in keys]) if keys else np.zeros((0, 3), np.float32)

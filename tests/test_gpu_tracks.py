@@ -170,6 +170,29 @@ def test_refusals_launch_nothing():
     assert bool((out == 7).all()) and bool((status == 7).all())
 
 
+def test_device_tables_are_uploaded_once_per_device(monkeypatch):
+    """'cuda' and 'cuda:<current>' are one cache entry for a TrackSet, a PairSet and a RowGroups: the same tensors, and after the
+    first call nothing is uploaded."""
+    from danet_densepose2smpl_amd import tracks
+    ts = tracks.TrackSet([0, 1, 3], [0, 0, 1], [0, 0, 0], [1, 1, 0.5], 2)
+    holders = (ts, tracks.PairSet([[0, 1]], 2), tracks.RowGroups([0, 3], [2, 0, 1]))
+    named = torch.device('cuda', torch.cuda.current_device())
+    first = [h.device(torch.device('cuda')) for h in holders]
+    torch.cuda.synchronize()
+    assert torch.equal(first[0][0].cpu(), torch.tensor([0, 1, 3], dtype=torch.int32)) and first[0][1].cpu().tolist() == [1, 1, 0.5]
+    assert first[1].cpu().tolist() == [[0, 1]] and first[2][0].cpu().tolist() == [0, 3] and first[2][1].cpu().tolist() == [2, 0, 1]
+
+    def no_upload(*a, **kw):
+        raise AssertionError('a second upload')
+    monkeypatch.setattr(torch, 'from_numpy', no_upload)
+    for h, f in zip(holders, first):
+        for dev in (named, torch.device('cuda'), named):
+            again = h.device(dev)
+            assert len(h._dev) == 1
+            for x, y in zip(f if isinstance(f, tuple) else (f,), again if isinstance(again, tuple) else (again,)):
+                assert x is y and x.data_ptr() == y.data_ptr() and x.device == named
+
+
 # ------------------------------------------------------------------------------------------------------------------ smooth_para
 def para_case():
     from danet_densepose2smpl_amd import tracks

@@ -132,3 +132,28 @@ def test_oracle_recovers_the_synthetic_case(smpl_model):
     assert h.shape == (2, 101) and (r['status'] == 0).all()
     assert (h[:, -1] <= 0.05 * h[:, 0]).all()
     assert reproj(r['para_fit']) < 0.25 * reproj(init)
+
+
+def test_fill_args_writes_the_shared_fields_alike_into_both_structs():
+    """The one fill of kp_fit.py on the two argument structs: every field they share gets the same value, and the dense struct's own
+    fields come from the same call."""
+    import ctypes
+    from danet_densepose2smpl_amd import _lib, kp_fit
+    assert ctypes.sizeof(_lib.KpFitArgs) == 18 * 8 + 8 * 4 + 8 * 4 + 8 * 4 and ctypes.sizeof(_lib.DenseFitArgs) == 25 * 8 + 8 * 4 + 9 * 4 + 11 * 4
+    shared = [k for k, _ in _lib.KpFitArgs._fields_]
+    assert shared == [k for k, _ in _lib.DenseFitArgs._fields_ if k in shared] and len(shared) == 36
+    pointers = {k: 4096 + 64 * i for i, (k, t) in enumerate(_lib.KpFitArgs._fields_) if t is ctypes.c_void_p}
+    pointers['grad0'] = None
+    sizes = {'P': 3, 'NB': 10, 'S': 100, 'Sp': 128, 'NL': 21, 'NE': 9}
+    floats = {'focal': 5000., 'res': 224., 'kappa': 44.625, 'sigma': 0.1, 'w_orient': 0.005, 'w_pose': 0.0025, 'w_shape': 0.002, 'lr': 0.02}
+    stages = kp_fit.parse_stages(((3, 'cam+orient'), (5, 'all'), (2, 'shape')))
+    a = kp_fit.fill_args(_lib.KpFitArgs(), pointers, sizes, stages, floats)
+    own = {'lm_corner': 9000, 'lm_w': 9064, 'csr_off': 9128, 'csr_lm': 9192, 'csr_w': 9256, 'obs': 9320, 'gate': 9384}
+    b = kp_fit.fill_args(_lib.DenseFitArgs(), dict(pointers, **own), dict(sizes, M=259), stages,
+                         dict(floats, w_dense=0.25, sigma_dense=0.05, min_cos=0.125))
+    for k in shared:
+        va, vb = getattr(a, k), getattr(b, k)
+        assert (list(va), list(vb)) == ([3, 5, 2, 0], [3, 5, 2, 0]) or (list(va), list(vb)) == ([3, 15, 8, 0], [3, 15, 8, 0]) if k.startswith('stage_') else va == vb, k
+    assert a.para == 4096 and a.grad0 is None and (a.P, a.NB, a.S, a.Sp, a.NL, a.NE, a.nstages, a.T) == (3, 10, 100, 128, 21, 9, 3, 10)
+    assert (a.focal, a.res, a.kappa, a.lr) == (5000., 224., 44.625, np.float32(0.02)) and a.w_pose == np.float32(0.0025)
+    assert all(getattr(b, k) == v for k, v in own.items()) and b.M == 259 and (b.w_dense, b.sigma_dense, b.min_cos) == (0.25, np.float32(0.05), 0.125)

@@ -246,3 +246,41 @@ def test_eval_batches_keep_the_dataset_order_for_a_result_file(monkeypatch):
     for result_file, shuffle, want in ((None, True, True), (None, False, False), ('r.npz', True, False), ('r.npz', False, False)):
         assert list(evaluate.eval_batches([], 'dev', result_file, 4, 224, 0, shuffle)) == [({'k': 1}, 'dev', 224)]
         assert seen.pop() is want
+
+
+def test_int_rule_accepts_whole_numbers_and_names_what_it_refuses():
+    from danet_densepose2smpl_amd import ops
+    for v in (3, 3.0, np.int64(3)):
+        got = ops._int(v, 'op', 'n', 1, 5)
+        assert got == 3 and type(got) is int
+    assert ops._int(-7, 'op', 'n') == -7 and ops._int(0, 'op', 'n', 0) == 0 and ops._int(5, 'op', 'n', None, 5) == 5
+    for bad, bound in ((True, r'in 1\.\.5'), (2.5, r'in 1\.\.5'), (0, r'in 1\.\.5'), (6, r'in 1\.\.5')):
+        with pytest.raises(ValueError, match=r'^op: n %s \(an integer %s\)$' % (repr(bad).replace('.', r'\.'), bound)):
+            ops._int(bad, 'op', 'n', 1, 5)
+    with pytest.raises(ValueError, match=r'^op: n 0 \(an integer >= 1\)$'):
+        ops._int(0, 'op', 'n', 1)
+    with pytest.raises(ValueError, match=r'^op: n 6 \(an integer <= 5\)$'):
+        ops._int(6, 'op', 'n', high=5)
+    with pytest.raises(ValueError, match=r'^op: n False \(an integer\)$'):
+        ops._int(False, 'op', 'n')
+
+
+def test_per_device_cache_makes_once_and_leaves_torch_cuda_alone_for_a_cpu_device(monkeypatch):
+    from danet_densepose2smpl_amd import ops
+
+    def no_cuda():
+        raise AssertionError('torch.cuda.current_device was asked about a CPU device')
+    monkeypatch.setattr(torch.cuda, 'current_device', no_cuda)
+    cache, made = {}, []
+
+    def make():
+        made.append(object())
+        return made[-1]
+    first = ops._per_device(cache, torch.device('cpu'), make)
+    assert ops._per_device(cache, torch.device('cpu'), make) is first and len(made) == 1 and list(cache) == [('cpu', None)]
+    assert ops._device_key(torch.device('cuda', 3)) == ('cuda', 3) and ops._device_key('cpu') == ('cpu', None)
+    # an index-less CUDA device is the current one
+    monkeypatch.setattr(torch.cuda, 'current_device', lambda: 2)
+    assert ops._device_key(torch.device('cuda')) == ('cuda', 2)
+    second = ops._per_device(cache, torch.device('cuda'), make)
+    assert ops._per_device(cache, torch.device('cuda', 2), make) is second and second is not first and len(made) == 2

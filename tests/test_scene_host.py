@@ -188,3 +188,100 @@ def test_scene_symbols_declared_bound_and_exported():
         assert name in _lib.exported_symbols() and hasattr(L, name)
     assert L.danet_scene_render_ws_bytes(2, 12, 100) == 2 * 12 * 3 * 4 + 100 * 8
     assert L.danet_scene_render_ws_bytes(1, 1, 0) == 16                                  # (12 bytes rounded up to the 8-byte buffer)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the demo stages' host side
+def test_box_row_and_row_box_bit_for_bit():
+    from danet_densepose2smpl_amd import scene
+    c, s = (10.25, 7.5), 0.8
+    row = scene.box_row((np.array(c), s, 0.9))                            # a confidence behind the scale is not looked at
+    want = np.zeros(3, np.float32)
+    want[:] = (np.float64(c[0]), np.float64(c[1]), np.log(float(s)))
+    assert row.dtype == np.float32 and row.shape == (3,) and row.tobytes() == want.tobytes()
+    assert scene.box_row(([[10.25], [7.5]], np.float32(0.8))).tobytes() == np.array([10.25, 7.5, np.log(float(np.float32(0.8)))], np.float32).tobytes()
+    center, scale = scene.row_box(row)
+    assert center.dtype == np.float64 and center.tobytes() == np.array(c, np.float64).tobytes()
+    assert type(scale) is float and scale == float(np.exp(np.float64(np.float32(np.log(0.8))))) and scale != 0.8
+
+
+def test_fit_record_reads_the_loss_at_the_start_and_at_the_best_iterate():
+    from danet_densepose2smpl_amd import scene
+    h = np.array([[5.0, 4.0, 3.0], [6.0, 2.0, 1.5], [7.0, 0.5, 0.75]], np.float32)                # P = 3, T = 2
+    init = torch.arange(3 * 229, dtype=torch.float32).view(3, 229)
+    info = {'history': torch.from_numpy(h), 'best_iter': torch.tensor([0, 2, 1], dtype=torch.int32), 'status': torch.zeros(3, dtype=torch.int32)}
+    got_init, loss, it = scene.fit_record((init, info), 3)
+    assert np.array_equal(got_init, init.numpy()) and it.dtype == np.int32 and it.tolist() == [0, 2, 1]
+    assert loss.dtype == np.float32 and loss.tolist() == [[5.0, 5.0], [6.0, 1.5], [7.0, 0.5]]
+    got_init, loss, it = scene.fit_record((torch.zeros(0, 229), None), 0)
+    assert got_init.shape == (0, 229) and (loss.shape, loss.dtype) == ((0, 2), np.float32) and (it.shape, it.dtype) == ((0,), np.int32)
+    assert scene.fit_columns(None, 3) == {}
+    cols = scene.fit_columns((init, info), 3)
+    assert list(cols) == ['para_init', 'fit_loss', 'fit_iter'] and cols['fit_loss'].tolist() == loss_of(h, [0, 2, 1])
+
+
+def loss_of(h, it):
+    return [[float(h[p, 0]), float(h[p, i])] for p, i in enumerate(it)]
+
+
+def bare_demo(res=224, focal=5000., focal_full=None):
+    """A SceneDemo without a model: what the host-side stages read."""
+    from danet_densepose2smpl_amd import scene
+    demo = object.__new__(scene.SceneDemo)
+    demo.res, demo.focal, demo.focal_full, demo.fitter = res, focal, focal_full, None
+    return demo
+
+
+def test_people_builder_against_literal_dicts():
+    from danet_densepose2smpl_amd import datasets, scene
+    demo = bare_demo()
+    center, scale, pf = np.array([[40., 50.], [60., 30.], [25., 35.]]), np.array([0.4, 0.3, 0.5]), np.array([0, 0, 1], np.int32)
+    shapes = np.array([[96, 80], [64, 48]], np.int32)
+    _, tinv = datasets.crop_transforms(center, scale, np.zeros(3), 224)
+    plan = {'P': 3, 'N': 2, 'person_frame': pf, 'tinv': tinv, 'shapes': shapes, 'center': center, 'scale': scale}
+    para = np.random.default_rng(0).normal(size=(3, 229)).astype(np.float32)
+    para[:, 0] = (0.9, 0.8, 1.1)
+    verts = np.arange(3 * 4 * 3, dtype=np.float32).reshape(3, 4, 3)
+    cams = scene.person_cameras(para[:, 0:3], tinv, shapes, pf, 224, 5000., None)
+    want = [{'para': para[:2], 'cam': para[:2, :3], 'cam_t_full': cams['cam_t_full'][:2], 'focal_full': cams['focal_full'][:2],
+             'center': center[:2], 'scale': scale[:2], 'vertices': verts[:2]},
+            {'para': para[2:], 'cam': para[2:, :3], 'cam_t_full': cams['cam_t_full'][2:], 'focal_full': cams['focal_full'][2:],
+             'center': center[2:], 'scale': scale[2:], 'vertices': verts[2:]}]
+    extra = {'track_id': np.array([4, 1, 4], np.int32), 'observed': np.array([True, False, True]), 'para_raw': para + 1, 'identity': np.array([0, 1, 0], np.int32),
+             'prefix_end': np.array([5, 5, 6], np.int32)}
+    want_extra = [dict(w, **{k: v[m] for k, v in extra.items()}) for w, m in zip(want, (slice(0, 2), slice(2, 3)))]
+    assert want_extra[0]['track_id'].tolist() == [4, 1] and want_extra[1]['observed'].tolist() == [True] and want_extra[1]['para_raw'].shape == (1, 229)
+    for columns, expected in (({}, want), (extra, want_extra)):
+        one = demo.people(para, verts, plan, **columns)
+        assert one['para'] is para and one['vertices'] is verts and one['cam'].shape == (3, 3) and one['focal_full'].shape == (3,)
+        got = scene.split_people(one, plan)
+        assert len(got) == 2
+        for g, w in zip(got, expected):
+            assert sorted(g) == sorted(w)
+            for k in w:
+                assert g[k].dtype == w[k].dtype and g[k].shape == w[k].shape and g[k].tobytes() == np.ascontiguousarray(w[k]).tobytes(), k
+    # no people at all: the empty columns, with their dtypes, in every frame
+    empty = {'P': 0, 'N': 2, 'person_frame': np.zeros(0, np.int32), 'shapes': shapes, 'center': np.zeros((0, 2)), 'scale': np.zeros(0)}
+    cols = {'track_id': np.zeros(0, np.int32), 'observed': np.zeros(0, bool), 'para_raw': np.zeros((0, 229), np.float32)}
+    got = scene.split_people(demo.people(np.zeros((0, 229), np.float32), np.zeros((0, 0, 3), np.float32), empty, **cols), empty)
+    want0 = {'para': ((0, 229), np.float32), 'cam': ((0, 3), np.float32), 'cam_t_full': ((0, 3), np.float64), 'focal_full': ((0,), np.float64),
+             'center': ((0, 2), np.float64), 'scale': ((0,), np.float64), 'vertices': ((0, 0, 3), np.float32), 'track_id': ((0,), np.int32),
+             'observed': ((0,), np.bool_), 'para_raw': ((0, 229), np.float32)}
+    assert len(got) == 2
+    for g in got:
+        assert {k: (v.shape, v.dtype.type) for k, v in g.items()} == want0
+
+
+def test_infer_and_fit_stages_decide_on_the_host():
+    """P = 0 and 'nothing to fit to' never reach the network or the fitter."""
+    from danet_densepose2smpl_amd import scene
+    demo = bare_demo()
+    demo.device = torch.device('cpu')
+    para, iuv = demo.infer_stage({'P': 0})
+    assert para.shape == (0, 229) and para.dtype == torch.float32 and iuv is None
+    rows = torch.zeros(2, 229)
+    assert demo.fit_stage(rows, {'P': 2}, [[np.zeros((49, 3))] * 2], None) == (None, rows)             # no fitter
+    demo.fitter = object()                                                                           # a keypoint fitter without keypoints
+    fitted, out = demo.fit_stage(rows, {'P': 2}, None, None)
+    assert fitted is None and out is rows
+    fitted, out = demo.fit_stage(rows[:0], {'P': 0}, [[]], None)                                      # a fit of nobody: the record of one
+    assert fitted[0].shape == (0, 229) and fitted[1] is None and out.shape == (0, 229)

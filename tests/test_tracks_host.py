@@ -258,3 +258,48 @@ def test_recovery_case_improves_on_every_track_in_float64():
     assert (e1 < e0).all() and (a1 < a0).all()
     from danet_densepose2smpl_amd import tracks
     assert tuple(map(tuple, tracks.DEFAULT_LAM)) == to.DEFAULT_LAM
+
+
+# ------------------------------------------------------------------------------------------------------------------ rules stated once
+def test_trackset_check_fires_from_the_constructor_and_from_the_ops():
+    from danet_densepose2smpl_amd import tracks
+    build = lambda start=(0, 1, 3), conf=(1, 1, 1): tracks.TrackSet(start, [0, 0, 1], [0, 0, 0], conf, 2)        # noqa: E731
+    ts = build()
+    assert (ts.K, ts.N) == (2, 3)
+    ts.check('op')
+    assert tracks._tracks(ts, 3, 'op') is ts
+    ts.conf[1] = -0.5
+    with pytest.raises(ValueError, match='^op: conf must be finite and not negative'):
+        tracks._tracks(ts, 3, 'op')
+    with pytest.raises(ValueError, match='^tracks.smooth: conf must be finite'):
+        tracks.smooth(torch.zeros(3, 2), ts)
+    with pytest.raises(ValueError, match='^TrackSet: conf must be finite and not negative'):
+        build(conf=(1, -0.5, 1))
+    ts = build()
+    ts.track_start = np.array([1, 2, 3], np.int32)
+    with pytest.raises(ValueError, match='^op: track_start must ascend from 0 to 3'):
+        tracks._tracks(ts, 3, 'op')
+    with pytest.raises(ValueError, match='^tracks.accel: track_start must ascend'):
+        tracks.accel(torch.zeros(3, 24, 3), ts)
+    with pytest.raises(ValueError, match='^TrackSet: track_start must ascend from 0 to 3'):
+        build(start=(1, 2, 3))
+    with pytest.raises(ValueError, match='^op: 4 rows, the TrackSet has 3'):
+        tracks._tracks(build(), 4, 'op')
+    with pytest.raises(ValueError, match='^op: a TrackSet expected, got list'):
+        tracks._tracks([0, 3], 3, 'op')
+
+
+def test_lam_pairs():
+    from danet_densepose2smpl_amd import tracks
+    assert tracks._lam_pairs(((0, 3), [0.5, 10], (1, 2.5)), 'op') == [0.0, 3.0, 0.5, 10.0, 1.0, 2.5]
+    assert tracks._lam_pairs(tracks.DEFAULT_LAM, 'op') == [0.0, 3.0, 0.0, 10.0, 0.0, 10.0]
+    for bad in (((0, 1), (0, 1)), ((0, 1), (0, 1, 2), (0, 1)), ((0, 1), (0, 1), (0, 1), (0, 1)), ((0, 1), (0,), (0, 1))):
+        with pytest.raises(ValueError, match=r'^op: lam must hold three \(lam_vel, lam_acc\) pairs'):
+            tracks._lam_pairs(bad, 'op')
+    for v in (-1.0, np.nan, np.inf):
+        with pytest.raises(ValueError, match='^op: lam: .*finite and not negative'):
+            tracks._lam_pairs(((0, 1), (0, v), (0, 1)), 'op')
+    # the two callers share it
+    with pytest.raises(ValueError, match='^tracks.StreamSmoother: lam must hold three'):
+        tracks.StreamSmoother(2, 3, para=True, lam=((0, 1), (0, 1)))
+    assert tracks.StreamSmoother(2, 3, para=True).lam == tracks._lam_pairs(tracks.DEFAULT_LAM, 'op')

@@ -23,6 +23,7 @@ its <name>_scene.png is written as it comes out; the JSON line adds delay_frames
 person detector here.  Last line: one JSON object with the counts and the
 milliseconds per frame of every stage (host clock around a device synchronisation, one run: the clip is processed once)."""
 import argparse
+import functools
 import json
 import os
 import sys
@@ -119,7 +120,7 @@ def main(argv=None):
         raise SystemExit('--fit_iters %d --rounds %d' % (a.fit_iters, a.rounds))
 
     import torch
-    from danet_densepose2smpl_amd import checkpoint, video
+    from danet_densepose2smpl_amd import checkpoint, scene, video
     from danet_densepose2smpl_amd.config import cfg_from_file
     from danet_densepose2smpl_amd.danet import DaNet
     from danet_densepose2smpl_amd.trainer import default_options
@@ -176,15 +177,7 @@ def main(argv=None):
 
     # the stages once by hand for the clock; the results come from the one call below
     ms = {}
-
-    def timed(key, f):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        r = f()
-        torch.cuda.synchronize()
-        ms[key] = ms.get(key, 0.0) + (time.perf_counter() - t0) * 1e3
-        return r
-
+    timed = functools.partial(scene.timed, ms)
     from danet_densepose2smpl_amd import tracks as tr
     ts = timed('associate', lambda: tr.associate(boxes, demo.max_gap, demo.min_iou))
     _, _, _, per_frame = timed('boxes', lambda: demo.track_boxes(boxes))
