@@ -188,6 +188,11 @@ _SIGNATURES = {
     'danet_track_affinity': (c_i, [c_f, c_f, c_i, c_i, c_f, ctypes.POINTER(ctypes.c_int32), ctypes.c_long, c_f, c_f]),
     'danet_track_group_mean': (c_i, [c_f, c_f, c_f, ctypes.POINTER(ctypes.c_int32), c_f, ctypes.POINTER(ctypes.c_int32), c_i, ctypes.c_long,
                                      c_i, c_i, c_f, c_f, c_i, c_f]),
+    'danet_track_desc_state_bytes': (c_sz, [c_i, c_i]),
+    'danet_track_desc_step': (c_i, [c_f, c_sz, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, ctypes.POINTER(ctypes.c_int32),
+                                    c_f, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_fl, c_fl, c_fl, c_f]),
+    'danet_track_desc_read': (c_i, [c_f, c_sz, c_i, c_i, c_f, ctypes.POINTER(ctypes.c_int32), c_i, c_i, c_f, c_f, c_f, c_f, c_f]),
+    'danet_track_desc_shape': (c_i, [c_f, c_sz, c_i, c_i, c_f, c_f, ctypes.POINTER(ctypes.c_int32), c_f, c_f, c_i, c_f]),
 }
 
 # fp32 instantiations (csrc/norm_act_f32.hip, stn.hip): same arguments, fp32 NHWC activations

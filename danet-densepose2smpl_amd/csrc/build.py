@@ -63,6 +63,7 @@ UNITS = {
     'track_ops.hip': ['-ffp-contract=off'],   # the track rule's factor and substitutions are restated operation by operation in the tests
     'track_stream.hip': ['-ffp-contract=off'],  # the same operations as track_ops.hip, one row at a time
     'track_link.hip': ['-ffp-contract=off'],  # the identity rule's sums are restated in the tests and rounded once
+    'track_reid.hip': ['-ffp-contract=off'],  # texture_ops.hip's per-view body and track_link.hip's sums restated: the same bits
 }
 INCLUDES = {'norm_act_f32.hip': ['norm_act.hip']}
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-I' + os.path.join(ROOT, 'include'), '-I' + HERE,

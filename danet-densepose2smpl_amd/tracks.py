@@ -22,7 +22,13 @@ Identities (DESIGN.md 4b'-link "the identity rule"; csrc/track_link.hip): the tr
     pairs = candidates(ts, max_absence)                                     # host: b begins 1 .. max_absence frames after a ends
     dist = affinity(shape, atlas, pairs)                                    # [C,4] = (d_shape, d_app, overlap, S), one launch
     res = link(ts, dist, pairs)                                             # host, float64: identity [K], links [L,2], link_cost [L]
-    para_i, mean, status = share_shape(para_s, ts, res['identity'])        # one shape per identity, one launch"""
+    para_i, mean, status = share_shape(para_s, ts, res['identity'])        # one shape per identity, one launch
+
+Identities while streaming (DESIGN.md 4b'-reid "the causal identity rule"; csrc/track_reid.hip): the same descriptors as running sums:
+
+    sd = StreamDescriptor(slots, gallery, texture_atlas)                    # per slot the unnormalised texel sums and the shape sums
+    sd.step(images, vertices, cam, depth, para, conf, slot, observed)       # a frame's people, one launch; read() = descriptors() so far
+    lk = OnlineLinker(gallery)                                              # host, float64: a track is decided once, at its first drawn frame"""
 import ctypes
 
 import numpy as np
@@ -706,3 +712,301 @@ class StreamSmoother(object):
         require_gpu(rows, 'tracks.StreamSmoother.step')
         self._commit(n_new, conf, emit, T, rows.device)
         return self.launch(rows)
+
+
+# ---- identities while streaming (DESIGN.md 4b'-reid "the causal identity rule"; csrc/track_reid.hip) ---------------------------------
+# (max_absence, sigma_s, sigma_a, min_overlap, no_app): DESIGN.md 4b'-reid, the table at heads of lag + 1 = 9 rows on the recovery case
+REID_DEFAULTS = {'max_absence': 150, 'sigma_s': 0.4, 'sigma_a': 0.2, 'min_overlap': 0.1, 'no_app': 0.5}
+REID_GALLERY = 64
+
+
+def _host_ints(a, n, what, low, high, unique=False):
+    """A host array of n whole numbers in [low, high] (bools count as 0 / 1) -> int32; `unique`: no value >= 0 twice."""
+    a = np.asarray(a)
+    if a.dtype == bool:
+        a = a.astype(np.int32)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('%s must be [%d] integers, got %s %s' % (what, n, a.dtype, a.shape))
+    if ((a < low) | (a > high)).any():
+        raise ValueError('%s must lie in %d..%d, got %s' % (what, low, high, a.tolist()))
+    if unique:
+        used = a[a >= 0]
+        if np.unique(used).size != used.size:
+            raise ValueError('%s names a value twice: %s' % (what, a.tolist()))
+    return np.ascontiguousarray(a, np.int32)
+
+
+class StreamDescriptor(object):
+    """The descriptor of the identity rule (descriptors(): a track's weighted mean shape and the texture fused over its observed rows)
+    kept as running sums for `slots` tracks, one frame at a time (csrc/track_reid.hip; DESIGN.md 4b'-reid).  `texture`: the
+    texture.TextureAtlas whose topology, chart size T and focal length the skin uses; `gallery`: the rows of the descriptor table kept
+    for finished tracks.
+
+        sd = StreamDescriptor(slots, gallery, texture)
+        sd.step(images, vertices, cam, depth, para, conf, slot, observed)     # one launch: a frame's people go into their slots
+        shape, atlas, status = sd.read(slots, rows)                           # one launch: descriptors -> rows of the table
+        sd.apply_shape(rows, slot, carry, use)                                # one launch: the identity's shape into emitted rows
+        sd.reset(slot)                                                        # the next step empties the slot first
+
+    step: images [P,3,H,H] in [0,1], vertices [P,NV,3], cam [P,3], depth [P,H,H] (depth_planes() makes it as TextureAtlas.unwrap does),
+    para [P,229] and conf [P] are GPU tensors (the caller vouches that conf is finite and not negative); slot [P] (-1: the entry is
+    empty; no slot twice) and observed [P] (0: a gap row, which adds to the shape with its conf and never to the skin; its image, mesh and
+    depth are never read) are HOST arrays.  After any number of steps read() gives, bit for bit, TextureAtlas.unwrap over the observed
+    rows the slot has taken in their order, and descriptors()' shape over all its rows.
+
+    The table has gallery + slots rows: desc_shape [R,10], desc_atlas [R,24,T,T,4], status [R] (1: no weight yet) and desc_sums [R,11]
+    float64, the shape sums (sum c betas, sum c) as they are.  head_row(s) = gallery + s is the row of the track in slot s, so that
+    affinity() compares finished tracks with live ones through an ordinary PairSet over R.  apply_shape: rows [P,229], a contiguous
+    fp32 GPU tensor changed IN PLACE: where use[p] != 0, slot[p] >= 0 and carry_c + sum_c > 0 the betas become
+    (carry_y + sum_y) / (carry_c + sum_c), carry [P,11] float64 on the GPU; other rows keep their bits.
+
+    Everything is checked before anything is launched and a refused call changes nothing.  Under torch.cuda.graph: capture
+    launch(...) on static tensors, then per frame refill them, call commands(slot, observed) and replay."""
+
+    def __init__(self, slots, gallery, texture, device=None):
+        from .texture import TextureAtlas
+        what = 'tracks.StreamDescriptor'
+        self.S, self.G = _int(slots, what, 'slots', 1, 4096), _int(gallery, what, 'gallery', 0, 1 << 16)
+        if not isinstance(texture, TextureAtlas):
+            raise ValueError('%s: a texture.TextureAtlas expected, got %s' % (what, type(texture).__name__))
+        self.tex, self.T, self.R = texture, texture.size, self.G + self.S
+        if PARTS * self.T * self.T >= 1 << 24:
+            raise ValueError('%s: chart size %d is too large' % (what, self.T))
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != 'cuda':
+            raise RuntimeError(_lib.GPU_ONLY % (what, self.device))
+        self._reset = np.zeros(self.S, np.int32)
+        self.state, self._cmd = None, {}
+
+    def head_row(self, slot):
+        return self.G + int(slot)
+
+    def reset(self, slot):
+        """Empty a slot: the next step clears it on the device before its row is added."""
+        self._reset[_int(slot, 'tracks.StreamDescriptor.reset', 'slot', 0, self.S - 1)] = 1
+
+    # ---- host side -----------------------------------------------------------------------------------------------------------------
+    def _check(self, slot, observed):
+        what = 'tracks.StreamDescriptor.step'
+        if np.asarray(slot).ndim != 1:
+            raise ValueError('%s: slot must be [P] integers, got shape %s' % (what, np.asarray(slot).shape))
+        P = np.asarray(slot).shape[0]
+        return _host_ints(slot, P, what + ': slot', -1, self.S - 1, unique=True), _host_ints(observed, P, what + ': observed', 0, 1)
+
+    def _check_rows(self, P, images, vertices, cam, depth, para, conf, what='tracks.StreamDescriptor.step'):
+        _rows(images, (P, 3, None, None), what + ': images')
+        H = images.shape[2]
+        if images.shape[3] != H or H < 1 or H > 4096:
+            raise ValueError('%s: images %s, expected square [P,3,H,H]' % (what, tuple(images.shape)))
+        _rows(vertices, (P, None, 3), what + ': vertices')
+        if vertices.shape[1] < self.tex.num_verts:
+            raise ValueError('%s: vertices %s (the topology names %d mesh vertices)' % (what, tuple(vertices.shape), self.tex.num_verts))
+        _rows(cam, (P, 3), what + ': cam')
+        _rows(depth, (P, H, H), what + ': depth')
+        _rows(para, (P, PARA), what + ': para')
+        _rows(conf, (P,), what + ': conf')
+        for name, t in (('images', images), ('vertices', vertices), ('cam', cam), ('depth', depth), ('para', para), ('conf', conf)):
+            require_gpu(t, '%s: %s' % (what, name))
+        if len(set(t.device for t in (images, vertices, cam, depth, para, conf))) != 1:
+            raise ValueError('%s: the tensors must be on one device' % what)
+
+    def _pick_device(self, device):
+        if device is None:
+            device = self.state.device if self.state is not None else (self.device or torch.device('cuda', torch.cuda.current_device()))
+        return torch.device(device)
+
+    def _alloc(self, device):
+        if self.state is not None:
+            if device != self.state.device:
+                raise ValueError('tracks.StreamDescriptor: tensors on %s, the state is on %s' % (device, self.state.device))
+            return
+        if self.device is not None and _device_key(device) != _device_key(self.device):
+            raise ValueError('tracks.StreamDescriptor: tensors on %s, the descriptor was made for %s' % (device, self.device))
+        nb = _lib.lib().danet_track_desc_state_bytes(self.S, self.T)
+        if nb == 0:
+            raise ValueError('tracks.StreamDescriptor: sizes out of range (slots %d, chart size %d)' % (self.S, self.T))
+        self.state_bytes = nb
+        self.state = torch.zeros(nb // 8, device=device, dtype=torch.int64)
+        self.d_reset = torch.zeros(self.S, device=device, dtype=torch.int32)
+        self.desc_shape = torch.zeros(self.R, 10, device=device, dtype=torch.float32)
+        self.desc_atlas = torch.zeros(self.R, PARTS, self.T, self.T, 4, device=device, dtype=torch.float32)
+        self.desc_sums = torch.zeros(self.R, 11, device=device, dtype=torch.float64)
+        self.status = torch.ones(self.R, device=device, dtype=torch.int32)
+
+    def _commit(self, slot, observed, device):
+        """The checked commands go into static tensors (one pair per chunk size P); the pending resets go with them."""
+        P = slot.size
+        if P == 0:
+            return                                                        # (nothing is launched: the resets wait for the next step)
+        self._alloc(device)
+        if P not in self._cmd:
+            self._cmd[P] = torch.zeros(2, P, device=device, dtype=torch.int32)
+        self._cmd[P].copy_(torch.from_numpy(np.stack([slot, observed])))
+        self.d_reset.copy_(torch.from_numpy(self._reset))
+        self._host_slot = slot
+        self._reset[:] = 0
+
+    # ---- the ops ---------------------------------------------------------------------------------------------------------------------
+    def depth_planes(self, vertices, cam, H):
+        """The rasteriser's depth plane [P,H,H] of the meshes, as TextureAtlas.unwrap makes it."""
+        from . import ops
+        v = _f32(vertices, (None, None, 3), 'tracks.StreamDescriptor.depth_planes: vertices')
+        c = _f32(cam, (v.shape[0], 3), 'tracks.StreamDescriptor.depth_planes: cam')
+        d = self.tex._dev(v.device)
+        return ops.iuv_raster(v, c, d['vert_mapping'], d['faces'], d['tex'], self.tex.focal_length, int(H), int(H), return_aux=True)[2]
+
+    def commands(self, slot, observed, device=None):
+        """The checked half of step: slot and observed go into the descriptor's static tensors; no launch."""
+        slot, observed = self._check(slot, observed)
+        self._commit(slot, observed, self._pick_device(device))
+
+    def launch(self, images, vertices, cam, depth, para, conf, depth_tol=0.02, min_cos=0.1):
+        """The launch alone, on the commands last given.  The caller vouches for what commands() checked."""
+        P = images.shape[0] if torch.is_tensor(images) and images.dim() else -1
+        self._check_rows(P, images, vertices, cam, depth, para, conf)
+        if P == 0:
+            return
+        if P not in self._cmd or self._host_slot.size != P:
+            raise ValueError('tracks.StreamDescriptor.launch: no commands for a chunk of %d' % P)
+        self._alloc(images.device)
+        what = 'tracks.StreamDescriptor'
+        H = images.shape[2]
+        img, v, c = _f32(images, (P, 3, H, H), what), _f32(vertices, (P, None, 3), what), _f32(cam, (P, 3), what)
+        dp, pa, cf = _f32(depth, (P, H, H), what), _f32(para, (P, PARA), what), _f32(conf, (P,), what)
+        d = self.tex._dev(img.device)
+        cmd = self._cmd[P]
+        check(_lib.lib().danet_track_desc_step(ptr(self.state), self.state_bytes, self.S, self.T, ptr(img), ptr(v), ptr(c), ptr(dp), P, v.shape[1], H,
+                                               ptr(pa), ptr(cf), ptr(cmd[0]), _host_i32(self._host_slot), ptr(cmd[1]), ptr(self.d_reset),
+                                               ptr(d['vert_mapping']), d['vert_mapping'].numel(), ptr(d['faces']), d['faces'].shape[0],
+                                               ptr(d['map_face']), ptr(d['map_bary']), self.tex.focal_length, float(depth_tol), float(min_cos),
+                                               stream()), 'danet_track_desc_step')
+
+    def step(self, images, vertices, cam, depth, para, conf, slot, observed, depth_tol=0.02, min_cos=0.1):
+        slot, observed = self._check(slot, observed)
+        self._check_rows(slot.size, images, vertices, cam, depth, para, conf)
+        self._commit(slot, observed, images.device)
+        self.launch(images, vertices, cam, depth, para, conf, depth_tol, min_cos)
+
+    def read(self, slots, rows, device=None):
+        """The descriptors of `slots` (host integers in [0, S)) go into the rows `rows` (host integers in [0, R), none twice) of the
+        table -> (desc_shape, desc_atlas, status): the descriptor's own tensors.  One launch; no pair launches nothing."""
+        what = 'tracks.StreamDescriptor.read'
+        if np.asarray(slots).ndim != 1:
+            raise ValueError('%s: slots must be [n] integers' % what)
+        n = np.asarray(slots).shape[0]
+        s, r = _host_ints(slots, n, what + ': slots', 0, self.S - 1), _host_ints(rows, n, what + ': rows', 0, self.R - 1, unique=True)
+        self._alloc(self._pick_device(device))
+        if n:
+            pairs = np.ascontiguousarray(np.stack([s, r], 1), np.int32)
+            check(_lib.lib().danet_track_desc_read(ptr(self.state), self.state_bytes, self.S, self.T, ptr(torch.from_numpy(pairs).to(self.state.device)),
+                                                   _host_i32(pairs), n, self.R, ptr(self.desc_shape), ptr(self.desc_atlas), ptr(self.desc_sums),
+                                                   ptr(self.status), stream()), 'danet_track_desc_read')
+        return self.desc_shape, self.desc_atlas, self.status
+
+    def apply_shape(self, rows, slot, carry, use):
+        what = 'tracks.StreamDescriptor.apply_shape'
+        P = _rows(rows, (None, PARA), what + ': rows').shape[0]
+        s, u = _host_ints(slot, P, what + ': slot', -1, self.S - 1), _host_ints(use, P, what + ': use', 0, 1)
+        if not torch.is_tensor(carry) or carry.dtype != torch.float64 or tuple(carry.shape) != (P, 11):
+            raise ValueError('%s: carry must be a float64 [%d,11] tensor' % (what, P))
+        r = _typed(rows, torch.float32, (P, PARA), what + ': rows')
+        cy = _typed(carry, torch.float64, (P, 11), what + ': carry')
+        if cy.device != r.device:
+            raise ValueError('%s: rows and carry must be on one device' % what)
+        self._alloc(r.device)
+        if P:
+            cmd = torch.from_numpy(np.stack([s, u])).to(r.device)
+            check(_lib.lib().danet_track_desc_shape(ptr(self.state), self.state_bytes, self.S, self.T, ptr(r), ptr(cmd[0]), _host_i32(s), ptr(cy),
+                                                    ptr(cmd[1]), P, stream()), 'danet_track_desc_shape')
+        return rows
+
+
+class OnlineLinker(object):
+    """The decisions of the causal identity rule (DESIGN.md 4b'-reid), host, float64, deterministic.  A finished track waits in one of
+    `gallery` rows until it gets a successor or has been away for more than max_absence frames; a track is decided once, at its
+    first drawn frame, and never again.
+
+        cand = lk.candidates(d, newborn)                 # [(track a, its gallery row, track b)], ascending in (a, b); evicts first
+        out = lk.decide(d, newborn, cand, dist)          # dist [C,4]: affinity's rows of cand -> {b: (identity, a's gallery row or None)}
+        row = lk.retire(track, last)                     # the track's last row has been drawn: -> its gallery row
+
+    The cost and the greedy acceptance are link()'s.  A linked b takes a's identity, and a's row is free again after decide: the caller
+    copies what it keeps per row (the chain totals) before it retires a track.  identity {track: number}, links and link_cost in
+    acceptance order."""
+
+    def __init__(self, gallery=REID_GALLERY, max_absence=None, sigma_s=None, sigma_a=None, min_overlap=None, no_app=None):
+        what = 'tracks.OnlineLinker'
+        given = {'max_absence': max_absence, 'sigma_s': sigma_s, 'sigma_a': sigma_a, 'min_overlap': min_overlap, 'no_app': no_app}
+        self.thr = link_arguments(what, **{k: REID_DEFAULTS[k] if v is None else v for k, v in given.items()})
+        self.G = _int(gallery, what, 'gallery', 1, 1 << 16)
+        self.entries = {}                                                # gallery row -> {'track', 'last', 'identity'}
+        self.free = list(range(self.G))
+        self.identity, self.links, self.link_cost = {}, [], []
+        self.n_identities = 0
+
+    def evict(self, d):
+        """Entries with d - last > max_absence leave: no later frame can bring them a successor."""
+        for row in [r for r, e in self.entries.items() if d - e['last'] > self.thr['max_absence']]:
+            del self.entries[row]
+            self.free.append(row)
+        self.free.sort()
+
+    def candidates(self, d, newborn):
+        self.evict(d)
+        rows = sorted((e['track'], r) for r, e in self.entries.items() if 1 <= d - e['last'] <= self.thr['max_absence'])
+        return [(a, r, int(b)) for a, r in rows for b in sorted(newborn)]
+
+    def decide(self, d, newborn, cand, dist):
+        what = 'tracks.OnlineLinker.decide'
+        dist = dist.detach().cpu().numpy() if torch.is_tensor(dist) else np.asarray(dist)
+        if dist.shape != (len(cand), 4) or (len(cand) and not np.issubdtype(dist.dtype, np.floating)):
+            raise ValueError('%s: dist must be [%d,4] floating point, got %s %s' % (what, len(cand), dist.dtype, dist.shape))
+        if any(b in self.identity for b in newborn):
+            raise ValueError('%s: a track is decided once' % what)
+        dist = dist.astype(np.float64).reshape(-1, 4)
+        if not np.isfinite(dist[:, :3]).all():
+            raise ValueError('%s: a non-finite distance' % what)
+        thr, keep = self.thr, []
+        for c, (a, row, b) in enumerate(cand):
+            app = dist[c, 1] / thr['sigma_a'] ** 2 if dist[c, 2] >= thr['min_overlap'] else thr['no_app']
+            cost = dist[c, 0] / thr['sigma_s'] ** 2 + app
+            if cost <= 1.0:
+                keep.append((cost, a, b, row))
+        keep.sort()
+        succ, pred = set(), {}
+        for cost, a, b, row in keep:
+            if a in succ or b in pred:
+                continue
+            succ.add(a)
+            pred[b] = (a, row)
+            self.links.append((a, b))
+            self.link_cost.append(cost)
+        out = {}
+        for b in sorted(newborn):
+            if b in pred:
+                a, row = pred[b]
+                self.identity[b] = self.entries[row]['identity']
+                del self.entries[row]
+                self.free.append(row)
+                out[b] = (self.identity[b], row)
+            else:
+                self.identity[b] = self.n_identities
+                self.n_identities += 1
+                out[b] = (self.identity[b], None)
+        self.free.sort()
+        return out
+
+    def retire(self, track, last):
+        if track not in self.identity:
+            raise ValueError('tracks.OnlineLinker.retire: track %d has not been decided' % track)
+        if not self.free:
+            raise RuntimeError('tracks.OnlineLinker: %d finished tracks wait in the gallery and frame %d retires another; the gallery holds %d'
+                               % (len(self.entries), last, self.G))
+        row = self.free.pop(0)
+        self.entries[row] = {'track': int(track), 'last': int(last), 'identity': self.identity[track]}
+        return row
+
+    def arrays(self, K):
+        """-> (identity [K] int32, links [L,2] int32, link_cost [L] float64), link()'s dtypes."""
+        return (np.array([self.identity[k] for k in range(K)], np.int32), np.array(self.links, np.int32).reshape(-1, 2),
+                np.array(self.link_cost, np.float64))

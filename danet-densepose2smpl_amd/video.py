@@ -10,7 +10,9 @@ row of every track is on the device at once.  StreamDemo (below) is the same pip
 exact fixed-lag smoother (tracks.StreamSmoother, DESIGN.md 4b'-stream "the stream rule") and a bounded number of frames held, for
 clips that do not fit on the device and for live sources.  With link=True a VideoDemo also links the tracks of one person into an
 identity by body shape and fused texture (tracks.descriptors / affinity / link / share_shape, DESIGN.md 4b'-link "the identity rule").
-Not here: video decoding, a person detector, identities while streaming, motion prediction, several ranks.
+With reid=True a StreamDemo decides a track's identity at its first drawn frame from the descriptors kept as running sums
+(tracks.StreamDescriptor / OnlineLinker, DESIGN.md 4b'-reid "the causal identity rule").
+Not here: video decoding, a person detector, revising an identity later, motion prediction, several ranks.
 There is no CPU path."""
 import numpy as np
 import torch
@@ -186,7 +188,8 @@ class VideoDemo(object):
 
 STREAM_LAG = 8          # the default lag and box_lag of StreamDemo: DESIGN.md 4b'-stream, the lag table
 NO_STREAM_LINK = ('StreamDemo: link=True is not available while streaming: the descriptor of the identity rule (DESIGN.md 4b\'-link) needs a '
-                  'finished track, its mean shape and the texture fused over all its observed rows; link the clip with VideoDemo')
+                  'finished track, its mean shape and the texture fused over all its observed rows; link the clip with VideoDemo.  '
+                  'While streaming, reid=True decides identities causally (DESIGN.md 4b\'-reid)')
 
 
 class StreamDemo(object):
@@ -206,7 +209,15 @@ class StreamDemo(object):
     from its first box until its last row is drawn.  There is no `rounds`: the fit / smooth alternation needs whole tracks and stays
     VideoDemo's.  With smooth = False observed rows keep their own box and row, and gap rows get the box stream's box.  Wraps a
     scene.SceneDemo and does not change it; there is no CPU path.  link=True raises ValueError: identities need finished tracks and
-    are VideoDemo's."""
+    are VideoDemo's.
+    reid=True (DESIGN.md 4b'-reid "the causal identity rule"): every track's descriptor is kept as running sums
+    (tracks.StreamDescriptor, one launch per processed frame); a track's identity is decided once, at its first drawn frame, from its
+    rows so far against the finished tracks of the last `max_absence` frames (tracks.OnlineLinker; at most `gallery` of them wait), and
+    never revised; with shared_shape the rows of a linked track are drawn with the shape of its identity so far.  The people dicts gain
+    'identity' [k], the summary 'identities' and 'links', and after flush() the object holds identity [K], links [L,2] and link_cost
+    [L].  max_absence, sigma_s, sigma_a, min_overlap, no_app default to tracks.REID_DEFAULTS.  Without it every output is what it
+    was.  With `record` set, `recorded` keeps device copies of the rows, heads, final descriptors and distances the decisions were
+    taken on (the tests compare them with the float64 oracle); it grows with the stream."""
 
     @staticmethod
     def check_arguments(lag, box_lag, slots, max_gap, gap_conf, link=False):
@@ -218,9 +229,27 @@ class StreamDemo(object):
             raise ValueError('StreamDemo: box_lag %d is below max_gap %d: a frame would be emitted before its gap rows are known' % (box_lag, max_gap))
         _gap_conf('StreamDemo', gap_conf)
 
+    @staticmethod
+    def check_reid_arguments(max_absence=None, id_texture_size=tr.ID_TEXTURE_SIZE, gallery=tr.REID_GALLERY, sigma_s=None, sigma_a=None,
+                             min_overlap=None, no_app=None):
+        """-> (the thresholds of the causal identity rule as a dict, None taking tracks.REID_DEFAULTS; the chart size; the gallery)."""
+        given = {'max_absence': max_absence, 'sigma_s': sigma_s, 'sigma_a': sigma_a, 'min_overlap': min_overlap, 'no_app': no_app}
+        thr = tr.link_arguments('StreamDemo', **{k: tr.REID_DEFAULTS[k] if v is None else v for k, v in given.items()})
+        return thr, _texture_size(id_texture_size), _int(gallery, 'StreamDemo', 'gallery', 1, 1 << 16)
+
     def __init__(self, model_or_engine, smpl, batch, fitter=None, smooth=True, lag=STREAM_LAG, box_lag=STREAM_LAG, slots=32, shared_shape=True,
-                 max_gap=5, min_iou=0.3, gap_conf=0., lam=tr.DEFAULT_LAM, box_lam=tr.BOX_LAM, link=False, **scene_kw):
+                 max_gap=5, min_iou=0.3, gap_conf=0., lam=tr.DEFAULT_LAM, box_lam=tr.BOX_LAM, link=False, reid=False, max_absence=None,
+                 id_texture_size=tr.ID_TEXTURE_SIZE, gallery=tr.REID_GALLERY, sigma_s=None, sigma_a=None, min_overlap=None, no_app=None,
+                 **scene_kw):
         self.check_arguments(lag, box_lag, slots, max_gap, gap_conf, link)
+        self.reid_kw, self.id_texture_size, self.gallery = self.check_reid_arguments(max_absence, id_texture_size, gallery, sigma_s, sigma_a,
+                                                                                    min_overlap, no_app)
+        self.reid, self.shared_shape = bool(reid), bool(shared_shape)
+        self.linker = tr.OnlineLinker(self.gallery, **self.reid_kw) if self.reid else None
+        self.desc = None                     # the tracks.StreamDescriptor, made at the first use
+        self._carry = self._tot = None       # the chain totals on the device (_tables)
+        self.carried = set()                 # the tracks that have a predecessor
+        self.record, self.recorded = False, {'rows': {}, 'head': {}, 'final': {}}       # record: keep device copies of what was decided on
         self.assoc = tr.OnlineAssociator(max_gap, min_iou, what='StreamDemo')
         self.smooth, self.lag, self.box_lag, self.slots = bool(smooth), int(lag), int(box_lag), int(slots)
         self.max_gap, self.gap_conf = int(max_gap), float(gap_conf)
@@ -262,6 +291,8 @@ class StreamDemo(object):
                 s = self.slot[k] = self.free.pop(0)
                 self.box_stream.reset(s)
                 self.para_stream.reset(s)
+                if self.reid:
+                    self._descriptor().reset(s)
             s = self.slot[k]
             n = f - self.boxed.get(k, f - 1)                               # the gap rows this detection has resolved, then its own row
             rows[s, n - 1] = box_row(self.held[f]['boxes'][d])
@@ -297,6 +328,79 @@ class StreamDemo(object):
         h['fitted'], h['para_in'] = sc.fit_stage(para, plan, kps, iuv)
         del h['boxes'], h['kps']
 
+    def _row_conf(self, k, det, g):
+        """The weight of track k's row of frame g: its detection's confidence, gap_conf for a gap row."""
+        return self.gap_conf if det < 0 else [r[2] for r in self.assoc.tracks[k]['rows'] if r[0] == g][0]
+
+    # ---- identities (DESIGN.md 4b'-reid) -----------------------------------------------------------------------------------------------
+    def _descriptor(self):
+        if self.desc is None:
+            from .texture import TextureAtlas
+            tex = TextureAtlas(size=self.id_texture_size, focal_length=self.scene.focal)
+            self.desc = tr.StreamDescriptor(self.slots, self.gallery, tex)
+        return self.desc
+
+    def _describe(self, g):
+        """The rows of frame g that enter the para stream go into their tracks' descriptors: the de-normalised crops as
+        VideoDemo.link_tracks makes them, the meshes and cameras of those rows, the rasteriser's depth plane.  One launch."""
+        sc, h, desc = self.scene, self.held[g], self._descriptor()
+        order = h['order']
+        if not order:
+            return
+        mean, std = (torch.tensor(c, device=sc.device).view(1, 3, 1, 1) for c in (constants.IMG_NORM_MEAN, constants.IMG_NORM_STD))
+        crops = (sc.crops(h['plan']) * std + mean).clamp(0.0, 1.0)
+        rows = h['para_in'].contiguous()
+        verts, cam = sc.vertices(rows), rows[:, 0:3].contiguous()
+        conf = np.array([self._row_conf(k, det, g) for k, det in order], np.float32)
+        observed = np.array([det >= 0 for _, det in order], np.int32)
+        desc.step(crops, verts, cam, desc.depth_planes(verts, cam, crops.shape[2]), rows, torch.from_numpy(conf).to(sc.device),
+                  np.array([self.slot[k] for k, _ in order], np.int32), observed)
+        if self.record:
+            for i, (k, _) in enumerate(order):
+                self.recorded['rows'][(k, g)] = (rows[i].clone(), float(conf[i]), bool(observed[i]))
+
+    def _tables(self):
+        """(carry [slots,11], tot [gallery,11]) float64 on the device: the chain totals (sum c betas, sum c) a slot's track inherits and
+        those of the finished tracks in the gallery."""
+        if self._carry is None:
+            self._carry = torch.zeros(self.slots, 11, device=self.scene.device, dtype=torch.float64)
+            self._tot = torch.zeros(self.gallery, 11, device=self.scene.device, dtype=torch.float64)
+        return self._carry, self._tot
+
+    def _identify(self, d):
+        """The decisions of drawn frame d: its newborn tracks against the gallery (the one host read: dist [C,4], where there are both),
+        then the tracks whose last row this is go into the gallery.  -> {track: identity} of the frame's people."""
+        lk, desc, order = self.linker, self._descriptor(), self.held[d]['order']
+        carry, tot = self._tables()
+        newborn = sorted(k for k, _ in order if self._span(k)[0] == d)
+        cand = lk.candidates(d, newborn)
+        if newborn:
+            dist = np.zeros((0, 4))
+            if cand:
+                desc.read([self.slot[b] for b in newborn], [desc.head_row(self.slot[b]) for b in newborn], device=self.scene.device)
+                pairs = tr.PairSet([(row, desc.head_row(self.slot[b])) for _, row, b in cand], desc.R)
+                dist = tr.affinity(desc.desc_shape, desc.desc_atlas, pairs).cpu().numpy()
+                if self.record:
+                    for n, (a, _, b) in enumerate(cand):
+                        self.recorded.setdefault('dist', {})[(a, b)] = dist[n].copy()
+                    for b in newborn:
+                        r = desc.head_row(self.slot[b])
+                        self.recorded['head'][b] = (desc.desc_shape[r].clone(), desc.desc_atlas[r].clone())
+            for b, (_, row) in lk.decide(d, newborn, cand, dist).items():
+                if row is None:
+                    carry[self.slot[b]].zero_()
+                else:
+                    carry[self.slot[b]].copy_(tot[row])
+                    self.carried.add(b)
+        for k in sorted(k for k, _ in order if self._span(k)[1] == d):        # before _draw frees the slot and a reset can empty it
+            row = lk.retire(k, d)
+            desc.read([self.slot[k]], [row], device=self.scene.device)
+            tot[row].copy_(carry[self.slot[k]] + desc.desc_sums[row])
+            if self.record:
+                self.recorded['final'][k] = (desc.desc_shape[row].clone(), desc.desc_atlas[row].clone(), desc.desc_sums[row].clone(),
+                                             carry[self.slot[k]].clone())
+        return {k: lk.identity[k] for k, _ in order}
+
     def _para_step(self, g, d):
         """The rows of frame g (or None) go into the para stream; the rows of frame d (or None) come out: ({track: [229] on the
         device}, {track: the prefix's last frame})."""
@@ -309,7 +413,7 @@ class StreamDemo(object):
             rows[slots, 0] = h['para_in']
             for s, (k, det) in zip(slots, h['order']):
                 n_new[s] = 1
-                conf[s, 0] = self.gap_conf if det < 0 else [r[2] for r in self.assoc.tracks[k]['rows'] if r[0] == g][0]
+                conf[s, 0] = self._row_conf(k, det, g)
         cover = [k for k, _ in self.held[d]['order']] if d is not None else []
         for k in cover:
             emit[self.slot[k]] = d - self._span(k)[0]
@@ -320,19 +424,28 @@ class StreamDemo(object):
         seen = self.assoc.n_frames - 1 if g is None else g                               # the last frame whose rows have gone in
         return {k: out[self.slot[k]] for k in cover}, {k: min(seen, self._span(k)[1]) for k in cover}
 
-    def _draw(self, d, sm_rows, ends):
+    def _draw(self, d, sm_rows, ends, ident=None):
         sc, h = self.scene, self.held.pop(d)
         plan, order, P = h['plan'], h['order'], h['plan']['P']
         para = h['para_in']
         if self.smooth and P:
             para = torch.stack([sm_rows[k] for k, _ in order])
+        columns = {}
+        if ident is not None:
+            columns['identity'] = np.array([ident[k] for k, _ in order], np.int32)
+            use = np.array([k in self.carried for k, _ in order], np.int32)
+            if self.shared_shape and use.any():                               # one shape per identity: the chain so far
+                para = para.contiguous() if self.smooth else para.clone(memory_format=torch.contiguous_format)     # (para_in stays as it is)
+                slots = np.array([self.slot[k] for k, _ in order], np.int32)
+                self.desc.apply_shape(para, slots, self._carry[torch.from_numpy(slots.astype(np.int64)).to(para.device)], use)
         verts = sc.vertices(para) if P else None
         aux = sc.render(para, plan, return_aux=True, vertices=verts)
         rendered = unpack_frames(aux[0].cpu().numpy(), plan['offsets'], plan['shapes'])[0]
         para_h, raw_h = para.cpu().numpy(), h['para_raw'].cpu().numpy()
         people = sc.people(para_h, verts.cpu().numpy() if P else np.zeros((0, 0, 3), np.float32), plan,
                            track_id=np.array([k for k, _ in order], np.int32), observed=np.array([det >= 0 for _, det in order], bool),
-                           para_raw=raw_h, prefix_end=np.array([ends.get(k, d) for k, _ in order], np.int32), **fit_columns(h['fitted'], P))
+                           para_raw=raw_h, prefix_end=np.array([ends.get(k, d) for k, _ in order], np.int32), **columns,
+                           **fit_columns(h['fitted'], P))
         for i, (k, _) in enumerate(order):
             self.rows[(k, d)] = (raw_h[i], para_h[i])
             if self._span(k)[1] == d:                                      # the track's last row: its slot is free again
@@ -349,9 +462,12 @@ class StreamDemo(object):
         sm_boxes = self._timed('boxes', lambda: self._box_step(matches, g))
         if g is not None:
             self._timed('infer', lambda: self._process(g, sm_boxes))
+            if self.reid:
+                self._timed('reid', lambda: self._describe(g))
         sm_rows, ends = self._timed('smooth', lambda: self._para_step(g, d))
+        ident = self._timed('reid', lambda: self._identify(d)) if self.reid and d is not None else None
         self.time += 1
-        return [self._timed('render', lambda: self._draw(d, sm_rows, ends))] if d is not None else []
+        return [self._timed('render', lambda: self._draw(d, sm_rows, ends, ident))] if d is not None else []
 
     # ---- the interface -------------------------------------------------------------------------------------------------------------------
     def push(self, frame, boxes, keypoints=None):
@@ -384,6 +500,9 @@ class StreamDemo(object):
         out = np.stack([self.rows[k][1] for k in keys]) if keys else np.zeros((0, 229), np.float32)
         summary.update(accel_summary(lambda rows: self.joints(torch.from_numpy(rows).to(self.scene.device)), raw, out, ts))
         self.tracks, self.para_raw, self.para = ts, raw, out
+        if self.reid:
+            self.identity, self.links, self.link_cost = self.linker.arrays(ts.K)
+            summary.update({'identities': self.linker.n_identities, 'links': len(self.linker.links)})
         zero = np.zeros(3, np.float32)
         self.boxes_raw = np.stack([zero if self.box_rows[k][0] is None else self.box_rows[k][0] for k in keys]) if keys else np.zeros((0, 3), np.float32)
         self.boxes = np.stack([self.box_rows[k][1] for k in keys]) if keys else np.zeros((0, 3), np.float32)

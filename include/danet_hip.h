@@ -1105,6 +1105,42 @@ int danet_track_group_mean(float* rows, const float* conf, const int32_t* group_
                            const int32_t* group_rows, const int32_t* group_rows_host, int G, long N, int col0, int ncol,
                            float* mean, int32_t* status, int write_back, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Streaming identities (csrc/track_reid.hip; tracks.StreamDescriptor is the caller; DESIGN.md 4b'-reid "the causal identity rule"):
+ * the descriptor of the identity rule kept as running sums for S slots, one frame at a time.  T is the side of a chart.
+ *
+ * state: danet_track_desc_state_bytes(S, T) bytes (0 for bad sizes), 16-byte aligned, owned by the caller and passed to every call;
+ *   all zero = every slot empty.  Per slot acc [24,T,T,4] f32, the unnormalised sums (sum cs r, sum cs g, sum cs b, sum cs) of every
+ *   texel, and sum_y [10], sum_c in double.
+ * danet_track_desc_step -- one frame's people, a chunk of fixed shape P.  images [P,3,H,H] f32 in [0,1], verts [P,NV,3], cam [P,3],
+ *   depth [P,H,H] and the four tables are danet_texture_unwrap's; para [P,229] and conf [P] f32 (the caller vouches: finite, not
+ *   negative); slot [P] i32, -1 = the entry is empty, with its HOST copy, which is checked (in [-1, S), no slot twice) before the
+ *   launch; observed [P] i32, 0 = a gap row, which adds to the shape sums with its conf and never to the skin, and whose image, mesh
+ *   and depth are never read; reset [S] i32, not 0: the slot is emptied first, whether a person of the frame holds it or not.
+ *   Per (person, texel) one 16-byte load, the per-view body of texture_unwrap_kernel operation for operation, one 16-byte store:
+ *   after n observed rows acc holds that kernel's four sums after the same n views.  The shape: sum_c += (double)c, sum_y +=
+ *   (double)c * (double)beta where c > 0; a row with c = 0 is never read.  One launch; P = 0 returns without one.
+ * danet_track_desc_read -- pairs [n,2] i32 = (slot, destination row in [0, R)) with their HOST copy (checked; no row twice):
+ *   desc_shape [R,10] f32 = (float)(sum_y / sum_c), or 0 with status [R] i32 = 1 where sum_c = 0; desc_atlas [R,24,T,T,4] f32
+ *   (16-byte aligned) = (sr / sw, sg / sw, sb / sw, sw) where sw > 0, else four zeros: danet_texture_unwrap's last line;
+ *   desc_sums [R,11] f64 = (sum_y, sum_c) as they are.  Other rows keep their contents.  One launch; n = 0 returns without one.
+ * danet_track_desc_shape -- rows [P,229] f32 (in / out), slot [P] i32 with its HOST copy (in [-1, S)), carry [P,11] f64 = (carry_y,
+ *   carry_c), use [P] i32: where use != 0, slot >= 0 and carry_c + sum_c > 0, columns 3 .. 12 become
+ *   (float)((carry_y + sum_y) / (carry_c + sum_c)); every other row keeps its bits.  One launch.
+ * No atomics, no LDS, no grid barrier, nothing read back on the host, no device allocation: all three capture under a graph for
+ * fixed shapes; two runs give the same bits, and a slot's result does not depend on the others of the launch.
+ */
+size_t danet_track_desc_state_bytes(int S, int T);
+int danet_track_desc_step(void* state, size_t state_bytes, int S, int T, const float* images, const float* verts, const float* cam,
+                          const float* depth, int P, int NV, int H, const float* para, const float* conf, const int32_t* slot,
+                          const int32_t* slot_host, const int32_t* observed, const int32_t* reset, const int32_t* vert_mapping,
+                          int NDV, const int32_t* faces, int F, const int32_t* map_face, const float* map_bary, float focal,
+                          float depth_tol, float min_cos, void* stream);
+int danet_track_desc_read(const void* state, size_t state_bytes, int S, int T, const int32_t* pairs, const int32_t* pairs_host,
+                          int n, int R, float* desc_shape, float* desc_atlas, double* desc_sums, int32_t* status, void* stream);
+int danet_track_desc_shape(const void* state, size_t state_bytes, int S, int T, float* rows, const int32_t* slot,
+                           const int32_t* slot_host, const double* carry, const int32_t* use, int P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,11 +7,15 @@ the SMPL joints per track before and after).
 
   python tools/demo_video.py --frames_dir DIR --out_dir DIR --boxes FILE.json [--keypoints_dir DIR] [--fit | --fit_iuv] [--rounds R]
                              [--no_smooth] [--engine] [--batch N] [--checkpoint FILE] [--cfg YAML] [--fit_iters N]
-                             [--stream [--lag L] [--box_lag L] [--slots S]] [--link [--max_absence F] [--id_texture_size T]]
+                             [--stream [--lag L] [--box_lag L] [--slots S] [--reid [--max_absence F] [--id_texture_size T] [--gallery G]]]
+                             [--link [--max_absence F] [--id_texture_size T]]
 
 With --link (DESIGN.md 4b'-link "the identity rule") the tracks of one person are linked into an identity by body shape and fused
 texture, every identity gets one shape, tracks.npz gains identity [K], links [L,2] and link_cost [L], and the JSON line the two counts
-and the stage's milliseconds per frame; it needs finished tracks, so --stream --link is refused.
+and the stage's milliseconds per frame; it needs finished tracks, so --stream --link is refused.  With --stream --reid (DESIGN.md
+4b'-reid "the causal identity rule") a track's identity is decided at its first drawn frame against the finished tracks of the last
+--max_absence frames, of which at most --gallery wait, and never revised; tracks.npz gains the same three arrays and the JSON line
+`reid`, the two counts and the stage's milliseconds per frame.  --reid without --stream is refused: a whole clip has --link.
 
 Frames are taken in name order; the input conventions are those of tools/demo_scene.py: .npy arrays always (uint8 [H,W,3]), .jpg / .png
 if PIL is installed; --boxes maps a frame's file name to a list of [x, y, w, h] or [x, y, w, h, confidence]; --keypoints_dir holds
@@ -68,14 +72,19 @@ def stream(a, demo, names, box_table, with_kp):
     written += write(rest)
     torch.cuda.synchronize()
     demo.ms['total'] = (time.perf_counter() - t0) * 1e3
+    extra = {'identity': demo.identity, 'links': demo.links, 'link_cost': demo.link_cost} if demo.reid else {}
     np.savez(os.path.join(a.out_dir, 'tracks.npz'), para_raw=demo.para_raw, para=demo.para, boxes_raw=demo.boxes_raw, boxes=demo.boxes,
-             accel_raw=summary['accel_raw_tracks'], accel=summary['accel_tracks'], **demo.tracks.arrays())
+             accel_raw=summary['accel_raw_tracks'], accel=summary['accel_tracks'], **extra, **demo.tracks.arrays())
     print('Video demo results (%d frames, %d tracks, %d rows) have been saved in %s.' % (written, summary['tracks'], summary['rows'], a.out_dir))
-    return {'tool': 'demo_video', 'stream': True, 'frames': written, 'tracks': summary['tracks'], 'rows': summary['rows'],
-            'gap_rows': summary['gap_rows'], 'accel_raw': summary['accel_raw'], 'accel': summary['accel'], 'batch': a.batch,
-            'engine': bool(a.engine), 'smooth': not a.no_smooth, 'fit': 'keypoints' if a.fit else ('iuv' if a.fit_iuv else None),
-            'lag': demo.lag, 'box_lag': demo.box_lag, 'max_gap': demo.max_gap, 'delay_frames': demo.lag + demo.box_lag,
-            'max_frames_held': demo.max_held, 'ms_per_frame': {k: round(v / max(written, 1), 4) for k, v in demo.ms.items()}}
+    res = {'tool': 'demo_video', 'stream': True, 'frames': written, 'tracks': summary['tracks'], 'rows': summary['rows'],
+           'gap_rows': summary['gap_rows'], 'accel_raw': summary['accel_raw'], 'accel': summary['accel'], 'batch': a.batch,
+           'engine': bool(a.engine), 'smooth': not a.no_smooth, 'fit': 'keypoints' if a.fit else ('iuv' if a.fit_iuv else None),
+           'lag': demo.lag, 'box_lag': demo.box_lag, 'max_gap': demo.max_gap, 'delay_frames': demo.lag + demo.box_lag,
+           'max_frames_held': demo.max_held, 'ms_per_frame': {k: round(v / max(written, 1), 4) for k, v in demo.ms.items()}}
+    if demo.reid:
+        res.update({'reid': True, 'identities': summary['identities'], 'links': summary['links'], 'max_absence': demo.reid_kw['max_absence'],
+                    'id_texture_size': demo.id_texture_size, 'gallery': demo.gallery})
+    return res
 
 
 def main(argv=None):
@@ -98,14 +107,20 @@ def main(argv=None):
     ap.add_argument('--box_lag', type=int, default=8, help='--stream: the same for the boxes; tracks bridge gaps of up to min(5, box_lag) frames')
     ap.add_argument('--slots', type=int, default=32, help='--stream: tracks alive at once')
     ap.add_argument('--link', action='store_true', help='link the tracks of one person into an identity by shape and fused texture')
-    ap.add_argument('--max_absence', type=int, default=None, help='--link: frames a person may be away and keep their identity')
-    ap.add_argument('--id_texture_size', type=int, default=None, help='--link: texels per side of a chart of the skin descriptor')
+    ap.add_argument('--reid', action='store_true', help='--stream: decide every track\'s identity at its first drawn frame, causally')
+    ap.add_argument('--max_absence', type=int, default=None, help='--link / --reid: frames a person may be away and keep their identity')
+    ap.add_argument('--id_texture_size', type=int, default=None, help='--link / --reid: texels per side of a chart of the skin descriptor')
+    ap.add_argument('--gallery', type=int, default=None, help='--reid: finished tracks that may wait for a successor at once')
     a = ap.parse_args(argv)
+    if a.reid and not a.stream:
+        raise SystemExit('--reid belongs to --stream: it decides identities while the clip is still coming in; a whole clip has --link')
+    if a.gallery is not None and not a.reid:
+        raise SystemExit('--gallery belongs to --reid')
     if a.stream and a.link:
         from danet_densepose2smpl_amd.video import NO_STREAM_LINK
         raise SystemExit('--stream --link: ' + NO_STREAM_LINK)
-    if not a.link and (a.max_absence is not None or a.id_texture_size is not None):
-        raise SystemExit('--max_absence and --id_texture_size belong to --link')
+    if not (a.link or a.reid) and (a.max_absence is not None or a.id_texture_size is not None):
+        raise SystemExit('--max_absence and --id_texture_size belong to --link or --reid')
     if a.stream and a.rounds != 1:
         raise SystemExit('--stream has no --rounds: the fit / smooth alternation needs whole tracks')
     if a.fit and a.fit_iuv:
@@ -142,8 +157,17 @@ def main(argv=None):
     smpl = model.iuv2smpl.smpl
     engine = model.inference_engine(a.batch) if a.engine else None
     if a.stream:
-        demo = video.StreamDemo(engine if engine is not None else model, smpl, a.batch, smooth=not a.no_smooth, lag=a.lag, box_lag=a.box_lag,
-                                slots=a.slots, max_gap=min(5, a.box_lag) if a.box_lag >= 1 else 5)
+        reid_kw = {}
+        if a.reid:
+            reid_kw = {'reid': True, 'max_absence': a.max_absence}
+            reid_kw.update({k: v for k, v in (('id_texture_size', a.id_texture_size), ('gallery', a.gallery)) if v is not None})
+        try:
+            demo = video.StreamDemo(engine if engine is not None else model, smpl, a.batch, smooth=not a.no_smooth, lag=a.lag, box_lag=a.box_lag,
+                                    slots=a.slots, max_gap=min(5, a.box_lag) if a.box_lag >= 1 else 5, **reid_kw)
+        except ValueError as e:
+            if not a.reid:
+                raise
+            raise SystemExit('--reid: %s' % e)
     else:
         link_kw = {}
         if a.link:
