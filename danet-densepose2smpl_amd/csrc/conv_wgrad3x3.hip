@@ -15,10 +15,11 @@
 // Any pixel <-> k assignment is valid as long as dY and X use the same one, so the tap shift is
 // just an address offset into the halo tile.
 // Partial sums of the blocks that share a dW tile go to a [split] workspace with plain coalesced
-// stores and are reduced (deterministically) by a second kernel that also writes the torch layout.
+// stores and are summed (in a fixed order) by the finish kernel of wgrad_finish.h, which also writes the torch layout.
 #include <cstdlib>
 #include "common.h"
 #include "conv_common.h"
+#include "wgrad_finish.h"
 
 namespace {
 
@@ -285,57 +286,6 @@ __global__ __launch_bounds__(256) void conv_wgrad3x3_multi_kernel(Wg3Multi mp)
     wgrad3x3_body<CT, NI, ST, SM>(p, bx, rest % mp.nyb[i], rest / mp.nyb[i]);
 }
 
-struct Red3Multi { const float* part[NPM]; float* dw[NPM]; int G[NPM], Cout_g[NPM], Cin_g[NPM], msplit[NPM]; long start[NPM + 1]; int n; float beta; };
-
-__global__ __launch_bounds__(256) void wgrad3x3_reduce_multi_kernel(Red3Multi rp)
-{
-    const long gidx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (gidx >= rp.start[rp.n]) return;
-    int i = 0;
-    while (i + 1 < rp.n && gidx >= rp.start[i + 1]) ++i;
-    const long idx = gidx - rp.start[i], total = rp.start[i + 1] - rp.start[i];
-    const float* part = rp.part[i];
-    float s = 0.f;
-    int sp = 0;
-    for (; sp + 4 <= rp.msplit[i]; sp += 4) {
-        const float v0 = part[(size_t)sp * total + idx], v1 = part[(size_t)(sp + 1) * total + idx];
-        const float v2 = part[(size_t)(sp + 2) * total + idx], v3 = part[(size_t)(sp + 3) * total + idx];
-        s += (v0 + v1) + (v2 + v3);
-    }
-    for (; sp < rp.msplit[i]; ++sp) s += part[(size_t)sp * total + idx];
-    const int Cin_g = rp.Cin_g[i], Cout_g = rp.Cout_g[i];
-    const int cin = (int)(idx % Cin_g);
-    long rest = idx / Cin_g;
-    const int cout = (int)(rest % Cout_g); rest /= Cout_g;
-    const int tap = (int)(rest % 9), g = (int)(rest / 9);
-    const size_t o = (((size_t)(g * Cout_g + cout)) * Cin_g + cin) * 9 + tap;
-    float* dw = rp.dw[i];
-    dw[o] = rp.beta != 0.f ? dw[o] * rp.beta + s : s;
-}
-
-// dW[Cout][Cin_g][3][3] = beta*dW + sum_s part[s][g][tap][cout][cin]   (fixed order -> deterministic)
-__global__ __launch_bounds__(256) void wgrad3x3_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
-                                                               int G, int Cout_g, int Cin_g, int msplit, float beta)
-{
-    const long total = (long)G * Cout_g * Cin_g * 9;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;          // index in part layout: [g][tap][cout][cin]
-    if (idx >= total) return;
-    float s = 0.f;
-    int sp = 0;
-    for (; sp + 4 <= msplit; sp += 4) {
-        const float v0 = part[(size_t)sp * total + idx], v1 = part[(size_t)(sp + 1) * total + idx];
-        const float v2 = part[(size_t)(sp + 2) * total + idx], v3 = part[(size_t)(sp + 3) * total + idx];
-        s += (v0 + v1) + (v2 + v3);
-    }
-    for (; sp < msplit; ++sp) s += part[(size_t)sp * total + idx];
-    const int cin = (int)(idx % Cin_g);
-    long rest = idx / Cin_g;
-    const int cout = (int)(rest % Cout_g); rest /= Cout_g;
-    const int tap = (int)(rest % 9), g = (int)(rest / 9);
-    const size_t o = (((size_t)(g * Cout_g + cout)) * Cin_g + cin) * 9 + tap;
-    dw[o] = beta != 0.f ? dw[o] * beta + s : s;
-}
-
 template <int CT, int NI, int ST>
 int launch3(const Wg3P& p, hipStream_t st) {
     const int nco = (p.Cout_g + CT * 16 - 1) / (CT * 16), nci = (p.Cin_g + NI * 16 - 1) / (NI * 16);
@@ -440,11 +390,9 @@ extern "C" int danet_conv_wgrad3x3(const void* x, const void* dy, float* dw, flo
         DANET_CHECK_LAUNCH("conv_wgrad3x3_kernel");
     }
     if (phase == 1) return DANET_OK;
-    const long total = (long)Cout * p.Cin_g * 9;
-    hipLaunchKernelGGL(wgrad3x3_reduce_kernel, dim3(danet::cdiv(total, 256)), dim3(256), 0, st, ws, dw, groups, p.Cout_g,
-                       p.Cin_g, p.msplit, beta);
-    DANET_CHECK_LAUNCH("wgrad3x3_reduce_kernel");
-    return DANET_OK;
+    FinishQueue fq(beta);
+    if (int e = fq.add(ws, dw, groups, p.Cout_g * p.Cin_g, p.msplit, 9)) return e;
+    return fq.flush<9>(st);
 }
 
 
@@ -492,6 +440,10 @@ static void plan_multi(const Wg3Job* jobs, const int* idx, int cnt, int ct, int 
 static int multi_foreach_launch(const Wg3Job* jobs, int n, float* ws, size_t ws_floats, float beta, hipStream_t st, size_t* need_out)
 {
     size_t used = 0;
+    // the finish launches trail the MFMA launches: a launch group's partials wait here until FIN_BUDGET_BYTES of them are pending (or
+    // FIN_NP problems), so that the small groups (stride 2, channel-padded, small-map) share a finish launch instead of running a few
+    // dozen workgroups each with the chip empty; the workspace holds every group's partials at once
+    FinishQueue fq(beta);
     bool done[4096];
     if (n > 4096) return danet::fail(DANET_ERR_ARG, "conv_wgrad3x3_multi: too many jobs (%d)", n);
     for (int i = 0; i < n; ++i) done[i] = false;
@@ -513,10 +465,10 @@ static int multi_foreach_launch(const Wg3Job* jobs, int n, float* ws, size_t ws_
         }
         int msplit[NPM];
         plan_multi(jobs, idx, cnt, ct, ni, msplit);
-        Wg3Multi mp; Red3Multi rp;
+        Wg3Multi mp;
         static const bool xcd_order = getenv("DANET_WGRAD3_XCD") && atoi(getenv("DANET_WGRAD3_XCD")) != 0;      // A-B knob, OFF: measured 117.7 vs 110.1 us per 12-problem flush, step 26.26 vs 26.21 ms
-        mp.n = cnt; rp.n = cnt; rp.beta = beta; mp.xcd = xcd_order ? 1 : 0;
-        mp.start[0] = 0; rp.start[0] = 0;
+        mp.n = cnt; mp.xcd = xcd_order ? 1 : 0;
+        mp.start[0] = 0;
         for (int k = 0; k < cnt; ++k) {
             const Wg3Job& j = jobs[idx[k]];
             Wg3P& p = mp.p[k];
@@ -536,8 +488,6 @@ static int multi_foreach_launch(const Wg3Job* jobs, int n, float* ws, size_t ws_
             mp.nyb[k] = nyb;
             mp.start[k + 1] = mp.start[k] + msplit[k] * nyb * j.groups;
             const long total = (long)j.Cout * p.Cin_g * 9;
-            rp.part[k] = p.part; rp.dw[k] = j.dw; rp.G[k] = j.groups; rp.Cout_g[k] = p.Cout_g; rp.Cin_g[k] = p.Cin_g; rp.msplit[k] = msplit[k];
-            rp.start[k + 1] = rp.start[k] + (direct ? 0 : total);          // (nothing to reduce for a direct job)
             if (!direct || !ws) used += (size_t)msplit[k] * total;          // (the sizing pass does not know beta: room for the partial form)
             if (ws && !(p.x_bytes < (1L << 31) && p.dy_bytes < (1L << 31)))
                 return danet::fail(DANET_ERR_ARG, "conv_wgrad3x3_multi: tensors of 2 GB or more are not supported");
@@ -564,11 +514,15 @@ static int multi_foreach_launch(const Wg3Job* jobs, int n, float* ws, size_t ws_
         return danet::fail(DANET_ERR_ARG, "conv_wgrad3x3_multi: no kernel for tiles %dx%d", ct, ni);
 #undef W3M
         DANET_CHECK_LAUNCH("conv_wgrad3x3_multi_kernel");
-        if (rp.start[cnt] > 0) {
-            hipLaunchKernelGGL(wgrad3x3_reduce_multi_kernel, dim3((unsigned)danet::cdiv(rp.start[cnt], 256)), dim3(256), 0, st, rp);
-            DANET_CHECK_LAUNCH("wgrad3x3_reduce_multi_kernel");
+        for (int k = 0; k < cnt; ++k) {
+            const Wg3P& p = mp.p[k];
+            if (p.direct) continue;                              // (nothing to sum for a direct job)
+            if (int e = fq.add(p.part, jobs[idx[k]].dw, p.groups, p.Cout_g * p.Cin_g, p.msplit, 9)) return e;
+            if (fq.full()) if (int e = fq.flush<9>(st)) return e;
         }
+        if (fq.over_budget()) if (int e = fq.flush<9>(st)) return e;
     }
+    if (ws) if (int e = fq.flush<9>(st)) return e;
     if (need_out) *need_out = used;
     return DANET_OK;
 }

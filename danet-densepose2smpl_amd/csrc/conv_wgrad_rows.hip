@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "conv_common.h"
+#include "wgrad_finish.h"
 
 namespace {
 
@@ -186,29 +187,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_kernel(WgRP p)
     }
 }
 
-// dW[Cout][Cin_g][R][S] = beta*dW + sum_s part[s][g][tap][cout][cin]   (fixed order -> deterministic)
-__global__ __launch_bounds__(256) void wgrad_rows_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
-                                                                 int G, int Cout_g, int Cin_g, int taps, int msplit, float beta)
-{
-    const long total = (long)G * Cout_g * Cin_g * taps;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;          // index in part layout: [g][tap][cout][cin]
-    if (idx >= total) return;
-    float s = 0.f;
-    int sp = 0;
-    for (; sp + 4 <= msplit; sp += 4) {
-        const float v0 = part[(size_t)sp * total + idx], v1 = part[(size_t)(sp + 1) * total + idx];
-        const float v2 = part[(size_t)(sp + 2) * total + idx], v3 = part[(size_t)(sp + 3) * total + idx];
-        s += (v0 + v1) + (v2 + v3);
-    }
-    for (; sp < msplit; ++sp) s += part[(size_t)sp * total + idx];
-    const int cin = (int)(idx % Cin_g);
-    long rest = idx / Cin_g;
-    const int cout = (int)(rest % Cout_g); rest /= Cout_g;
-    const int tap = (int)(rest % taps), g = (int)(rest / taps);
-    const size_t o = (((size_t)(g * Cout_g + cout)) * Cin_g + cin) * taps + tap;
-    dw[o] = beta != 0.f ? dw[o] * beta + s : s;
-}
-
 int plan_rows(int B, int OH, int OW, int Cin, int Cout, int R, int groups) {
     const int Cout_g = Cout / groups, Cin_g = Cin / groups;
     const long other = (long)R * ((Cout_g + 63) / 64) * ((Cin_g + 63) / 64) * groups;
@@ -264,9 +242,7 @@ extern "C" int danet_conv_wgrad_rows(const void* x, const void* dy, float* dw, f
     const size_t lds = 2 * (size_t)(TH * TW * (CT * 32 + 16) + TH * (ST * (TW - 1) + SS) * (NI * 32 + 16));
     hipLaunchKernelGGL((conv_wgrad_rows_kernel<CT, NI, SS, ST>), dim3(p.msplit, R * nco * nci, groups), dim3(256), lds, st, p);
     DANET_CHECK_LAUNCH("conv_wgrad_rows_kernel");
-    const long total = (long)Cout * p.Cin_g * R * S;
-    hipLaunchKernelGGL(wgrad_rows_reduce_kernel, dim3(danet::cdiv(total, 256)), dim3(256), 0, st, ws, dw, groups, p.Cout_g,
-                       p.Cin_g, R * S, p.msplit, beta);
-    DANET_CHECK_LAUNCH("wgrad_rows_reduce_kernel");
-    return DANET_OK;
+    FinishQueue fq(beta);
+    if (int e = fq.add(ws, dw, groups, p.Cout_g * p.Cin_g, p.msplit, R * S)) return e;
+    return fq.flush<49>(st);
 }

@@ -541,6 +541,8 @@ size_t danet_conv_wgrad3x3_multi_ws_floats(const void* jobs, int n);
 size_t danet_conv_wgrad_multi_ws_floats(const void* jobs, int n);
 size_t danet_conv_wgrad_multi_ws_zero_from(const void* jobs, int n);
 int danet_conv_wgrad_multi(const void* jobs, int n, float* ws, size_t ws_floats, float beta, void* stream);
+/* danet_conv_wgrad3x3(_multi) and danet_conv_wgrad_rows: ws must be 16-byte aligned (the split-K finish reads it with 16-byte loads;
+ * DANET_ERR_ARG otherwise); dw needs 4-byte alignment only. */
 int danet_conv_wgrad3x3_multi(const void* jobs, int n, float* ws, size_t ws_floats, float beta, void* stream);
 int danet_conv_wgrad3x3_kernel_id(int B, int H, int W, int Cin, int Cout, int groups, int stride);   /* CT*10 + NI */
 int danet_conv_wgrad3x3(const void* x, const void* dy, float* dw, float* ws, size_t ws_floats,
