@@ -56,14 +56,15 @@ UNITS = {
     'input_ops.hip': ['-ffp-contract=off'],   # the crop's arithmetic is restated operation by operation in the tests
     'train_vis.hip': ['-ffp-contract=off'],   # x * std + mean and the min / max normalisation are the written operations
     'scene_ops.hip': ['-ffp-contract=off'],   # the scene rule's arithmetic is restated operation by operation in the tests
-    'texture_ops.hip': ['-ffp-contract=off'],  # the texture rule likewise; its map is bit-equal to a float64 restatement
+    # the texture rule likewise; its map is bit-equal to a float64 restatement; the per-view body is shared (unwrap_view.h) with track_reid.hip
+    'texture_ops.hip': ['-ffp-contract=off'],
     'kp_fit.hip': [],
     'dense_fit.hip': [],
     'fit_loop.hip': ['-ffp-contract=off'],    # the pose undo is input_ops.hip's (pose_aug.h): the same bits in both units
     'track_ops.hip': ['-ffp-contract=off'],   # the track rule's factor and substitutions are restated operation by operation in the tests
-    'track_stream.hip': ['-ffp-contract=off'],  # the same operations as track_ops.hip, one row at a time
+    'track_stream.hip': ['-ffp-contract=off'],  # the factor row and substitution steps shared (track_rule.h) with track_ops.hip, one row at a time
     'track_link.hip': ['-ffp-contract=off'],  # the identity rule's sums are restated in the tests and rounded once
-    'track_reid.hip': ['-ffp-contract=off'],  # texture_ops.hip's per-view body and track_link.hip's sums restated: the same bits
+    'track_reid.hip': ['-ffp-contract=off'],  # the per-view body shared (unwrap_view.h) with texture_ops.hip, track_link.hip's sums: the same bits
 }
 INCLUDES = {'norm_act_f32.hip': ['norm_act.hip']}
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-I' + os.path.join(ROOT, 'include'), '-I' + HERE,

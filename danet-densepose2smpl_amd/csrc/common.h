@@ -22,6 +22,17 @@ inline int fail(int code, const char* fmt, ...) {
 #define DANET_CHECK_ARG(cond, ...) \
     do { if (!(cond)) return ::danet::fail(DANET_ERR_ARG, __VA_ARGS__); } while (0)
 
+// An offsets table on the host (the row starts of a CSR: tracks, groups, a person's views): off[0] = 0, off[n] = total, and no entry
+// below the one before it.  `op` and `name` open the message ("track_smooth: track_start ...").
+inline int check_offsets(const char* op, const char* name, const int32_t* off, int n, long total) {
+    DANET_CHECK_ARG(off[0] == 0 && off[n] == total, "%s: %s must run from 0 to N=%ld, got %d..%d", op, name, total, off[0], off[n]);
+    for (int i = 0; i < n; ++i) DANET_CHECK_ARG(off[i + 1] >= off[i], "%s: %s descends at entry %d", op, name, i);
+    return DANET_OK;
+}
+
+#define DANET_CHECK_OFFSETS(op, name, off, n, total) \
+    do { const int e_ = ::danet::check_offsets(op, name, off, n, total); if (e_ != DANET_OK) return e_; } while (0)
+
 // first statement of every enqueueing entry point: drop any sticky error left by an earlier,
 // unrelated HIP call so that DANET_CHECK_LAUNCH reports only our own launch failures
 #define DANET_ENTER() (void)hipGetLastError()

@@ -4,19 +4,20 @@
 //   map      one lane per texel (part, i, j): the faces of the part are walked in ascending index (a CSR by part); the first
 //            face whose UV triangle holds the texel centre wins.  Edge functions in double from the f32 UV table, so the
 //            float64 restatement of the tests reproduces face and barycentrics bit for bit.  Made once per topology and T.
-//   unwrap   one lane per (person, texel): loops over the person's views in order; per view the surface point is projected
-//            with the rasteriser's camera (iuv_raster.hip raster_project_kernel, operation by operation), tested against the
-//            rasteriser's depth plane and the facing cosine, and the photograph is sampled bilinearly.  One 16-byte store.
+//   unwrap   one lane per (person, texel): loops danet::add_view (unwrap_view.h, shared with track_reid.hip) over the person's
+//            views in order and stores danet::texel of the sums.  One 16-byte store.
 //   render   one lane per pixel: the winning face comes from the rasteriser's face-index plane; barycentrics as
 //            mesh_shade_pixel_kernel (vis_ops.hip) computes them; a valid-aware bilinear sample of the face's chart.
 //
 // Compiled with -ffp-contract=off: every operation below is one IEEE-754 operation in the written order (the tests restate
 // them).  No LDS, no atomics, no inline assembly.
 #include "common.h"
+#include "unwrap_view.h"
+#include "video_sizes.h"
+
+using namespace danet;
 
 namespace {
-
-constexpr int PARTS = 24;
 
 __global__ __launch_bounds__(256) void texture_map_kernel(
     const float* __restrict__ uv, const int* __restrict__ faces, const int* __restrict__ part_off,
@@ -52,24 +53,9 @@ __global__ __launch_bounds__(256) void texture_map_kernel(
     bary[o * 2 + 1] = (float)b1;
 }
 
-// the rasteriser's intrinsics (iuv_raster.hip raster_project_kernel): for orig != 224 the principal point is scaled too
-struct Camera { float fx, cx, tz; };
-
-__device__ __forceinline__ Camera camera(float focal, float orig, float s) {
-    Camera k;
-    k.fx = focal; k.cx = orig / 2.0f;
-    if (orig != 224.0f) { const float sc = orig / 224.0f; k.fx = k.fx * sc; k.cx = k.cx * sc; }
-    k.tz = (2.0f * focal) / (orig * s + 1e-9f);
-    return k;
-}
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 __global__ __launch_bounds__(256) void texture_unwrap_kernel(
-    const float* __restrict__ images, const float* __restrict__ verts, const float* __restrict__ cam,
-    const float* __restrict__ depth, int NV, int H, const int* __restrict__ view_off,
-    const int* __restrict__ vert_mapping, const int* __restrict__ faces, int F, const int* __restrict__ map_face,
-    const float* __restrict__ map_bary, int ntex, float focal, float depth_tol, float min_cos, float4* __restrict__ atlas)
+    const ViewInputs in, const int* __restrict__ view_off, const int* __restrict__ vert_mapping, const int* __restrict__ faces, int F,
+    const int* __restrict__ map_face, const float* __restrict__ map_bary, int ntex, float4* __restrict__ atlas)
 {
     const int p = blockIdx.y;
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -80,52 +66,10 @@ __global__ __launch_bounds__(256) void texture_unwrap_kernel(
         const float w0 = map_bary[t * 2 + 0], w1 = map_bary[t * 2 + 1];
         const float w2 = 1.0f - w0 - w1;
         const int i0 = vert_mapping[faces[f * 3 + 0]], i1 = vert_mapping[faces[f * 3 + 1]], i2 = vert_mapping[faces[f * 3 + 2]];
-        const float orig = (float)H;
-        const size_t npix = (size_t)H * H;
         float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f;
         const int n1 = view_off[p + 1];
-        for (int n = view_off[p]; n < n1; ++n) {
-            const float* vb = verts + (size_t)n * NV * 3;
-            const float tx = cam[n * 3 + 1], ty = cam[n * 3 + 2];
-            const Camera k = camera(focal, orig, cam[n * 3 + 0]);
-            const float ax = vb[i0 * 3 + 0], ay = vb[i0 * 3 + 1], az = vb[i0 * 3 + 2];
-            const float bx = vb[i1 * 3 + 0], by = vb[i1 * 3 + 1], bz = vb[i1 * 3 + 2];
-            const float cx = vb[i2 * 3 + 0], cy = vb[i2 * 3 + 1], cz = vb[i2 * 3 + 2];
-            // the surface point, then the rasteriser's projection of it
-            const float X = w0 * ax + w1 * bx + w2 * cx, Y = w0 * ay + w1 * by + w2 * cy, Z = w0 * az + w1 * bz + w2 * cz;
-            const float px = X + tx, py = Y + ty, pz = Z + k.tz;
-            const float zz = pz + 1e-9f;
-            const float x = px / zz, y = py / zz;
-            const float c = k.fx * x + k.cx - 0.5f, r = k.fx * y + k.cx - 0.5f;
-            const float rn = floorf(r + 0.5f), cn = floorf(c + 0.5f);
-            if (!(rn >= 0.0f && rn < orig && cn >= 0.0f && cn < orig)) continue;
-            const float d = depth[(size_t)n * npix + (size_t)(int)rn * H + (int)cn];
-            if (!(d < __builtin_inff()) || !(pz <= d + depth_tol)) continue;
-            // facing: the normal of the camera-space corners against the direction to the camera
-            const float t0x = ax + tx, t0y = ay + ty, t0z = az + k.tz;
-            const float ux = (bx + tx) - t0x, uy = (by + ty) - t0y, uz = (bz + k.tz) - t0z;
-            const float vx = (cx + tx) - t0x, vy = (cy + ty) - t0y, vz = (cz + k.tz) - t0z;
-            const float nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
-            const float nl = sqrtf(nx * nx + ny * ny + nz * nz), pl = sqrtf(px * px + py * py + pz * pz);
-            if (!(nl > 0.0f && pl > 0.0f)) continue;
-            const float cs = (0.0f - (nx * px + ny * py + nz * pz)) / (nl * pl);
-            if (!(cs > min_cos)) continue;
-            // bilinear, pixel centres at integers, edge clamp
-            const float rf = floorf(r), cf = floorf(c);
-            const float lr = r - rf, lc = c - cf;
-            const int r0 = clampi((int)rf, H - 1), r1 = clampi((int)rf + 1, H - 1);
-            const int c0 = clampi((int)cf, H - 1), c1 = clampi((int)cf + 1, H - 1);
-            const float* img = images + (size_t)n * 3 * npix;
-            float col[3];
-            for (int ch = 0; ch < 3; ++ch) {
-                const float* plane = img + ch * npix;
-                const float top = (1.0f - lc) * plane[(size_t)r0 * H + c0] + lc * plane[(size_t)r0 * H + c1];
-                const float bot = (1.0f - lc) * plane[(size_t)r1 * H + c0] + lc * plane[(size_t)r1 * H + c1];
-                col[ch] = (1.0f - lr) * top + lr * bot;
-            }
-            sr += cs * col[0]; sg += cs * col[1]; sb += cs * col[2]; sw += cs;
-        }
-        if (sw > 0.0f) out = float4{sr / sw, sg / sw, sb / sw, sw};
+        for (int n = view_off[p]; n < n1; ++n) add_view(in, n, i0, i1, i2, w0, w1, w2, sr, sg, sb, sw);
+        out = texel(sr, sg, sb, sw);
     }
     atlas[(size_t)p * ntex + t] = out;
 }
@@ -190,7 +134,7 @@ __global__ __launch_bounds__(256) void texture_render_kernel(
         const int j0 = (int)fminf(fmaxf(xf, 0.0f), hi), j1 = (int)fminf(fmaxf(xf + 1.0f, 0.0f), hi);
         const int r0 = (int)fminf(fmaxf(yf, 0.0f), hi), r1 = (int)fminf(fmaxf(yf + 1.0f, 0.0f), hi);
         const int part = face_part[f];
-        const float4* chart = atlas + ((size_t)atlas_index[b] * PARTS + part) * T * T;
+        const float4* chart = atlas + ((size_t)atlas_index[b] * kParts + part) * T * T;
         const int ti[4] = {r0 * T + j0, r0 * T + j1, r1 * T + j0, r1 * T + j1};
         const float tb[4] = {(1.0f - ly) * (1.0f - lx), (1.0f - ly) * lx, ly * (1.0f - lx), ly * lx};
         for (int q = 0; q < 4; ++q) {
@@ -216,7 +160,7 @@ extern "C" int danet_texture_map(const float* uv, int NDV, const int32_t* faces,
     DANET_ENTER();
     DANET_CHECK_ARG(NDV > 0 && F > 0 && T >= 2 && T <= 4096, "texture_map: bad sizes NDV=%d F=%d T=%d (T >= 2)", NDV, F, T);
     DANET_CHECK_ARG(uv && faces && part_off && part_faces && face && bary, "texture_map: null pointer");
-    hipLaunchKernelGGL(texture_map_kernel, dim3(danet::cdiv((long)T * T, 256), PARTS), dim3(256), 0, (hipStream_t)stream, uv, faces,
+    hipLaunchKernelGGL(texture_map_kernel, dim3(danet::cdiv((long)T * T, 256), kParts), dim3(256), 0, (hipStream_t)stream, uv, faces,
                        part_off, part_faces, T, face, bary);
     DANET_CHECK_LAUNCH("texture_map_kernel");
     return DANET_OK;
@@ -233,15 +177,13 @@ extern "C" int danet_texture_unwrap(const float* images, const float* verts, con
                     "texture_unwrap: bad sizes N=%d NV=%d NDV=%d F=%d H=%d P=%d T=%d", N, NV, NDV, F, H, P, T);
     DANET_CHECK_ARG(view_off && host_view_off && vert_mapping && faces && map_face && map_bary && atlas, "texture_unwrap: null pointer");
     DANET_CHECK_ARG(N == 0 || (images && verts && cam && depth), "texture_unwrap: null pointer");
-    DANET_CHECK_ARG((long)PARTS * T * T < (1L << 30), "texture_unwrap: T=%d is too large", T);
+    DANET_CHECK_ARG((long)kParts * T * T < (1L << 30), "texture_unwrap: T=%d is too large", T);
     DANET_CHECK_ARG(((uintptr_t)atlas & 15) == 0, "texture_unwrap: atlas must be 16-byte aligned");
-    DANET_CHECK_ARG(host_view_off[0] == 0 && host_view_off[P] == N, "texture_unwrap: view_off must run from 0 to N=%d", N);
-    for (int p = 0; p < P; ++p)
-        DANET_CHECK_ARG(host_view_off[p] <= host_view_off[p + 1], "texture_unwrap: view_off must be non-decreasing");
-    const int ntex = PARTS * T * T;
-    hipLaunchKernelGGL(texture_unwrap_kernel, dim3(danet::cdiv(ntex, 256), P), dim3(256), 0, (hipStream_t)stream, images, verts, cam,
-                       depth, NV, H, view_off, vert_mapping, faces, F, map_face, map_bary, ntex, focal, depth_tol, min_cos,
-                       (float4*)atlas);
+    DANET_CHECK_OFFSETS("texture_unwrap", "view_off", host_view_off, P, N);
+    const int ntex = kParts * T * T;
+    const ViewInputs in = {images, verts, cam, depth, NV, H, focal, depth_tol, min_cos};
+    hipLaunchKernelGGL(texture_unwrap_kernel, dim3(danet::cdiv(ntex, 256), P), dim3(256), 0, (hipStream_t)stream, in, view_off,
+                       vert_mapping, faces, F, map_face, map_bary, ntex, (float4*)atlas);
     DANET_CHECK_LAUNCH("texture_unwrap_kernel");
     return DANET_OK;
 }

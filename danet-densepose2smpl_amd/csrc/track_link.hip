@@ -16,14 +16,14 @@
 #include <vector>
 
 #include "common.h"
+#include "video_sizes.h"
+
+using namespace danet;
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kPairsPerBlock = 4;
-constexpr int kNB = 10;
-constexpr int kParaRow = 229;
-constexpr int kParts = 24;
 constexpr double kWMin = 1e-3;
 
 __device__ __forceinline__ double wave_sum(double v)
@@ -148,10 +148,7 @@ extern "C" int danet_track_group_mean(float* rows, const float* conf, const int3
     DANET_CHECK_ARG(col0 >= 0 && ncol >= 1 && col0 + ncol <= kParaRow, "track_group_mean: columns %d .. %d of %d", col0, col0 + ncol, kParaRow);
     DANET_CHECK_ARG(rows && conf && group_start && group_start_host && group_rows && group_rows_host && mean && status,
                     "track_group_mean: null pointer");
-    DANET_CHECK_ARG(group_start_host[0] == 0 && group_start_host[G] == N, "track_group_mean: group_start must run from 0 to N=%ld, got %d..%d", N,
-                    group_start_host[0], group_start_host[G]);
-    for (int g = 0; g < G; ++g)
-        DANET_CHECK_ARG(group_start_host[g + 1] >= group_start_host[g], "track_group_mean: group_start descends at group %d", g);
+    DANET_CHECK_OFFSETS("track_group_mean", "group_start", group_start_host, G, N);
     std::vector<unsigned char> seen((size_t)N, 0);                             // every row in exactly one group: no two lanes share a row
     for (long r = 0; r < N; ++r) {
         const int32_t row = group_rows_host[r];

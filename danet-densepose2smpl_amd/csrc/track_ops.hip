@@ -15,20 +15,16 @@
 //
 // No grid barrier, no atomics; a lane reads only its own track's rows, so a track's result does not depend on its neighbours in the
 // launch, and two runs give the same bits.  Compiled with -ffp-contract=off: tests/track_oracle.py restates the factor and the two
-// substitutions operation by operation.
+// substitutions operation by operation; they are shared with track_stream.hip (track_rule.h).
 #include "common.h"
 #include "rot6d.h"
+#include "track_rule.h"
+
+using namespace danet;
 
 namespace {
 
 constexpr int kWave = 64;
-constexpr double kEps = 1e-6;
-constexpr int kNB = 10;
-constexpr int kParaRow = 3 + kNB + 216;          // 229
-constexpr int kParaCh = 3 + kNB + 144;           // 157 unknowns
-constexpr int kGroups = 3;                       // cam, betas, rotations
-
-struct Lams { double vel[kGroups]; double acc[kGroups]; };
 
 __global__ __launch_bounds__(kWave) void track_factor_kernel(const float* __restrict__ conf, const int32_t* __restrict__ track_start, int K,
                                                              int G, Lams lam, double* __restrict__ ws, size_t N)
@@ -43,31 +39,10 @@ __global__ __launch_bounds__(kWave) void track_factor_kernel(const float* __rest
     double* D = l2 + N;
     double Dm1 = 0.0, Dm2 = 0.0, l1m1 = 0.0;
     for (int t = 0; t < T; ++t) {
-        const double w = (double)conf[s + t] + kEps;
-        const double nv = T >= 2 ? ((t == 0 || t == T - 1) ? 1.0 : 2.0) : 0.0;
-        const double na = (t + 1 <= T - 2 ? 1.0 : 0.0) + (t >= 1 && t <= T - 2 ? 4.0 : 0.0) + (t - 1 >= 1 ? 1.0 : 0.0);
-        const double d = (w + lv * nv) + la * (T >= 3 ? na : 0.0);
-        double L1 = 0.0, L2 = 0.0;
-        if (t >= 2) L2 = la / Dm2;                                             // f_{t-2} = la
-        if (t >= 1) {
-            const int u = t - 1;                                               // e_u: rows (u, u + 1)
-            const double ne = (u >= 1 && u <= T - 2 ? 1.0 : 0.0) + (u + 1 >= 1 && u + 1 <= T - 2 ? 1.0 : 0.0);
-            const double e = -lv - 2.0 * la * ne;
-            L1 = (e - (L2 * Dm2) * l1m1) / Dm1;
-        }
-        const double Dt = (d - (L1 * L1) * Dm1) - (L2 * L2) * Dm2;
-        l1[t] = L1; l2[t] = L2; D[t] = Dt;
-        Dm2 = Dm1; Dm1 = Dt; l1m1 = L1;
+        const FactorRow f = factor_row(t, T, (double)conf[s + t] + kEps, lv, la, Dm1, Dm2, l1m1);
+        l1[t] = f.L1; l2[t] = f.L2; D[t] = f.Dt;
+        Dm2 = Dm1; Dm1 = f.Dt; l1m1 = f.L1;
     }
-}
-
-// Column of channel ch in a row: the plain form is [N,C]; the para form reads and writes the fit rule's unknowns in place in a
-// [N,229] row: cam, betas, and per joint the [3,2] row-major view of the first two matrix columns.
-template <bool kPara> __device__ __forceinline__ int channel_col(int ch)
-{
-    if (!kPara || ch < 3 + kNB) return ch;
-    const int r = ch - (3 + kNB), j = r / 6, i = r % 6;
-    return 3 + kNB + j * 9 + (i >> 1) * 3 + (i & 1);
 }
 
 template <bool kPara>
@@ -82,7 +57,7 @@ __global__ __launch_bounds__(kWave) void track_solve_kernel(const float* __restr
     const int s = track_start[k], T = track_start[k + 1] - s;
     const int stride = kPara ? kParaRow : C;
     const int col = channel_col<kPara>(ch);
-    const int g = !kPara ? 0 : (ch < 3 ? 0 : (ch < 3 + kNB ? 1 : 2));
+    const int g = channel_group<kPara>(ch);
     const float* x = values + (size_t)s * stride + col;
     float* y = out + (size_t)s * stride + col;
     const float* c = conf + s;
@@ -119,7 +94,7 @@ __global__ __launch_bounds__(kWave) void track_solve_kernel(const float* __restr
         const float ct = c[t];
         const double w = (double)ct + kEps;
         const double yt = ct > 0.0f ? (double)x[(size_t)t * stride] : mean;
-        const double zt = (w * yt - l1[t] * zm1) - l2[t] * zm2;
+        const double zt = forward_step(w * yt, l1[t], zm1, l2[t], zm2);
         z[(size_t)t * C] = zt;
         zm2 = zm1; zm1 = zt;
     }
@@ -127,7 +102,7 @@ __global__ __launch_bounds__(kWave) void track_solve_kernel(const float* __restr
     for (int t = T - 1; t >= 0; --t) {
         const double a1 = t + 1 < T ? l1[t + 1] : 0.0;
         const double a2 = t + 2 < T ? l2[t + 2] : 0.0;
-        const double xt = (z[(size_t)t * C] / D[t] - a1 * xp1) - a2 * xp2;
+        const double xt = backward_step(z[(size_t)t * C], D[t], a1, xp1, a2, xp2);
         float r = (float)xt;
         if (kPara && ch == 0) r = r < lo ? lo : (r > hi ? hi : r);             // (a NaN stays a NaN)
         y[(size_t)t * stride] = r;
@@ -197,17 +172,12 @@ int check_common(const char* op, const void* values, const float* conf, const in
     DANET_CHECK_ARG(N >= 1 && C >= 1 && K >= 1 && N < (1L << 31), "%s: bad sizes N=%ld C=%d K=%d", op, N, C, K);
     DANET_CHECK_ARG(values && conf && track_start && track_start_host && out && status && ws, "%s: null pointer", op);
     DANET_CHECK_ARG(values != out, "%s: the output must not alias the input", op);
-    DANET_CHECK_ARG(track_start_host[0] == 0 && track_start_host[K] == N, "%s: track_start must run from 0 to N=%ld, got %d..%d", op, N,
-                    track_start_host[0], track_start_host[K]);
-    for (int k = 0; k < K; ++k)
-        DANET_CHECK_ARG(track_start_host[k + 1] >= track_start_host[k], "%s: track_start descends at track %d", op, k);
+    DANET_CHECK_OFFSETS(op, "track_start", track_start_host, K, N);
     DANET_CHECK_ARG((long)K * danet::cdiv(C, kWave) < (1L << 31), "%s: K=%d tracks of C=%d channels exceed the grid", op, K, C);
     if (ws_bytes < danet_track_smooth_ws_bytes(N, C))
         return ::danet::fail(DANET_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", op, ws_bytes, danet_track_smooth_ws_bytes(N, C));
     return DANET_OK;
 }
-
-bool lam_ok(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }    // not negative, finite, not NaN
 
 }  // namespace
 
@@ -244,14 +214,9 @@ extern "C" int danet_track_smooth_para(const float* para, const float* conf, con
     DANET_ENTER();
     const int rc = check_common("track_smooth_para", para, conf, track_start, track_start_host, N, kParaCh, K, out, status, ws, ws_bytes);
     if (rc != DANET_OK) return rc;
-    DANET_CHECK_ARG(lam, "track_smooth_para: null lam");
-    DANET_CHECK_ARG(N * 24 / kWave + 1 < (1L << 31), "track_smooth_para: N=%ld rows exceed the grid", N);
     Lams l = {};
-    for (int g = 0; g < kGroups; ++g) {
-        l.vel[g] = lam[2 * g]; l.acc[g] = lam[2 * g + 1];
-        DANET_CHECK_ARG(lam_ok(l.vel[g]) && lam_ok(l.acc[g]), "track_smooth_para: group %d lam_vel=%g lam_acc=%g (finite and not negative)", g,
-                        l.vel[g], l.acc[g]);
-    }
+    if (const int e = read_lams("track_smooth_para", lam, l)) return e;
+    DANET_CHECK_ARG(N * 24 / kWave + 1 < (1L << 31), "track_smooth_para: N=%ld rows exceed the grid", N);
     const int cb = danet::cdiv(kParaCh, kWave);
     hipLaunchKernelGGL(track_factor_kernel, dim3(danet::cdiv((long)K * kGroups, kWave)), dim3(kWave), 0, (hipStream_t)stream, conf, track_start,
                        K, kGroups, l, (double*)ws, (size_t)N);
@@ -271,10 +236,7 @@ extern "C" int danet_track_accel(const float* joints, const float* joints_ref, c
     DANET_ENTER();
     DANET_CHECK_ARG(N >= 1 && J >= 1 && K >= 1 && N < (1L << 31), "track_accel: bad sizes N=%ld J=%d K=%d", N, J, K);
     DANET_CHECK_ARG(joints && track_start && track_start_host && accel && count, "track_accel: null pointer");
-    DANET_CHECK_ARG(track_start_host[0] == 0 && track_start_host[K] == N, "track_accel: track_start must run from 0 to N=%ld, got %d..%d", N,
-                    track_start_host[0], track_start_host[K]);
-    for (int k = 0; k < K; ++k)
-        DANET_CHECK_ARG(track_start_host[k + 1] >= track_start_host[k], "track_accel: track_start descends at track %d", k);
+    DANET_CHECK_OFFSETS("track_accel", "track_start", track_start_host, K, N);
     hipLaunchKernelGGL(track_accel_kernel, dim3(K), dim3(kWave), 0, (hipStream_t)stream, joints, joints_ref, track_start, J, accel, count);
     DANET_CHECK_LAUNCH("track_accel_kernel");
     return DANET_OK;

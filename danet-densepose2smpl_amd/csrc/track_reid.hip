@@ -3,14 +3,14 @@
 // at a time, for S slots.
 //
 //   track_desc_step   one lane per (person of the frame, texel).  The lane loads the four unnormalised sums (sum cs r, sum cs g, sum cs b,
-//                     sum cs) of its texel of the person's slot (one 16-byte load), adds this frame's view with the per-view body of
-//                     texture_unwrap_kernel (texture_ops.hip), restated operation by operation, and stores them (one 16-byte store).  The
+//                     sum cs) of its texel of the person's slot (one 16-byte load), adds this frame's view with danet::add_view
+//                     (unwrap_view.h), the function texture_unwrap_kernel (texture_ops.hip) loops, and stores them (one 16-byte store).  The
 //                     sums after n views are the registers of texture_unwrap_kernel after the same n views: dividing them gives its bits.
 //                     Eleven lanes of each person's first workgroup add the row to the shape sums as track_group_mean_kernel
 //                     (track_link.hip) adds it: sum_c += (double)c, sum_y += (double)c * (double)beta, only where c > 0.  A gap row
 //                     (observed 0) adds to the shape alone: its image, mesh and depth are never read.  S further rows of workgroups empty the
 //                     slots named in `reset` that hold no person of this frame; a person's lanes empty their own slot by starting from 0.
-//   track_desc_read   one lane per (pair, texel): the descriptor of a slot goes into a row of the table, unwrap's last line for the skin,
+//   track_desc_read   one lane per (pair, texel): the descriptor of a slot goes into a row of the table, unwrap's danet::texel for the skin,
 //                     (float)(sum_y / sum_c) for the shape; the raw shape sums go beside it in double.
 //   track_desc_shape  one lane per (row, shape column): the betas of an emitted row become (float)((carry_y + sum_y) / (carry_c + sum_c)).
 //
@@ -19,26 +19,14 @@
 #include <vector>
 
 #include "common.h"
+#include "unwrap_view.h"
+#include "video_sizes.h"
+
+using namespace danet;
 
 namespace {
 
-constexpr int kParts = 24;
-constexpr int kNB = 10;
-constexpr int kParaRow = 229;
 constexpr int kShapeWords = 12;                       // sum_y [10], sum_c, one spare: a slot's shape sums are 96 bytes
-
-// the rasteriser's intrinsics, as texture_ops.hip states them
-struct Camera { float fx, cx, tz; };
-
-__device__ __forceinline__ Camera camera(float focal, float orig, float s) {
-    Camera k;
-    k.fx = focal; k.cx = orig / 2.0f;
-    if (orig != 224.0f) { const float sc = orig / 224.0f; k.fx = k.fx * sc; k.cx = k.cx * sc; }
-    k.tz = (2.0f * focal) / (orig * s + 1e-9f);
-    return k;
-}
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 __device__ __forceinline__ float4* slot_acc(void* state, int s, int ntex) { return (float4*)state + (size_t)s * ntex; }
 
@@ -48,10 +36,10 @@ __device__ __forceinline__ double* slot_shape(void* state, int S, int s, int nte
 }
 
 struct StepArgs {
-    const float *images, *verts, *cam, *depth, *para, *conf, *map_bary;
+    ViewInputs view;                                                         // the chunk's frames: person p is view p
+    const float *para, *conf, *map_bary;
     const int32_t *slot, *observed, *reset, *vert_mapping, *faces, *map_face;
-    int S, P, NV, NDV, F, H, ntex;
-    float focal, depth_tol, min_cos;
+    int S, P, NDV, F, ntex;
 };
 
 __global__ __launch_bounds__(256) void track_desc_step_kernel(void* __restrict__ state, const StepArgs a)
@@ -85,58 +73,14 @@ __global__ __launch_bounds__(256) void track_desc_step_kernel(void* __restrict__
     const int f = a.map_face[t];
     if (seen && f >= 0 && f < a.F) {
         float sr = sum.x, sg = sum.y, sb = sum.z, sw = sum.w;
-        const int H = a.H;
-        const float depth_tol = a.depth_tol, min_cos = a.min_cos;
         const float w0 = a.map_bary[t * 2 + 0], w1 = a.map_bary[t * 2 + 1];
         const float w2 = 1.0f - w0 - w1;
         const int d0 = a.faces[f * 3 + 0], d1 = a.faces[f * 3 + 1], d2 = a.faces[f * 3 + 2];
         const bool named = d0 >= 0 && d0 < a.NDV && d1 >= 0 && d1 < a.NDV && d2 >= 0 && d2 < a.NDV;
         const int i0 = named ? a.vert_mapping[d0] : -1, i1 = named ? a.vert_mapping[d1] : -1, i2 = named ? a.vert_mapping[d2] : -1;
-        const float orig = (float)H;
-        const size_t npix = (size_t)H * H;
-        const int n = p;
-        do {                                                                 // the body of texture_unwrap_kernel's loop over the views, once
-            if (i0 < 0 || i0 >= a.NV || i1 < 0 || i1 >= a.NV || i2 < 0 || i2 >= a.NV) break;      // (refused on the host already)
-            const float* vb = a.verts + (size_t)n * a.NV * 3;
-            const float tx = a.cam[n * 3 + 1], ty = a.cam[n * 3 + 2];
-            const Camera k = camera(a.focal, orig, a.cam[n * 3 + 0]);
-            const float ax = vb[i0 * 3 + 0], ay = vb[i0 * 3 + 1], az = vb[i0 * 3 + 2];
-            const float bx = vb[i1 * 3 + 0], by = vb[i1 * 3 + 1], bz = vb[i1 * 3 + 2];
-            const float cx = vb[i2 * 3 + 0], cy = vb[i2 * 3 + 1], cz = vb[i2 * 3 + 2];
-            // the surface point, then the rasteriser's projection of it
-            const float X = w0 * ax + w1 * bx + w2 * cx, Y = w0 * ay + w1 * by + w2 * cy, Z = w0 * az + w1 * bz + w2 * cz;
-            const float px = X + tx, py = Y + ty, pz = Z + k.tz;
-            const float zz = pz + 1e-9f;
-            const float x = px / zz, y = py / zz;
-            const float c = k.fx * x + k.cx - 0.5f, r = k.fx * y + k.cx - 0.5f;
-            const float rn = floorf(r + 0.5f), cn = floorf(c + 0.5f);
-            if (!(rn >= 0.0f && rn < orig && cn >= 0.0f && cn < orig)) break;
-            const float d = a.depth[(size_t)n * npix + (size_t)(int)rn * H + (int)cn];
-            if (!(d < __builtin_inff()) || !(pz <= d + depth_tol)) break;
-            // facing: the normal of the camera-space corners against the direction to the camera
-            const float t0x = ax + tx, t0y = ay + ty, t0z = az + k.tz;
-            const float ux = (bx + tx) - t0x, uy = (by + ty) - t0y, uz = (bz + k.tz) - t0z;
-            const float vx = (cx + tx) - t0x, vy = (cy + ty) - t0y, vz = (cz + k.tz) - t0z;
-            const float nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
-            const float nl = sqrtf(nx * nx + ny * ny + nz * nz), pl = sqrtf(px * px + py * py + pz * pz);
-            if (!(nl > 0.0f && pl > 0.0f)) break;
-            const float cs = (0.0f - (nx * px + ny * py + nz * pz)) / (nl * pl);
-            if (!(cs > min_cos)) break;
-            // bilinear, pixel centres at integers, edge clamp
-            const float rf = floorf(r), cf = floorf(c);
-            const float lr = r - rf, lc = c - cf;
-            const int r0 = clampi((int)rf, H - 1), r1 = clampi((int)rf + 1, H - 1);
-            const int c0 = clampi((int)cf, H - 1), c1 = clampi((int)cf + 1, H - 1);
-            const float* img = a.images + (size_t)n * 3 * npix;
-            float col[3];
-            for (int ch = 0; ch < 3; ++ch) {
-                const float* plane = img + ch * npix;
-                const float top = (1.0f - lc) * plane[(size_t)r0 * H + c0] + lc * plane[(size_t)r0 * H + c1];
-                const float bot = (1.0f - lc) * plane[(size_t)r1 * H + c0] + lc * plane[(size_t)r1 * H + c1];
-                col[ch] = (1.0f - lr) * top + lr * bot;
-            }
-            sr += cs * col[0]; sg += cs * col[1]; sb += cs * col[2]; sw += cs;
-        } while (false);
+        const int NV = a.view.NV;
+        if (i0 >= 0 && i0 < NV && i1 >= 0 && i1 < NV && i2 >= 0 && i2 < NV)      // (anything else is refused on the host already)
+            add_view(a.view, p, i0, i1, i2, w0, w1, w2, sr, sg, sb, sw);          // the frame's one view: person p of the chunk
         sum = float4{sr, sg, sb, sw};
     }
     *acc = sum;
@@ -161,9 +105,7 @@ __global__ __launch_bounds__(256) void track_desc_read_kernel(const void* __rest
     }
     if (t >= ntex) return;
     const float4 sum = slot_acc(const_cast<void*>(state), s, ntex)[t];
-    float4 out = float4{0.0f, 0.0f, 0.0f, 0.0f};
-    if (sum.w > 0.0f) out = float4{sum.x / sum.w, sum.y / sum.w, sum.z / sum.w, sum.w};
-    desc_atlas[(size_t)row * ntex + t] = out;
+    desc_atlas[(size_t)row * ntex + t] = texel(sum.x, sum.y, sum.z, sum.w);
 }
 
 __global__ __launch_bounds__(64) void track_desc_shape_kernel(const void* __restrict__ state, int S, int ntex, float* __restrict__ rows,
@@ -214,10 +156,10 @@ extern "C" int danet_track_desc_step(void* state, size_t state_nbytes, int S, in
         taken[(size_t)s] = 1;
     }
     StepArgs a;
-    a.images = images; a.verts = verts; a.cam = cam; a.depth = depth; a.para = para; a.conf = conf; a.map_bary = map_bary;
+    a.view = ViewInputs{images, verts, cam, depth, NV, H, focal, depth_tol, min_cos};
+    a.para = para; a.conf = conf; a.map_bary = map_bary;
     a.slot = slot; a.observed = observed; a.reset = reset; a.vert_mapping = vert_mapping; a.faces = faces; a.map_face = map_face;
-    a.S = S; a.P = P; a.NV = NV; a.NDV = NDV; a.F = F; a.H = H; a.ntex = kParts * T * T;
-    a.focal = focal; a.depth_tol = depth_tol; a.min_cos = min_cos;
+    a.S = S; a.P = P; a.NDV = NDV; a.F = F; a.ntex = kParts * T * T;
     hipLaunchKernelGGL(track_desc_step_kernel, dim3(danet::cdiv(a.ntex, 256), P + S), dim3(256), 0, (hipStream_t)stream, state, a);
     DANET_CHECK_LAUNCH("track_desc_step_kernel");
     return DANET_OK;

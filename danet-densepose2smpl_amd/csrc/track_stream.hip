@@ -14,22 +14,19 @@
 //
 // The rings hold R = lag + max_new + 4 rows: the back substitution reaches lag rows back, the refactoring max_new + 4.  A lane
 // touches only its own slot's state, rows and output: a slot's bits do not depend on its neighbours.  No atomics, no grid barrier,
-// nothing read on the host.  Compiled with -ffp-contract=off: the operations are those of track_ops.hip and tests/track_oracle.py.
+// nothing read on the host.  Compiled with -ffp-contract=off: the factor row and the substitution steps are shared with
+// track_ops.hip (track_rule.h) and restated in tests/track_oracle.py.
 #include "common.h"
 #include "rot6d.h"
+#include "track_rule.h"
+
+using namespace danet;
 
 namespace {
 
 constexpr int kWave = 64;
-constexpr double kEps = 1e-6;
-constexpr int kNB = 10;
-constexpr int kParaRow = 3 + kNB + 216;          // 229
-constexpr int kParaCh = 3 + kNB + 144;           // 157 unknowns
-constexpr int kGroups = 3;                       // cam, betas, rotations
 constexpr int kParaBlock = 192;                  // >= kParaCh: one lane per unknown
 constexpr int kMaxSlots = 1 << 20, kMaxLag = 4096, kMaxNew = 64, kMaxC = 65536;
-
-struct Lams { double vel[kGroups]; double acc[kGroups]; };
 
 struct SlotHeader { int32_t T; int32_t pad; float lo; float hi; double sc; };    // 24 bytes; all zero: an empty slot
 static_assert(sizeof(SlotHeader) == 24, "SlotHeader");
@@ -39,13 +36,6 @@ __host__ __device__ inline size_t slot_bytes(int C, int R)
 {
     const size_t Re = (size_t)((R + 1) & ~1);
     return sizeof(SlotHeader) + 4 * Re + 8 * ((size_t)kGroups * 4 * R + (size_t)C + 2 * (size_t)R * C);
-}
-
-template <bool kPara> __device__ __forceinline__ int channel_col(int ch)
-{
-    if (!kPara || ch < 3 + kNB) return ch;
-    const int r = ch - (3 + kNB), j = r / 6, i = r % 6;
-    return 3 + kNB + j * 9 + (i >> 1) * 3 + (i & 1);
 }
 
 template <bool kPara>
@@ -90,21 +80,10 @@ __global__ __launch_bounds__(256) void track_stream_kernel(unsigned char* __rest
         for (int t = t0; t < T; ++t) {
             const float ct = t >= T0 ? cin[t - T0] : cring[t % R];
             const double w = (double)ct + kEps;
-            const double nv = T >= 2 ? ((t == 0 || t == T - 1) ? 1.0 : 2.0) : 0.0;
-            const double na = (t + 1 <= T - 2 ? 1.0 : 0.0) + (t >= 1 && t <= T - 2 ? 4.0 : 0.0) + (t - 1 >= 1 ? 1.0 : 0.0);
-            const double d = (w + lv * nv) + la * (T >= 3 ? na : 0.0);
-            double L1 = 0.0, L2 = 0.0;
-            if (t >= 2) L2 = la / Dm2;
-            if (t >= 1) {
-                const int u = t - 1;
-                const double ne = (u >= 1 && u <= T - 2 ? 1.0 : 0.0) + (u + 1 >= 1 && u + 1 <= T - 2 ? 1.0 : 0.0);
-                const double e = -lv - 2.0 * la * ne;
-                L1 = (e - (L2 * Dm2) * l1m1) / Dm1;
-            }
-            const double Dt = (d - (L1 * L1) * Dm1) - (L2 * L2) * Dm2;
-            const double zt = ((ct > 0.0f ? 0.0 : w) - L1 * zm1) - L2 * zm2;
-            l1[t % R] = L1; l2[t % R] = L2; D[t % R] = Dt; zB[t % R] = zt;
-            Dm2 = Dm1; Dm1 = Dt; l1m1 = L1;
+            const FactorRow f = factor_row(t, T, w, lv, la, Dm1, Dm2, l1m1);
+            const double zt = forward_step(ct > 0.0f ? 0.0 : w, f.L1, zm1, f.L2, zm2);
+            l1[t % R] = f.L1; l2[t % R] = f.L2; D[t % R] = f.Dt; zB[t % R] = zt;
+            Dm2 = Dm1; Dm1 = f.Dt; l1m1 = f.L1;
             zm2 = zm1; zm1 = zt;
         }
     }
@@ -129,7 +108,7 @@ __global__ __launch_bounds__(256) void track_stream_kernel(unsigned char* __rest
     // ---- phase 2: a lane per channel ----------------------------------------------------------------------------------------------
     for (int ch = tid; ch < C; ch += blockDim.x) {
         const int col = channel_col<kPara>(ch);
-        const int g = !kPara ? 0 : (ch < 3 ? 0 : (ch < 3 + kNB ? 1 : 2));
+        const int g = channel_group<kPara>(ch);
         const double* l1 = fac + (size_t)g * 4 * R;
         const double* l2 = l1 + R;
         const double* D = l2 + R;
@@ -157,7 +136,7 @@ __global__ __launch_bounds__(256) void track_stream_kernel(unsigned char* __rest
             double zm1 = t0 >= 1 ? zA[(size_t)((t0 - 1) % R) * C + ch] : 0.0, zm2 = t0 >= 2 ? zA[(size_t)((t0 - 2) % R) * C + ch] : 0.0;
             for (int t = t0; t < T; ++t) {
                 const int r = t % R;
-                const double zt = (rA[(size_t)r * C + ch] - l1[r] * zm1) - l2[r] * zm2;
+                const double zt = forward_step(rA[(size_t)r * C + ch], l1[r], zm1, l2[r], zm2);
                 zA[(size_t)r * C + ch] = zt;
                 zm2 = zm1; zm1 = zt;
             }
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(256) void track_stream_kernel(unsigned char* __rest
                     const double a1 = t + 1 < T ? l1[(t + 1) % R] : 0.0;
                     const double a2 = t + 2 < T ? l2[(t + 2) % R] : 0.0;
                     const double z = zA[(size_t)r * C + ch] + mean * zB[r];
-                    xt = (z / D[r] - a1 * xp1) - a2 * xp2;
+                    xt = backward_step(z, D[r], a1, xp1, a2, xp2);
                     xp2 = xp1; xp1 = xt;
                 }
                 res = (float)xt;
@@ -203,8 +182,6 @@ __global__ __launch_bounds__(256) void track_stream_kernel(unsigned char* __rest
         }
     }
 }
-
-bool lam_ok(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }    // not negative, finite, not NaN
 
 int check_common(const char* op, const void* state, size_t state_bytes, int S, int C, int lag, int max_new, const void* n_new,
                  const void* reset, const void* rows, const void* conf, const void* emit, const void* out, const void* valid)
@@ -250,13 +227,8 @@ extern "C" int danet_track_stream_step_para(void* state, size_t state_bytes, int
     DANET_ENTER();
     const int rc = check_common("track_stream_step_para", state, state_bytes, S, kParaCh, lag, max_new, n_new, reset, rows, conf, emit, out, valid);
     if (rc != DANET_OK) return rc;
-    DANET_CHECK_ARG(lam, "track_stream_step_para: null lam");
     Lams l = {};
-    for (int g = 0; g < kGroups; ++g) {
-        l.vel[g] = lam[2 * g]; l.acc[g] = lam[2 * g + 1];
-        DANET_CHECK_ARG(lam_ok(l.vel[g]) && lam_ok(l.acc[g]), "track_stream_step_para: group %d lam_vel=%g lam_acc=%g (finite and not negative)", g,
-                        l.vel[g], l.acc[g]);
-    }
+    if (const int e = read_lams("track_stream_step_para", lam, l)) return e;
     static_assert(kParaBlock >= kParaCh, "one lane per unknown");
     hipLaunchKernelGGL(track_stream_kernel<true>, dim3(S), dim3(kParaBlock), 0, (hipStream_t)stream, (unsigned char*)state, kParaCh, lag, max_new,
                        n_new, reset, rows, conf, emit, l, shared_shape ? 1 : 0, out, valid);
