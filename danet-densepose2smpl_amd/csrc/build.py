@@ -58,8 +58,8 @@ UNITS = {
     'scene_ops.hip': ['-ffp-contract=off'],   # the scene rule's arithmetic is restated operation by operation in the tests
     # the texture rule likewise; its map is bit-equal to a float64 restatement; the per-view body is shared (unwrap_view.h) with track_reid.hip
     'texture_ops.hip': ['-ffp-contract=off'],
-    'kp_fit.hip': [],
-    'dense_fit.hip': [],
+    'kp_fit.hip': [],               # fit_kernel<false, ...> of fit_kernel.h: the fit's one text, the keypoint term alone
+    'dense_fit.hip': [],            # fit_kernel<true, ...> of fit_kernel.h: the same text with the landmark term; same (no) flags as kp_fit.hip
     'fit_loop.hip': ['-ffp-contract=off'],    # the pose undo is input_ops.hip's (pose_aug.h): the same bits in both units
     'track_ops.hip': ['-ffp-contract=off'],   # the track rule's factor and substitutions are restated operation by operation in the tests
     'track_stream.hip': ['-ffp-contract=off'],  # the factor row and substitution steps shared (track_rule.h) with track_ops.hip, one row at a time

@@ -1,5 +1,5 @@
 // 6D rotation representation -> rotation matrix and its backward, ONE pair of device functions for every caller: geometry.hip
-// (danet_rot6d_to_rotmat_forward / _backward, one thread per rotation) and kp_fit.hip (the keypoint fit, 24 rotations per person per
+// (danet_rot6d_to_rotmat_forward / _backward, one thread per rotation) and fit_kernel.h (the keypoint and dense fits, 24 rotations per person per
 // iteration, operands in LDS).
 #pragma once
 #include <hip/hip_runtime.h>
