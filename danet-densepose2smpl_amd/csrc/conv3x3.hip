@@ -23,16 +23,13 @@
 // the data gradient only mirrors the tap offsets.
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 #include <type_traits>
 
 namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-
-constexpr int OOB = 0x7fffffff;
 constexpr int TAB_BYTES = 1024;           // tap table: up to 128 k-steps x {lo, hi} offsets
 constexpr int NSUB = 2;                   // staging: a row's W*S chunks are covered by NSUB passes of 256 threads
 constexpr int PADN = 4;                   // pad-column cells re-zeroed per thread (K-split tiles only)
@@ -55,34 +52,6 @@ struct C3Prob {
 
 struct C3Launch { C3Prob p[C3_MAXP]; int n; int total; int stagger; };
 
-__device__ inline unsigned udiv24(unsigned n, unsigned d, float rcp) {      // n < 2^24
-    unsigned q = (unsigned)((float)n * rcp);
-    const int r = (int)(n - q * d);
-    if (r < 0) --q; else if (r >= (int)d) ++q;
-    return q;
-}
-
-// Workgroup barrier that orders LDS traffic only: global stores of the epilogue keep draining across it
-// (__syncthreads() would wait for them: its fence covers every address space).
-__device__ inline void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, o);
-}
-__device__ inline float row_sum16(float v) {
-    v = dpp_add<0xB1>(v);
-    v = dpp_add<0x4E>(v);
-    v = dpp_add<0x141>(v);
-    v = dpp_add<0x140>(v);
-    return v;
-}
-
 // s1/s2[nt][r] (per-lane partial sums of channels n0 + nt*16 + lg*4 + r) -> 16 pixel lanes (DPP) -> 4 waves (LDS
 // scratch `sc`, >= 4*2*NT*16 floats, free at this point) -> one atomic per channel into replica rep % BN_NCOPY.
 template <int NT>
@@ -99,12 +68,7 @@ __device__ inline void flush_channel_sums(float (*s1)[4], float (*s2)[4], float*
             s1[nt][r] = 0.f; s2[nt][r] = 0.f;
         }
     lds_barrier();
-    if (t < 2 * NT * 16) {
-        const int which = t / (NT * 16), c = t - which * (NT * 16);
-        const float v = (sc[(0 * 2 + which) * (NT * 16) + c] + sc[(1 * 2 + which) * (NT * 16) + c]) +
-                        (sc[(2 * 2 + which) * (NT * 16) + c] + sc[(3 * 2 + which) * (NT * 16) + c]);
-        if (n0 + c < Ctot) bn_acc_add(dst, rep, which, Ctot, n0 + c, v);
-    }
+    scratch_to_replicas<NT>(sc, dst, rep, Ctot, 0, n0, Ctot, t);
     lds_barrier();                          // (the scratch overlays tile cells: the next staging pass rewrites them, pad columns included)
 }
 
@@ -400,14 +364,13 @@ __device__ __forceinline__ void c3_body(const C3Prob& p, const int bid, const in
                         if (p.addend) {
                             const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.addend), 0, p.y_bytes, 0x00020000);
                             const i32x2 aq = __builtin_amdgcn_raw_buffer_load_b64(ar, off, so, 0);
-                            v[0] += __uint_as_float((unsigned)aq.x << 16); v[1] += __uint_as_float((unsigned)aq.x & 0xffff0000u);
-                            v[2] += __uint_as_float((unsigned)aq.y << 16); v[3] += __uint_as_float((unsigned)aq.y & 0xffff0000u);
+                            v = add_bf16x4(v, aq);
                         }
                         if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
                         if (p.out_fp32) {
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), yr, off, so, 0);
                         } else {
-                            const i32x2 pk = {(int)f2bf_pk(v[0], v[1]), (int)f2bf_pk(v[2], v[3])};
+                            const i32x2 pk = pack_bf16x4(v);
                             __builtin_amdgcn_raw_buffer_store_b64(pk, yr, off, so, 0);
                             if (p.stats) {
                                 // BatchNorm statistics from the fp32 accumulators (two VALU per value): they differ from the
@@ -426,6 +389,7 @@ __device__ __forceinline__ void c3_body(const C3Prob& p, const int bid, const in
                                 const __amdgpu_buffer_rsrc_t bxr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.bn_x), 0, p.y_bytes, 0x00020000);
                                 const __amdgpu_buffer_rsrc_t byr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.bn_y ? p.bn_y : p.bn_x), 0, p.y_bytes, 0x00020000);
                                 const i32x2 xq = __builtin_amdgcn_raw_buffer_load_b64(bxr, off, so, 0);
+                                // (bf16x4_to_f32 of conv_lane.h written out, here and for gq: with f32x4 values the instruction order of every tiling changed)
                                 const float xv[4] = {__uint_as_float((unsigned)xq.x << 16), __uint_as_float((unsigned)xq.x & 0xffff0000u),
                                                      __uint_as_float((unsigned)xq.y << 16), __uint_as_float((unsigned)xq.y & 0xffff0000u)};
                                 // the ReLU gate as 4 bits: from the BatchNorm's output (8 bytes per lane) or its byte mask (1 byte)

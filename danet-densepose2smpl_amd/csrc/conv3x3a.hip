@@ -17,17 +17,13 @@
 //     its output or its byte mask (data gradient) -- the contracts of danet_conv_forward's bn_sums / bn_* / addend arguments.
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 #include <type_traits>
 
 namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int OOB = 0x7fffffff;
 constexpr int CA_NT = 4, CA_MT = 8, CA_D = 3, CA_KS = 5;    // 5 k-steps per 16-channel slab in the chunk-16 packing (9 taps + 1 zero tap)
 constexpr int CA_NE0 = 12, CA_NE1 = 6, CA_NEMAX = 16;        // k-steps per tile of the two K halves (+ wrap-around entries)
 constexpr int CA_EXCH = 32768;
@@ -50,29 +46,6 @@ struct C3aP {
     int bytes;                                               // of x (= of y: same shape)
     const float* bias; int relu;                             // conv3x3a_bias_kernel only: y = [relu](acc + bias[c] [+ addend])
 };
-
-__device__ __forceinline__ void dma16(unsigned lds_addr, int voff, const i32x4& desc, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds_addr), "v"(voff), "s"(desc), "s"(soff) : "memory");
-}
-__device__ inline i32x4 raw_desc(const void* base, int bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffffu)),
-                 __builtin_amdgcn_readfirstlane(bytes), 0x00020000};
-}
-__device__ inline void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, o);
-}
-__device__ inline float row_sum16(float v) {
-    v = dpp_add<0xB1>(v); v = dpp_add<0x4E>(v); v = dpp_add<0x141>(v); v = dpp_add<0x140>(v);
-    return v;
-}
 
 // EPI = false: the training forward / data gradient; EPI = true: the folded-inference forward (bias, optional residual addend, optional
 // ReLU; no statistics).  Two kernels over one body, so conv3x3a_kernel itself compiles as before.
@@ -218,7 +191,7 @@ __device__ __forceinline__ void conv3x3a_body(const C3aP& p)
         for (int q = 0; q < NE; ++q) CA_KSTEP(A[q % CA_D], Bq[q & 1], Bq[(q + 1) & 1], q, q + 1 < NE, q == 0);
 #undef CA_KSTEP
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");                   // (inline-asm MFMAs: the hazard recogniser does not see them)
-        // ---- the two K halves meet in LDS: wave (pw, 0) finishes fragments 0-3, wave (pw, 1) fragments 4-7
+        // ---- the two K halves meet in LDS: wave (pw, 0) finishes fragments 0-3, wave (pw, 1) fragments 4-7 (conv_stem.hip's exchange, written out: conv_lane.h says why)
 #pragma unroll
         for (int round = 0; round < 2; ++round) {
             unsigned char* const mine = sR + wave * 8192 + lane * 16;
@@ -266,10 +239,7 @@ __device__ __forceinline__ void conv3x3a_body(const C3aP& p)
                 if (p.addend) {                             // before the exchange a lane holds channels nt * 16 + lg * 4 .. + 3 of pixel li
                     const i32x2 qa = __builtin_amdgcn_raw_buffer_load_b64(adr, (pix * 64 + np * 16 + lg * 4) * 2, 0, 0);
                     const i32x2 qb = __builtin_amdgcn_raw_buffer_load_b64(adr, (pix * 64 + (np + 1) * 16 + lg * 4) * 2, 0, 0);
-                    va[0] += __uint_as_float((unsigned)qa.x << 16); va[1] += __uint_as_float((unsigned)qa.x & 0xffff0000u);
-                    va[2] += __uint_as_float((unsigned)qa.y << 16); va[3] += __uint_as_float((unsigned)qa.y & 0xffff0000u);
-                    vb[0] += __uint_as_float((unsigned)qb.x << 16); vb[1] += __uint_as_float((unsigned)qb.x & 0xffff0000u);
-                    vb[2] += __uint_as_float((unsigned)qb.y << 16); vb[3] += __uint_as_float((unsigned)qb.y & 0xffff0000u);
+                    va = add_bf16x4(va, qa); vb = add_bf16x4(vb, qb);
                 }
                 if constexpr (EPI) {
                     if (p.relu) {
@@ -277,22 +247,12 @@ __device__ __forceinline__ void conv3x3a_body(const C3aP& p)
                         for (int r = 0; r < 4; ++r) { va[r] = fmaxf(va[r], 0.f); vb[r] = fmaxf(vb[r], 0.f); }
                     }
                 }
-                const i32x2 pa = {(int)f2bf_pk(va[0], va[1]), (int)f2bf_pk(va[2], va[3])}, pb = {(int)f2bf_pk(vb[0], vb[1]), (int)f2bf_pk(vb[2], vb[3])};
-                if (!EPI && p.stats) {
-                    auto stat = [&](int nt, const i32x2& pk) {
-                        f32x2_ lo = {__uint_as_float((unsigned)pk.x << 16), __uint_as_float((unsigned)pk.x & 0xffff0000u)};
-                        f32x2_ hi = {__uint_as_float((unsigned)pk.y << 16), __uint_as_float((unsigned)pk.y & 0xffff0000u)};
-                        f32x2_& a0 = *reinterpret_cast<f32x2_*>(&t1[nt][0]); f32x2_& a1 = *reinterpret_cast<f32x2_*>(&t1[nt][2]);
-                        f32x2_& q0 = *reinterpret_cast<f32x2_*>(&t2[nt][0]); f32x2_& q1 = *reinterpret_cast<f32x2_*>(&t2[nt][2]);
-                        a0 += lo; a1 += hi;
-                        q0 = __builtin_elementwise_fma(lo, lo, q0); q1 = __builtin_elementwise_fma(hi, hi, q1);
-                    };
-                    stat(np, pa); stat(np + 1, pb);
+                const i32x2 pa = pack_bf16x4(va), pb = pack_bf16x4(vb);
+                if (!EPI && p.stats) {                      // statistics of the bf16-ROUNDED output
+                    sums_add(t1[np], t2[np], bf16x4_to_f32(pa)); sums_add(t1[np + 1], t2[np + 1], bf16x4_to_f32(pb));
                 }
-                const auto sx = __builtin_amdgcn_permlane16_swap((unsigned)pa.x, (unsigned)pb.x, false, false);
-                const auto sy = __builtin_amdgcn_permlane16_swap((unsigned)pa.y, (unsigned)pb.y, false, false);
-                const i32x4 q = {(int)sx[0], (int)sy[0], (int)sx[1], (int)sy[1]};
-                const int c8 = (np + (lg & 1)) * 16 + (lg >> 1) * 8;               // the lane's eight channels after the exchange (conv_pw.hip)
+                const i32x4 q = swap8(pa, pb);
+                const int c8 = (np + (lg & 1)) * 16 + (lg >> 1) * 8;               // the lane's eight channels after the exchange
                 const int off = (pix * 64 + c8) * 2;
                 __builtin_amdgcn_raw_buffer_store_b128(q, yr, off, 0, 0);
                 if (!EPI && p.bn_red) {
@@ -311,45 +271,20 @@ __device__ __forceinline__ void conv3x3a_body(const C3aP& p)
                             yq = __builtin_amdgcn_raw_buffer_load_b128(byr, off, 0, 0);
                         }
                     }
-                    const f32x4 m0 = *reinterpret_cast<const f32x4*>(sMean + c8), m1 = *reinterpret_cast<const f32x4*>(sMean + c8 + 4);
-                    const f32x4 i0 = *reinterpret_cast<const f32x4*>(sMean + 64 + c8), i1 = *reinterpret_cast<const f32x4*>(sMean + 64 + c8 + 4);
-                    const float mean[8] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-                    const float invs[8] = {i0[0], i0[1], i0[2], i0[3], i1[0], i1[1], i1[2], i1[3]};
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const unsigned gw = (unsigned)q[k >> 1], xw = (unsigned)xq[k >> 1], yw = (unsigned)yq[k >> 1];
-                        const float gv0 = (k & 1) ? __uint_as_float(gw & 0xffff0000u) : __uint_as_float(gw << 16);
-                        const float xv = (k & 1) ? __uint_as_float(xw & 0xffff0000u) : __uint_as_float(xw << 16);
-                        const float yv = (k & 1) ? __uint_as_float(yw & 0xffff0000u) : __uint_as_float(yw << 16);
-                        const float gv = yv > 0.f ? gv0 : 0.f;
-                        s1[np >> 1][k] += gv;
-                        s2[np >> 1][k] += gv * (xv - mean[k]) * invs[k];
-                    }
+                    bn_bwd_sums8(q, xq, yq, sMean, c8, s1[np >> 1], s2[np >> 1]);
                 }
             }
         }
-        if (!EPI && p.stats) {                              // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS
-#pragma unroll
-            for (int nt = 0; nt < CA_NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float a = row_sum16(t1[nt][r]), bq = row_sum16(t2[nt][r]);
-                    if (li == 0) { sAcc[wave * 128 + nt * 16 + lg * 4 + r] += a; sAcc[wave * 128 + 64 + nt * 16 + lg * 4 + r] += bq; }
-                }
-        }
-        if constexpr (KW == 1) {
-            // before the barrier that publishes the other slot: every load of this wave has landed (belt and braces, see conv_stem.hip)
-#pragma unroll
-            for (int d = 0; d < CA_D; ++d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[d][0]), "+v"(A[d][1]), "+v"(A[d][2]), "+v"(A[d][3]));
-        }
+        if (!EPI && p.stats) acc_tile_sums<CA_NT>(sAcc, wave, li, lg, t1, t2);    // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS
+        // before the barrier that publishes the other slot: every load of this wave has landed (belt and braces, see conv_stem.hip)
+        if constexpr (KW == 1) ring_wait_all(A);
         lds_barrier();                                      // slot g & 1 consumed by every wave, slot (g + 1) & 1 complete
         ++g;
     }
-#pragma unroll
-    for (int d = 0; d < CA_D; ++d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[d][0]), "+v"(A[d][1]), "+v"(A[d][2]), "+v"(A[d][3]));
+    ring_wait_all(A);
     };
     if (kw == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
-    if (!EPI && p.bn_red) {
+    if (!EPI && p.bn_red) {                                 // (conv_stem_dgrad.hip's loop, written out: as a function of the two arrays it changed this kernel's code)
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -362,10 +297,7 @@ __device__ __forceinline__ void conv3x3a_body(const C3aP& p)
     float* const dst = p.bn_red ? p.bn_red : p.stats;
     if (!EPI && dst) {
         __syncthreads();
-        if (t < 128) {
-            const int which = t >> 6, c = t & 63;
-            bn_acc_add(dst, blockIdx.x, which, 64, c, (sAcc[t] + sAcc[128 + t]) + (sAcc[256 + t] + sAcc[384 + t]));
-        }
+        acc_to_replicas64(sAcc, dst, blockIdx.x, 64, t);
     }
 }
 

@@ -29,6 +29,7 @@
 // branch's tile is computed, the first stage of the next branch's tile is already arriving.
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 #include "grid_barrier.h"
 #include <type_traits>
 #include <algorithm>
@@ -40,11 +41,6 @@ namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int OOB = 0x7fffffff;
 constexpr int S3_MAXP = 4, S3_MAXST = 4;
 constexpr int S3_TAB = 112;                       // table entries (k-steps of a problem)
 constexpr int S3_TABB = S3_TAB * 16;              // bytes of one table slot (two slots: the next problem's table arrives early)
@@ -135,27 +131,6 @@ __device__ inline S3Bn desc_bn(int idx) {
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(S3Bn) / 4); ++i) u.w[i] = src[i];
     return u.v;
-}
-
-__device__ inline unsigned udiv24(unsigned n, unsigned d, float rcp) {      // n < 2^24
-    unsigned q = (unsigned)((float)n * rcp);
-    const int r = (int)(n - q * d);
-    if (r < 0) --q; else if (r >= (int)d) ++q;
-    return q;
-}
-__device__ inline void lds_barrier() {           // orders LDS traffic only: global stores keep draining across it
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, o);
-}
-__device__ inline float row_sum16(float v) {
-    v = dpp_add<0xB1>(v); v = dpp_add<0x4E>(v); v = dpp_add<0x141>(v); v = dpp_add<0x140>(v);
-    return v;
 }
 
 // ---- the tap table of a problem (built once per signature, s3_table_for) ---------------------------------------------------
@@ -299,16 +274,6 @@ __device__ inline bool flush_after(const S3Prob& p, int tau, int nblk) {
 // hardware writes zeros.  With two workgroups of four waves copying at once an instruction takes ~100 cycles: the CU's
 // 64 B / clk vector-memory path, not the issue, is the limit (84 KB per CU and tile pair = 1.3 k cycles).
 constexpr int S3_NIR = 8;                         // copy instructions per row at most (Wp * Sp <= 512 cells)
-
-__device__ __forceinline__ void dma16(unsigned lds_addr, int voff, const i32x4& desc, int soff) {
-    // M0 = LDS base of the 1 KB piece (written in the statement that uses it: the compiler does not preserve it)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds_addr), "v"(voff), "s"(desc), "s"(soff) : "memory");
-}
-__device__ inline i32x4 raw_desc(const void* base, int bytes) {           // raw buffer: stride 0, num_records in bytes
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffffu)),
-                 __builtin_amdgcn_readfirstlane(bytes), 0x00020000};
-}
 
 template <int NIR>
 __device__ __forceinline__ int s3_rows(const S3Prob& p, int s, int img0, int y0, int gofs, unsigned char* buf, int wave, int lane)
@@ -462,17 +427,10 @@ __device__ __forceinline__ void s3_finish(const S3Prob& p, f32x4 (*acc)[NT], flo
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
     // n0: first output channel of the tile's block among ALL groups' channels, climit: end of its group's channels
     const int tile_out = ((img0 * H + y0) * W) * p.Cout_tot * osz;
-    auto add_stats = [&](int nt, f32x4 v) {                 // BatchNorm statistics from the fp32 accumulators (see conv3x3.hip), two values per instruction
-        f32x2_ lo = {v[0], v[1]}, hi = {v[2], v[3]};
-        f32x2_& a0 = *reinterpret_cast<f32x2_*>(&s1[nt][0]); f32x2_& a1 = *reinterpret_cast<f32x2_*>(&s1[nt][2]);
-        f32x2_& q0 = *reinterpret_cast<f32x2_*>(&s2[nt][0]); f32x2_& q1 = *reinterpret_cast<f32x2_*>(&s2[nt][2]);
-        a0 += lo; a1 += hi;
-        q0 = __builtin_elementwise_fma(lo, lo, q0); q1 = __builtin_elementwise_fma(hi, hi, q1);
-    };
-    // PLAIN, two channel blocks at a time: v_permlane16_swap trades lane rows 1 <-> 0 and 3 <-> 2 between the packed registers of
-    // blocks a and b, after which a lane owns EIGHT consecutive channels (rows 0 / 2: block a's channels 0-7 / 8-15, rows 1 / 3:
-    // block b's) and stores 16 bytes -- 8 instead of 12 store instructions per pixel fragment row at NT = 3 (csrc/conv_pw.hip measured
-    // the same exchange: 8-byte pieces 32 bytes apart cost the write path twice the instructions for the same lines).
+    // (BatchNorm statistics from the fp32 ACCUMULATORS, see conv3x3.hip: sums_add of conv_lane.h on v itself, not on its rounded value)
+    // PLAIN, two channel blocks at a time through pack_swap8 (conv_lane.h): a lane owns EIGHT consecutive channels and stores 16 bytes
+    // -- 8 instead of 12 store instructions per pixel fragment row at NT = 3 (conv_pw.hip measured the exchange: 8-byte pieces 32 bytes
+    // apart cost the write path twice the instructions for the same lines).
     constexpr int NPAIR = (PLAIN && S3_WIDE_STORES) ? NT / 2 : 0;
 #pragma unroll
     for (int qq = 0; qq < KW; ++qq) {
@@ -484,10 +442,8 @@ __device__ __forceinline__ void s3_finish(const S3Prob& p, f32x4 (*acc)[NT], flo
                     for (int m = 0; m < MO; ++m) {
                         const int mt = qq * MO + m;
                         const f32x4 va = acc[mt][2 * np], vb = acc[mt][2 * np + 1];
-                        if (p.stats) { add_stats(2 * np, va); add_stats(2 * np + 1, vb); }
-                        const auto sx = __builtin_amdgcn_permlane16_swap(f2bf_pk(va[0], va[1]), f2bf_pk(vb[0], vb[1]), false, false);
-                        const auto sy = __builtin_amdgcn_permlane16_swap(f2bf_pk(va[2], va[3]), f2bf_pk(vb[2], vb[3]), false, false);
-                        const i32x4 q = {(int)sx[0], (int)sy[0], (int)sx[1], (int)sy[1]};
+                        if (p.stats) { sums_add(s1[2 * np], s2[2 * np], va); sums_add(s1[2 * np + 1], s2[2 * np + 1], vb); }
+                        const i32x4 q = pack_swap8(va, vb);
                         // outoff holds the lane's 4-channel run (lg * 8 bytes); the 8-channel run starts at block (lg & 1), channel (lg >> 1) * 8
                         const int off = outoff[mt] != OOB ? outoff[mt] - lg * 8 + (lg & 1) * 32 + (lg >> 1) * 16 : OOB;
                         __builtin_amdgcn_raw_buffer_store_b128(q, yr, off, tile_out + (n0 + 2 * np * 16) * 2, 0);
@@ -512,18 +468,16 @@ __device__ __forceinline__ void s3_finish(const S3Prob& p, f32x4 (*acc)[NT], flo
                     if (has_add) {
                         const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.addend), 0, p.y_bytes, 0x00020000);
                         const i32x2 aq = __builtin_amdgcn_raw_buffer_load_b64(ar, off, so, 0);
-                        v[0] += __uint_as_float((unsigned)aq.x << 16); v[1] += __uint_as_float((unsigned)aq.x & 0xffff0000u);
-                        v[2] += __uint_as_float((unsigned)aq.y << 16); v[3] += __uint_as_float((unsigned)aq.y & 0xffff0000u);
+                        v = add_bf16x4(v, aq);
                     }
                     if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
                     if (out_fp32) {
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), yr, off, so, 0);
                     } else {
-                        const i32x2 pk = {(int)f2bf_pk(v[0], v[1]), (int)f2bf_pk(v[2], v[3])};
-                        __builtin_amdgcn_raw_buffer_store_b64(pk, yr, off, so, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(pack_bf16x4(v), yr, off, so, 0);
                         if (p.stats) {
                             if (has_idle) { const float msk = off != OOB ? 1.f : 0.f; v *= msk; }
-                            add_stats(nt, v);
+                            sums_add(s1[nt], s2[nt], v);
                         }
                     }
                 }
@@ -542,14 +496,8 @@ __device__ __forceinline__ void s3_finish(const S3Prob& p, f32x4 (*acc)[NT], flo
                 s1[nt][r] = 0.f; s2[nt][r] = 0.f;
             }
         lds_barrier();
-        if (t < 2 * NT * 16) {
-            const int which = t / (NT * 16), c = t - which * (NT * 16);
-            const float v = (sScr[(0 * 2 + which) * (NT * 16) + c] + sScr[(1 * 2 + which) * (NT * 16) + c]) +
-                            (sScr[(2 * 2 + which) * (NT * 16) + c] + sScr[(3 * 2 + which) * (NT * 16) + c]);
-            // (a GLOBAL atomic: see dbg_ptr -- a FLAT one would serialise every later LDS wait of the kernel)
-            if (n0 + c < climit)
-                bn_acc_add(p.stats, bid, which, p.Cout_tot, n0 + c, v);
-        }
+        // (bn_acc_add is a GLOBAL atomic: see dbg_ptr -- a FLAT one would serialise every later LDS wait of the kernel)
+        scratch_to_replicas<NT>(sScr, p.stats, bid, p.Cout_tot, 0, n0, climit, t);
     }
 }
 
@@ -970,15 +918,11 @@ __device__ __forceinline__ void s3_bn_tail(const int nprob, const int rot, const
             for (int u = 0; u < U; ++u) {
                 const int c0 = min(cb + cgo[u], CMAX - 4);                 // (idle lanes read a valid slot)
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(&tab[c0]), sh = *reinterpret_cast<const f32x4*>(&tab[CMAX + c0]);
-                const float a[4] = {__uint_as_float((unsigned)xq[u].x << 16), __uint_as_float((unsigned)xq[u].x & 0xffff0000u),
-                                    __uint_as_float((unsigned)xq[u].y << 16), __uint_as_float((unsigned)xq[u].y & 0xffff0000u)};
-                float r[4] = {0.f, 0.f, 0.f, 0.f};
-                if (has_res) {
-                    r[0] = __uint_as_float((unsigned)rq[u].x << 16); r[1] = __uint_as_float((unsigned)rq[u].x & 0xffff0000u);
-                    r[2] = __uint_as_float((unsigned)rq[u].y << 16); r[3] = __uint_as_float((unsigned)rq[u].y & 0xffff0000u);
-                }
+                const f32x4 a = bf16x4_to_f32(xq[u]);
+                f32x4 r = {0.f, 0.f, 0.f, 0.f};
+                if (has_res) r = bf16x4_to_f32(rq[u]);
                 int mb = 0;
-                float o[4];
+                f32x4 o;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float v = __builtin_fmaf(a[j], sc[j], sh[j]);
@@ -986,8 +930,7 @@ __device__ __forceinline__ void s3_bn_tail(const int nprob, const int rot, const
                     mb |= (v > 0.f ? 1 : 0) << j;
                     o[j] = relu ? fmaxf(v, 0.f) : v;
                 }
-                const i32x2 pk = {(int)f2bf_pk(o[0], o[1]), (int)f2bf_pk(o[2], o[3])};
-                __builtin_amdgcn_raw_buffer_store_b64(pk, yr, off[u], 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(pack_bf16x4(o), yr, off[u], 0, 0);
                 if (has_mask) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)mb, mr, off[u] == OOB ? OOB : off[u] >> 3, 0, 0);
             }
         };

@@ -17,22 +17,11 @@
 // Activations fp32 NHWC; weights repacked (danet_conv_f32m_pack_weights) to [group][row / 16][k / 16][lane][4].
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 
 namespace {
 
 using namespace danet_conv;
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-
-constexpr int OOB = 0x7fffffff;
-
-__device__ inline unsigned udiv24(unsigned n, unsigned d, float rcp) {      // n < 2^24
-    unsigned q = (unsigned)((float)n * rcp);
-    const int r = (int)(n - q * d);
-    if (r < 0) --q; else if (r >= (int)d) ++q;
-    return q;
-}
 
 struct ConvF {
     const float* x; const float* w; const float* bias; float* y;

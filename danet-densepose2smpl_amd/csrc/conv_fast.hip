@@ -15,40 +15,16 @@
 // transposed gather with stride 1 or in parity-class mode; everything else stays on conv_igemm_kernel.
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 
 namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-
-__device__ inline unsigned udiv24(unsigned n, unsigned d, float rcp) {      // n < 2^24
-    unsigned q = (unsigned)((float)n * rcp);
-    const int r = (int)(n - q * d);
-    if (r < 0) --q; else if (r >= (int)d) ++q;
-    return q;
-}
-
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, o);
-}
-// sum over the 16 lanes of a DPP row, result in every lane (xor 1, xor 2, half-row mirror, row mirror)
-__device__ inline float row_sum16(float v) {
-    v = dpp_add<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v);     // row_half_mirror
-    v = dpp_add<0x140>(v);     // row_mirror
-    return v;
-}
-
-constexpr int OOB = 0x7fffffff;      // beyond every buffer (sizes are checked to be < 2^31 bytes)
-
 // Per-lane partial sums s1/s2[nt][r] of channels n0 + nt*16 + lg*4 + r (over the lane's pixels) -> summed over
 // the 16 pixel lanes (DPP), over the 4 waves (LDS), then one atomic per channel into replica blockIdx.x % 32 of
-// dst [32][2][Ctot].
+// dst [32][2][Ctot].  The (w0 + w1) + (w2 + w3) sum is scratch_to_replicas of conv_lane.h written out: through a pointer to the static
+// array the NT = 3 kernels compiled to other code.
 template <int NT>
 __device__ inline void channel_sums_to_replicas(float (*s1)[4], float (*s2)[4], float* __restrict__ dst, int Ctot, int cbase,
                                                 int n0, int Cg, int t, int li, int lg, int wave, int rep)
@@ -310,6 +286,7 @@ __device__ __forceinline__ void conv_fast_body(const ConvP& p, const int bx_, co
                 const i32x2 xq = __builtin_amdgcn_raw_buffer_load_b64(bxr, off, 0, 0);
                 i32x2 yq = {0x3f803f80, 0x3f803f80};                               // "positive" when there is no ReLU
                 if (p.bn_y) yq = __builtin_amdgcn_raw_buffer_load_b64(byr, off, 0, 0);
+                // (bf16x4_to_f32 of conv_lane.h written out: with f32x4 values this loop compiled to other code)
                 const float xv[4] = {__uint_as_float((unsigned)xq.x << 16), __uint_as_float((unsigned)xq.x & 0xffff0000u),
                                      __uint_as_float((unsigned)xq.y << 16), __uint_as_float((unsigned)xq.y & 0xffff0000u)};
                 const float yv[4] = {__uint_as_float((unsigned)yq.x << 16), __uint_as_float((unsigned)yq.x & 0xffff0000u),
@@ -342,14 +319,13 @@ __device__ __forceinline__ void conv_fast_body(const ConvP& p, const int bx_, co
             if (p.addend) {               // (bf16 outputs only, checked by the host) the residual branch's gradient, added before rounding
                 const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.addend), 0, (int)p.y_bytes, 0x00020000);
                 const i32x2 aq = __builtin_amdgcn_raw_buffer_load_b64(ar, ok ? outoff[mt] + cl * 2 : OOB, 0, 0);
-                v[0] += __uint_as_float((unsigned)aq.x << 16); v[1] += __uint_as_float((unsigned)aq.x & 0xffff0000u);
-                v[2] += __uint_as_float((unsigned)aq.y << 16); v[3] += __uint_as_float((unsigned)aq.y & 0xffff0000u);
+                v = add_bf16x4(v, aq);
             }
             if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             if (p.out_fp32) {
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), yr, ok ? outoff[mt] + cl * 4 : OOB, 0, 0);
             } else {
-                i32x2 pk = {(int)f2bf_pk(v[0], v[1]), (int)f2bf_pk(v[2], v[3])};
+                i32x2 pk = pack_bf16x4(v);
                 __builtin_amdgcn_raw_buffer_store_b64(pk, yr, ok ? outoff[mt] + cl * 2 : OOB, 0, 0);
             }
         }

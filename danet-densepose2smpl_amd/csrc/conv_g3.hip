@@ -20,14 +20,12 @@
 #include <cstdlib>
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 
 namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-constexpr int OOB = 0x7fffffff;
 constexpr int G3_KH = 7;                                      // k-steps of weight fragments held in registers at a time
 
 template <int CIN> struct G3Cfg;

@@ -20,27 +20,14 @@
 // interchangeable per problem (conv_pw_ok decides).
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 
 namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-
-constexpr int OOB = 0x7fffffff;
 constexpr int PW_MT = 4;                      // 16-pixel fragments per wave and tile (64 pixels)
 constexpr int PW_LDS_MAX = 64 * 1024;         // packed weights of a layer (two workgroups per compute unit)
-
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, o);
-}
-__device__ inline float row_sum16(float v) {
-    v = dpp_add<0xB1>(v); v = dpp_add<0x4E>(v); v = dpp_add<0x141>(v); v = dpp_add<0x140>(v);
-    return v;
-}
 
 struct PwP {
     const bf16_t* x; const bf16_t* w; const float* bias; void* y; float* stats; const bf16_t* addend;
@@ -139,14 +126,15 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(PwP p)
             if (p.addend) {
                 const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.addend), 0, p.y_bytes, 0x00020000);
                 const i32x2 aq = __builtin_amdgcn_raw_buffer_load_b64(ar, ok ? (pix[mt] * p.Cout + cl) * 2 : OOB, 0, 0);
-                v[0] += __uint_as_float((unsigned)aq.x << 16); v[1] += __uint_as_float((unsigned)aq.x & 0xffff0000u);
-                v[2] += __uint_as_float((unsigned)aq.y << 16); v[3] += __uint_as_float((unsigned)aq.y & 0xffff0000u);
+                v = add_bf16x4(v, aq);
             }
             if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             return v;
         };
         auto stat = [&](int nt, const i32x2& pk, bool ok) {               // statistics of the bf16-ROUNDED output, as conv_fast.hip takes them
             const float msk = ok ? 1.f : 0.f;
+            // (sums_add(bf16x4_to_f32(pk) * msk) of conv_lane.h written out: through it the instruction order changed and the 24 -> 64 layer
+            // over the 768 crops measured 3 % slower with statistics)
             f32x2_ lo = {__uint_as_float((unsigned)pk.x << 16) * msk, __uint_as_float((unsigned)pk.x & 0xffff0000u) * msk};
             f32x2_ hi = {__uint_as_float((unsigned)pk.y << 16) * msk, __uint_as_float((unsigned)pk.y & 0xffff0000u) * msk};
             f32x2_& a0 = *reinterpret_cast<f32x2_*>(&s1[nt][0]); f32x2_& a1 = *reinterpret_cast<f32x2_*>(&s1[nt][2]);
@@ -164,21 +152,17 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(PwP p)
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), yr, ok ? (pix[mt] * p.Cout + n0 + nt * 16 + lg * 4) * 4 : OOB, 0, 0);
                 }
         } else {
-            // bf16: two output blocks at a time leave as 16-byte stores.  v_permlane16_swap exchanges lane rows 1 <-> 0 and 3 <-> 2
-            // between two registers: from (block a: channels 4 lg .. + 3, block b: the same) a lane ends up with EIGHT consecutive
-            // channels -- rows 0 / 2 of block a (channels 0-7 / 8-15), rows 1 / 3 of block b -- instead of two 8-byte pieces
-            // 32 bytes apart (the write path handles a 64-lane store as 16-byte pieces per lane: half the instructions).
+            // bf16: two output blocks at a time leave as 16-byte stores through swap8 (conv_lane.h) -- the write path handles a 64-lane
+            // store as 16-byte pieces per lane: half the instructions of two 8-byte pieces 32 bytes apart.
 #pragma unroll
             for (int np = 0; np + 1 < NTB; np += 2)
 #pragma unroll
                 for (int mt = 0; mt < PW_MT; ++mt) {
                     bool oka, okb;
                     const f32x4 va = value(mt, np, oka), vb = value(mt, np + 1, okb);
-                    const i32x2 pa = {(int)f2bf_pk(va[0], va[1]), (int)f2bf_pk(va[2], va[3])}, pb = {(int)f2bf_pk(vb[0], vb[1]), (int)f2bf_pk(vb[2], vb[3])};
+                    const i32x2 pa = pack_bf16x4(va), pb = pack_bf16x4(vb);
                     if (p.stats) { stat(np, pa, oka); stat(np + 1, pb, okb); }
-                    const auto sx = __builtin_amdgcn_permlane16_swap((unsigned)pa.x, (unsigned)pb.x, false, false);
-                    const auto sy = __builtin_amdgcn_permlane16_swap((unsigned)pa.y, (unsigned)pb.y, false, false);
-                    const i32x4 q = {(int)sx[0], (int)sy[0], (int)sx[1], (int)sy[1]};
+                    const i32x4 q = swap8(pa, pb);
                     const int blk = np + (lg & 1), c8 = n0 + blk * 16 + (lg >> 1) * 8;      // the lane's eight channels after the exchange
                     const bool ok = pix[mt] >= 0 && c8 < p.Cout && nb0 + blk < NB;         // (Cout % 8 == 0 on this path, see conv_pw_ok)
                     __builtin_amdgcn_raw_buffer_store_b128(q, yr, ok ? (pix[mt] * p.Cout + c8) * 2 : OOB, 0, 0);
@@ -189,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(PwP p)
                 for (int mt = 0; mt < PW_MT; ++mt) {
                     bool ok;
                     const f32x4 v = value(mt, nt, ok);
-                    const i32x2 pk = {(int)f2bf_pk(v[0], v[1]), (int)f2bf_pk(v[2], v[3])};
+                    const i32x2 pk = pack_bf16x4(v);
                     if (p.stats) stat(nt, pk, ok);
                     __builtin_amdgcn_raw_buffer_store_b64(pk, yr, ok ? (pix[mt] * p.Cout + n0 + nt * 16 + lg * 4) * 2 : OOB, 0, 0);
                 }
@@ -216,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(PwP p)
         }
     }
     if (p.stats) {
-        // 16 pixel lanes (DPP) -> the waves of the group (LDS, behind the weights) -> one atomic per channel into replica blockIdx % ncopy
+        // 16 pixel lanes (DPP) -> the waves of the group (LDS, behind the weights; summed over the nsub waves of a group, not four: this unit's own second half) -> one atomic per channel into replica blockIdx % ncopy
         float* const sStat = reinterpret_cast<float*>(sW + (size_t)NB * nks * 1024);          // [4 waves][2][NTB * 16]
 #pragma unroll
         for (int nt = 0; nt < NTB; ++nt)

@@ -16,22 +16,15 @@
 // Several problems share a launch (the trainer queues weight gradients and flushes them in multi-problem launches).
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 
 namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(2))) unsigned v2u;
-constexpr int OOB = 0x7fffffff;
 constexpr int PWG_KS = 32;                    // pixels per MFMA k-step; a chunk = NKC k-steps (narrow layers: 2, so that a barrier round moves >= ~10 KB)
 constexpr int PWG_NPM = 16;                   // problems per launch
 constexpr int PWG_MAXPIECES = 4;              // 16-byte pieces per thread and tensor: 32 pixels x <= 256 channels
-
-__device__ inline v2u tr_read(unsigned lds_byte_addr) {
-    v2u r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(lds_byte_addr) : "memory");
-    return r;
-}
 
 struct PwgP {
     const bf16_t* x; const bf16_t* dy; float* part;

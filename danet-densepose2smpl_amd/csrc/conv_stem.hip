@@ -20,17 +20,13 @@
 //     (per lane over all tiles, flushed once per workgroup), 16-byte stores through v_permlane16_swap.
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 #include <type_traits>
 
 namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int OOB = 0x7fffffff;
 constexpr int ST_R = 7, ST_TAPS = 49, ST_TH = 8, ST_OW = 32, ST_NT = 4, ST_MT = 8;
 constexpr int ST_ROWS = 2 * ST_TH + 5;                      // 21 input rows of a tile
 constexpr int ST_CELLS = 35;                                // cells per plane: input columns -3 .. 66 in two planes
@@ -50,29 +46,6 @@ struct StemP {
     int nslab, ntiles, strips;                               // Cin / 16; B * strips; OH / 8
     int x_bytes, y_bytes;
 };
-
-__device__ __forceinline__ void dma16(unsigned lds_addr, int voff, const i32x4& desc, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds_addr), "v"(voff), "s"(desc), "s"(soff) : "memory");
-}
-__device__ inline i32x4 raw_desc(const void* base, int bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffffu)),
-                 __builtin_amdgcn_readfirstlane(bytes), 0x00020000};
-}
-__device__ inline void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, o);
-}
-__device__ inline float row_sum16(float v) {
-    v = dpp_add<0xB1>(v); v = dpp_add<0x4E>(v); v = dpp_add<0x141>(v); v = dpp_add<0x140>(v);
-    return v;
-}
 
 #ifndef ST_STRICT_COPIES
 #define ST_STRICT_COPIES 1
@@ -250,8 +223,7 @@ __device__ __forceinline__ void conv_stem_body(StemP p, const float* bias, int r
                 // before the barrier that publishes the other slot: every load of this copying wave has landed (belt and braces: the ring waits
                 // since the copies already imply it if loads return in order, which tools/experiments/dma_order.hip observes but no document
                 // at hand states; +1 %)
-#pragma unroll
-                for (int d = 0; d < D; ++d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[d][0]), "+v"(A[d][1]), "+v"(A[d][2]), "+v"(A[d][3]));
+                ring_wait_all(A);
             }
 #endif
             ST_CLK(c1);
@@ -271,8 +243,7 @@ __device__ __forceinline__ void conv_stem_body(StemP p, const float* bias, int r
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
         // the ring's refills past the tile's end are still in flight: nobody needs them, but the compiler knows nothing of them and
         // would hand their registers to the exchange / epilogue below
-#pragma unroll
-        for (int d = 0; d < D; ++d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[d][0]), "+v"(A[d][1]), "+v"(A[d][2]), "+v"(A[d][3]));
+        ring_wait_all(A);
         // ---- the two K halves of a pixel half meet in LDS: wave (pw, 0) finishes fragments 0-3, wave (pw, 1) fragments 4-7; two rounds of
         // two fragments x 4 blocks per wave (8 KB each, 32 KB in all) through the slot consumed last (the other one is receiving the next
         // tile's first slab)
@@ -330,36 +301,17 @@ __device__ __forceinline__ void conv_stem_body(StemP p, const float* bias, int r
                             for (int r = 0; r < 4; ++r) { va[r] = fmaxf(va[r], 0.f); vb[r] = fmaxf(vb[r], 0.f); }
                         }
                     }
-                    const i32x2 pa = {(int)f2bf_pk(va[0], va[1]), (int)f2bf_pk(va[2], va[3])}, pb = {(int)f2bf_pk(vb[0], vb[1]), (int)f2bf_pk(vb[2], vb[3])};
-                    if (!EPI && p.stats) {
-                        auto stat = [&](int nt, const i32x2& pk) {
-                            f32x2_ lo = {__uint_as_float((unsigned)pk.x << 16), __uint_as_float((unsigned)pk.x & 0xffff0000u)};
-                            f32x2_ hi = {__uint_as_float((unsigned)pk.y << 16), __uint_as_float((unsigned)pk.y & 0xffff0000u)};
-                            f32x2_& a0 = *reinterpret_cast<f32x2_*>(&s1[nt][0]); f32x2_& a1 = *reinterpret_cast<f32x2_*>(&s1[nt][2]);
-                            f32x2_& q0 = *reinterpret_cast<f32x2_*>(&s2[nt][0]); f32x2_& q1 = *reinterpret_cast<f32x2_*>(&s2[nt][2]);
-                            a0 += lo; a1 += hi;
-                            q0 = __builtin_elementwise_fma(lo, lo, q0); q1 = __builtin_elementwise_fma(hi, hi, q1);
-                        };
-                        stat(np, pa); stat(np + 1, pb);
+                    const i32x2 pa = pack_bf16x4(va), pb = pack_bf16x4(vb);
+                    if (!EPI && p.stats) {                  // statistics of the bf16-ROUNDED output
+                        sums_add(s1[np], s2[np], bf16x4_to_f32(pa)); sums_add(s1[np + 1], s2[np + 1], bf16x4_to_f32(pb));
                     }
-                    const auto sx = __builtin_amdgcn_permlane16_swap((unsigned)pa.x, (unsigned)pb.x, false, false);
-                    const auto sy = __builtin_amdgcn_permlane16_swap((unsigned)pa.y, (unsigned)pb.y, false, false);
-                    const i32x4 q = {(int)sx[0], (int)sy[0], (int)sx[1], (int)sy[1]};
-                    const int c8 = (np + (lg & 1)) * 16 + (lg >> 1) * 8;           // the lane's eight channels after the exchange (conv_pw.hip)
-                    __builtin_amdgcn_raw_buffer_store_b128(q, yr, (pix * p.Cout + c8) * 2, 0, 0);
+                    const int c8 = (np + (lg & 1)) * 16 + (lg >> 1) * 8;           // the lane's eight channels after the exchange
+                    __builtin_amdgcn_raw_buffer_store_b128(swap8(pa, pb), yr, (pix * p.Cout + c8) * 2, 0, 0);
                 }
             };
             body(KW * 4 + m);
         }
-        if (!EPI && p.stats) {                              // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS
-#pragma unroll
-            for (int nt = 0; nt < ST_NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float a = row_sum16(s1[nt][r]), bq = row_sum16(s2[nt][r]);
-                    if (li == 0) { sAcc[wave * 128 + nt * 16 + lg * 4 + r] += a; sAcc[wave * 128 + 64 + nt * 16 + lg * 4 + r] += bq; }
-                }
-        }
+        if (!EPI && p.stats) acc_tile_sums<ST_NT>(sAcc, wave, li, lg, s1, s2);    // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS
 #ifdef ST_DIAG
         ST_CLK(c0); de += c0 - c1;
 #endif
@@ -375,10 +327,7 @@ __device__ __forceinline__ void conv_stem_body(StemP p, const float* bias, int r
     if (kw == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
     if (!EPI && p.stats) {
         __syncthreads();
-        if (t < 128) {
-            const int which = t >> 6, c = t & 63;
-            bn_acc_add(p.stats, blockIdx.x, which, p.Cout, c, (sAcc[t] + sAcc[128 + t]) + (sAcc[256 + t] + sAcc[384 + t]));
-        }
+        acc_to_replicas64(sAcc, p.stats, blockIdx.x, p.Cout, t);
     }
 }
 

@@ -20,17 +20,13 @@
 //     outputs, kept in registers over all tiles and flushed once per workgroup (the gather kernel's bn_red contract).
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 #include <type_traits>
 
 namespace {
 
 using namespace danet_conv;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int OOB = 0x7fffffff;
 constexpr int SD_R = 7, SD_TH = 8, SD_JW = 32, SD_NT = 4, SD_MT = 8, SD_NSLAB = 4, SD_KS = 25;
 constexpr int SD_ROWS = SD_TH + 3, SD_CELLS = SD_JW + 3;     // 11 dy rows x 35 cells of a tile (halo: one before, two behind)
 constexpr int SD_ROWB = SD_CELLS * 32;                       // bytes per row of a 16-channel plane
@@ -53,29 +49,6 @@ struct StemDP {
     int ntiles, strips;
     int dy_bytes, dx_bytes;
 };
-
-__device__ __forceinline__ void dma16(unsigned lds_addr, int voff, const i32x4& desc, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds_addr), "v"(voff), "s"(desc), "s"(soff) : "memory");
-}
-__device__ inline i32x4 raw_desc(const void* base, int bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffffu)),
-                 __builtin_amdgcn_readfirstlane(bytes), 0x00020000};
-}
-__device__ inline void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, o);
-}
-__device__ inline float row_sum16(float v) {
-    v = dpp_add<0xB1>(v); v = dpp_add<0x4E>(v); v = dpp_add<0x141>(v); v = dpp_add<0x140>(v);
-    return v;
-}
 
 // k-steps of the classes (c = py * 2 + px) and their cut between the two K halves
 __device__ __host__ constexpr int sd_pairs(int c) { return c == 0 ? 5 : (c == 3 ? 8 : 6); }
@@ -231,10 +204,9 @@ __global__ __launch_bounds__(256, 1) void conv_stem_dgrad_kernel(StemDP p)
 #undef SD_KSTEP
             asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");               // (inline-asm MFMAs: the hazard recogniser does not see them)
 #ifdef SD_DRAIN
-#pragma unroll
-            for (int d = 0; d < SD_D; ++d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[d][0]), "+v"(A[d][1]), "+v"(A[d][2]), "+v"(A[d][3]));
+            ring_wait_all(A);
 #endif
-            // ---- the two K halves meet in LDS: wave (pw, 0) finishes fragments 0-3, wave (pw, 1) fragments 4-7
+            // ---- the two K halves meet in LDS: wave (pw, 0) finishes fragments 0-3, wave (pw, 1) fragments 4-7 (conv_stem.hip's exchange, written out: conv_lane.h says why)
 #pragma unroll
             for (int round = 0; round < 2; ++round) {
                 unsigned char* const mine = sR + wave * 8192 + lane * 16;
@@ -270,31 +242,15 @@ __global__ __launch_bounds__(256, 1) void conv_stem_dgrad_kernel(StemDP p)
                 for (int np = 0; np < SD_NT; np += 2) {
                     f32x4 va = acc[mt][np], vb = acc[mt][np + 1];
                     asm volatile("" : "+v"(va), "+v"(vb));
-                    const i32x2 pa = {(int)f2bf_pk(va[0], va[1]), (int)f2bf_pk(va[2], va[3])}, pb = {(int)f2bf_pk(vb[0], vb[1]), (int)f2bf_pk(vb[2], vb[3])};
-                    const auto sx = __builtin_amdgcn_permlane16_swap((unsigned)pa.x, (unsigned)pb.x, false, false);
-                    const auto sy = __builtin_amdgcn_permlane16_swap((unsigned)pa.y, (unsigned)pb.y, false, false);
-                    const i32x4 q = {(int)sx[0], (int)sy[0], (int)sx[1], (int)sy[1]};
-                    const int c8 = (np + (lg & 1)) * 16 + (lg >> 1) * 8;           // the lane's eight channels after the exchange (conv_pw.hip)
+                    const i32x4 q = pack_swap8(va, vb);
+                    const int c8 = (np + (lg & 1)) * 16 + (lg >> 1) * 8;           // the lane's eight channels after the exchange
                     const int off = (pix * 64 + c8) * 2;
                     __builtin_amdgcn_raw_buffer_store_b128(q, xr, off, 0, 0);
                     if (p.bn_red) {
                         const i32x4 xq = __builtin_amdgcn_raw_buffer_load_b128(bxr, off, 0, 0);
                         i32x4 yq = {0x3f803f80, 0x3f803f80, 0x3f803f80, 0x3f803f80};       // "positive" when there is no ReLU
                         if (p.bn_y) yq = __builtin_amdgcn_raw_buffer_load_b128(byr, off, 0, 0);
-                        const f32x4 m0 = *reinterpret_cast<const f32x4*>(sMean + c8), m1 = *reinterpret_cast<const f32x4*>(sMean + c8 + 4);
-                        const f32x4 i0 = *reinterpret_cast<const f32x4*>(sMean + 64 + c8), i1 = *reinterpret_cast<const f32x4*>(sMean + 64 + c8 + 4);
-                        const float mean[8] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-                        const float invs[8] = {i0[0], i0[1], i0[2], i0[3], i1[0], i1[1], i1[2], i1[3]};
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) {
-                            const unsigned gw = (unsigned)q[k >> 1], xw = (unsigned)xq[k >> 1], yw = (unsigned)yq[k >> 1];
-                            const float gv0 = (k & 1) ? __uint_as_float(gw & 0xffff0000u) : __uint_as_float(gw << 16);
-                            const float xv = (k & 1) ? __uint_as_float(xw & 0xffff0000u) : __uint_as_float(xw << 16);
-                            const float yv = (k & 1) ? __uint_as_float(yw & 0xffff0000u) : __uint_as_float(yw << 16);
-                            const float gv = yv > 0.f ? gv0 : 0.f;
-                            s1[np >> 1][k] += gv;
-                            s2[np >> 1][k] += gv * (xv - mean[k]) * invs[k];
-                        }
+                        bn_bwd_sums8(q, xq, yq, sMean, c8, s1[np >> 1], s2[np >> 1]);
                     }
                 }
             }
@@ -307,15 +263,12 @@ __global__ __launch_bounds__(256, 1) void conv_stem_dgrad_kernel(StemDP p)
             // the next tile's copies were requested ~48 k-steps ago and every ring wait since has counted them; before the barrier that
             // publishes the slot, wait for everything all the same (belt and braces: in-order return is observed -- tools/experiments/
             // dma_order.hip -- not documented; one refill latency per tile)
-#pragma unroll
-            for (int d = 0; d < SD_D; ++d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[d][0]), "+v"(A[d][1]), "+v"(A[d][2]), "+v"(A[d][3]));
+            ring_wait_all(A);
         }
         lds_barrier();                                      // slot g & 1 consumed by every wave, slot (g + 1) & 1 complete
         ++g;
     }
-    // the ring's refills past the last tile are still in flight
-#pragma unroll
-    for (int d = 0; d < SD_D; ++d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[d][0]), "+v"(A[d][1]), "+v"(A[d][2]), "+v"(A[d][3]));
+    ring_wait_all(A);                                       // the ring's refills past the last tile are still in flight
     };
     if (kw == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
     if (p.bn_red) {                                         // 16 pixel lanes (DPP) -> the workgroup's accumulators in LDS -> one replica
@@ -328,10 +281,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_dgrad_kernel(StemDP p)
                 if (li == 0) { sAcc[wave * 128 + c] += u; sAcc[wave * 128 + 64 + c] += v; }
             }
         __syncthreads();
-        if (t < 128) {
-            const int which = t >> 6, c = t & 63;
-            bn_acc_add(p.bn_red, blockIdx.x, which, 64, c, (sAcc[t] + sAcc[128 + t]) + (sAcc[256 + t] + sAcc[384 + t]));
-        }
+        acc_to_replicas64(sAcc, p.bn_red, blockIdx.x, 64, t);
     }
 }
 

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 
 namespace {
 
@@ -52,12 +53,6 @@ __device__ inline void store_transposed(bf16_t* dst, const uint4* raw) {
     }
 }
 
-__device__ inline unsigned udiv24(unsigned n, unsigned d, float rcp) {      // n < 2^24 (checked by the host)
-    unsigned q = (unsigned)((float)n * rcp);
-    const int r = (int)(n - q * d);
-    if (r < 0) --q; else if (r >= (int)d) ++q;
-    return q;
-}
 __device__ inline int sTap_dh(const WgradP& p, int tap) { const int tt = min(tap, p.R * p.S - 1); return (tt / p.S) * p.dil; }
 __device__ inline int sTap_dw(const WgradP& p, int tap) { const int tt = min(tap, p.R * p.S - 1); return (tt - (tt / p.S) * p.S) * p.dil; }
 
@@ -129,7 +124,6 @@ __device__ __forceinline__ void wgrad_body(const WgradP& p, const int bx, const 
     uint4 raw[NITEM_B + 1][4];
     // 32-bit byte offsets into buffer resources; out-of-image / out-of-range runs get an out-of-range offset and
     // load zeros (no address selects, no branches)
-    constexpr int OOB = 0x7fffffff;
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.dy + (size_t)g * p.Cout_g), 0, (int)(p.M * p.Cout * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.x + (size_t)g * p.Cin_g), 0, (int)((long)p.B * p.H * p.W * p.Cin * 2), 0x00020000);
     const float rc_ohw = 1.0f / (float)ohw, rc_ow = 1.0f / (float)p.OW;

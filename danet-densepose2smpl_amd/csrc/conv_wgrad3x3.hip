@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 #include "wgrad_finish.h"
 
 namespace {
@@ -40,14 +41,6 @@ struct Wg3P {
     long nchunks;                              // B * tiles_h * tiles_w
     long x_bytes, dy_bytes;                    // extents from the group / channel-block offset on (buffer resources)
 };
-
-typedef __attribute__((ext_vector_type(2))) unsigned v2u;
-
-__device__ inline v2u tr_read(unsigned lds_byte_addr) {
-    v2u r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(lds_byte_addr) : "memory");
-    return r;
-}
 
 // One workgroup's share of one problem: (bx of msplit pixel ranges, by = cout-block x cin-block, bz = group).
 // PAIR (round 6): 4 x 4 OUTPUT maps (the regressor tails: limb_net layer3 over the 768 part crops, /root/reference/models/module/res_module.py:393-464)
@@ -114,7 +107,6 @@ __device__ __forceinline__ void wgrad3x3_body(const Wg3P& p, const int bx, const
     // out-of-image halo pixels get an out-of-range offset and load zeros).
     constexpr int NPY = TH * TW * (BCO / 8), NPX = HH * HW * (BCI / 8);
     constexpr int NRY = (NPY + 255) / 256, NRX = (NPX + 255) / 256;
-    constexpr int OOB = 0x7fffffff;
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(dyg), 0, (int)p.dy_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(xg), 0, (int)p.x_bytes, 0x00020000);
     int yrel[NRY], xrel[NRX], xhy[NRX], xhx[NRX];

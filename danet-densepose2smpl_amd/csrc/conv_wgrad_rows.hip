@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "conv_common.h"
+#include "conv_lane.h"
 #include "wgrad_finish.h"
 
 namespace {
@@ -32,14 +33,6 @@ struct WgRP {
     int tiles_h, tiles_w, msplit, nchunks;
     long x_bytes, dy_bytes;
 };
-
-typedef __attribute__((ext_vector_type(2))) unsigned v2u;
-
-__device__ inline v2u tr_read(unsigned lds_byte_addr) {
-    v2u r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(lds_byte_addr) : "memory");
-    return r;
-}
 
 // grid: (msplit pixel ranges, R * cout-blocks * cin-blocks, groups)
 template <int CT, int NI, int S, int ST>
@@ -82,7 +75,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_kernel(WgRP p)
 
     constexpr int NPY = TH * TW * (BCO / 8), NPX = TH * HWc * (BCI / 8);
     constexpr int NRY = (NPY + 255) / 256, NRX = (NPX + 255) / 256;
-    constexpr int OOB = 0x7fffffff;
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(dyg), 0, (int)p.dy_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(xg), 0, (int)p.x_bytes, 0x00020000);
     int yrel[NRY], ylds[NRY], xrel[NRX], xlds[NRX], xhy[NRX], xhx[NRX];

@@ -336,6 +336,52 @@ def _wgrad_ref(x, w, gy):
     return wr.grad
 
 
+@pytest.mark.parametrize('shape', [(48, 32, 20, 12, 3), (80, 48, 16, 16, 5), (64, 64, 16, 16, 24)], ids=lambda s: 'x'.join(map(str, s)))
+def test_lds_tile_3x3_data_gradient_fused_batchnorm_backward_sums(shape):
+    """conv3x3.hip's data gradient with the fused BatchNorm-backward sums of the BatchNorm that produced the convolution's input: gated
+    by that BatchNorm's bf16 output (mode 0), by its bit mask (mode 2: one byte per four channels, bit r = channel 4 k + r passed, as
+    norm_act.hip writes it) and without a ReLU -- the sums against their recomputation from the kernel's own rounded output (the oracle
+    and bounds of the conv3x3a.hip test below), the data gradient bit for bit the one without sums, and both against the gather kernel."""
+    from danet_densepose2smpl_amd import conv as dconv, _lib
+    L = _lib.lib()
+    Cin, Cout, H, W, B = shape                                  # the forward convolution's: dx has Cin channels
+    g = torch.Generator().manual_seed(Cin + 3 * H)
+    gy = dconv.nhwc_bf16(torch.randn(B, Cout, H, W, generator=g).cuda())
+    w = (torch.randn(Cout, Cin, 3, 3, generator=g) / np.sqrt(9 * Cout / 4)).bfloat16().float().cuda()
+    wpt = dconv.pack_weight(w, 1, 1)
+    bn_x = dconv.nhwc_bf16(torch.randn(B, Cin, H, W, generator=g).cuda())
+    bn_y = dconv.nhwc_bf16(torch.randn(B, Cin, H, W, generator=g).cuda())
+    saved = torch.cat([torch.randn(Cin, generator=g) * 0.2, torch.rand(Cin, generator=g) + 0.5]).cuda()
+    bits = (bn_y.permute(0, 2, 3, 1) > 0).view(B, H, W, Cin // 4, 4).to(torch.int32)
+    mask = (bits * torch.tensor([1, 2, 4, 8], dtype=torch.int32, device='cuda')).sum(dim=-1).to(torch.uint8).contiguous()
+    xhat = (bn_x.float() - saved[:Cin].view(1, -1, 1, 1)) * saved[Cin:].view(1, -1, 1, 1)
+    nred = L.danet_bn_ws_floats(Cin)
+    dims = (B, H, W, Cout, H, W, Cin, 3, 3, 1, 1, 1, 1)
+
+    def run(bn):
+        return dconv._conv_fwd_raw(gy, wpt, None, *dims, True, False, False, None, bn)
+    with _lib.knobs(c3s_enable=0):
+        assert L.danet_conv_forward_kernel(*dims, 1, 0) % 10 == 2                       # conv3x3_tile_kernel
+        gx = run(None)
+        ref = F.conv_transpose2d(gy.float(), w, None, 1, 1)
+        assert (gx.float() - ref).abs().max().item() <= 1e-2 * ref.abs().max().item()
+        for gate_t, mode in ((bn_y, 0), (mask, 2), (None, 0)):
+            red = torch.zeros(nred, device='cuda')
+            gxb = run((bn_x, gate_t, saved, red, mode))
+            with _lib.knobs(c3_enable=0):
+                red2 = torch.zeros(nred, device='cuda')
+                gx2 = run((bn_x, bn_y if gate_t is not None else None, saved, red2, 0))   # the gather kernel on the same operands
+            torch.cuda.synchronize()
+            assert torch.equal(gxb, gx), mode
+            gf = gx.float() * ((bn_y.float() > 0).float() if gate_t is not None else 1.0)
+            s1, s2 = gf.sum(dim=(0, 2, 3)), (gf * xhat).sum(dim=(0, 2, 3))
+            st, st2 = dconv.bn_sums_total(red, Cin), dconv.bn_sums_total(red2, Cin)
+            tol1, tol2 = 2e-3 * gf.abs().sum(dim=(0, 2, 3)).max().item(), 2e-3 * (gf * xhat).abs().sum(dim=(0, 2, 3)).max().item()
+            assert (st[0] - s1).abs().max().item() <= tol1 and (st[1] - s2).abs().max().item() <= tol2, mode
+            assert (gx.float() - gx2.float()).abs().max().item() <= 1e-2 * ref.abs().max().item()
+            assert (st[0] - st2[0]).abs().max().item() <= 4 * tol1 and (st[1] - st2[1]).abs().max().item() <= 4 * tol2, mode
+
+
 def test_lds_tile_3x3_bias_fp32_relu_and_lockstep_launch():
     """Head-style epilogue (bias, fp32 output) on the LDS-tile kernel, and the four HRNet branches in ONE launch
     (forward and data gradient) against their separate launches."""
