@@ -490,9 +490,28 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     bn_bwd_apply_body(blockIdx.x, dy, x, y, fm, saved, gamma, red, Cst, inv_count, relu, dx, dres, dparam, mask_mode, mask, beta);
 }
 
-// Up to 4 independent BatchNorms in one launch (the HRNet branches advance in lockstep: nn.multi_batch_norm): the
+// The problem of a multi-problem launch that this workgroup belongs to: problem i owns the workgroups start[i] .. start[i + 1] - 1.
+template <typename Multi>
+__device__ __forceinline__ int problem_of(const Multi& m) {
+    int i = 0;
+    while (i + 1 < m.n && (int)blockIdx.x >= m.start[i + 1]) ++i;
+    return i;
+}
+
+// Up to NBM independent BatchNorms in one launch (the HRNet branches advance in lockstep: nn.multi_batch_norm): the
 // small branches' launches are dominated by the per-launch floor, one launch over all of them is not.
 constexpr int NBM = 12;
+// The jobs of the multi-tensor entry points, as the caller lays them out on the host (include/danet_hip.h repeats the two lists); the
+// single-tensor entries build one from their arguments.  C <= 1024 per job in the multi entries.
+//  sums_state / red_state: 1 = sums / red is zeroed scratch (this unit runs the statistics / reduction pass), 2 = already accumulated
+//      by the producer conv's epilogue / the consumer conv's data-gradient epilogue
+//  mask: NULL, or M*C/4 bytes: the forward writes the ReLU gate of y there (bit j of byte i = channel 4i+j positive), the backward
+//      reads it under mask_mode 1 (mask_mode: see ldmask above)
+struct BnFwdJob { const void* x; const void* res; void* y; const float* gamma; const float* beta; float* running_mean; float* running_var;
+                  float* saved; float* sums; void* mask; int64_t M; int C, sums_state, relu; };
+struct BnBwdJob { const void* dy; const void* x; const void* y; const float* gamma; const float* saved; void* dx; void* dres; float* dparam;
+                  float* red; const float* beta; const void* mask; int64_t M; int C, red_state, relu, mask_mode; };
+// ... and what a kernel gets for one channel slab of one job (bn_fwd_fill / bn_bwd_fill below)
 struct BnFwdOne {
     const elem_t* x; const elem_t* res; elem_t* y; const bn_acc_t* sums; const float* gamma; const float* beta;
     float* running_mean; float* running_var; float* saved; unsigned char* mask; FlatMap fm; int C; float inv_count, unbias; int relu;
@@ -500,8 +519,7 @@ struct BnFwdOne {
 struct BnFwdMulti { BnFwdOne a[NBM]; int start[NBM + 1]; int n; float momentum, eps; int mode; };
 __global__ __launch_bounds__(256) void bn_apply_multi_kernel(BnFwdMulti m)
 {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.start[i + 1]) ++i;
+    const int i = problem_of(m);
     const BnFwdOne& a = m.a[i];
     bn_apply_body(blockIdx.x - m.start[i], a.x, a.res, a.y, a.fm, a.sums, a.gamma, a.beta, a.running_mean, a.running_var, a.saved,
                   a.C, a.inv_count, a.unbias, m.momentum, m.eps, m.mode, a.relu, a.mask);
@@ -514,16 +532,14 @@ struct BnBwdOne {
 struct BnBwdMulti { BnBwdOne a[NBM]; int start[NBM + 1]; int n; };
 __global__ __launch_bounds__(256) void bn_bwd_reduce_multi_kernel(BnBwdMulti m)
 {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.start[i + 1]) ++i;
+    const int i = problem_of(m);
     const BnBwdOne& a = m.a[i];
     if (a.have_red) return;                              // already reduced by the consumer conv's data-gradient epilogue
     bn_bwd_reduce_body(blockIdx.x - m.start[i], a.dy, a.x, a.y, a.fm, a.saved, a.C, a.relu, a.red, a.mask_mode, a.mask, a.gamma, a.beta);
 }
 __global__ __launch_bounds__(256) void bn_bwd_apply_multi_kernel(BnBwdMulti m)
 {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.start[i + 1]) ++i;
+    const int i = problem_of(m);
     const BnBwdOne& a = m.a[i];
     bn_bwd_apply_body(blockIdx.x - m.start[i], a.dy, a.x, a.y, a.fm, a.saved, a.gamma, a.red, a.C, a.inv_count, a.relu, a.dx, a.dres, a.dparam,
                       a.mask_mode, a.mask, a.beta);
@@ -588,7 +604,7 @@ struct BnOnePass { BnBwdOne a[NBM]; int start[NBM + 1]; int n; unsigned* bar; in
 template <int NV>
 __global__ __launch_bounds__(256, 2) void bn_bwd_onepass_kernel(BnOnePass m)
 {
-    int ji = 0;
+    int ji = 0;                                 // (problem_of, written out: DESIGN.md 3.2)
     while (ji + 1 < m.n && (int)blockIdx.x >= m.start[ji + 1]) ++ji;
     const BnBwdOne& a = m.a[ji];
     const int bid = blockIdx.x - m.start[ji];
@@ -784,14 +800,18 @@ __global__ __launch_bounds__(256) void sum_relu_kernel(SumP p, elem_t* __restric
 {
     sum_relu_body(p, y, relu, blockIdx.x, gridDim.x);
 }
-// The fuse sums of ONE HighResolutionModule (up to four outputs, one per branch) in one launch: they are independent of each other
+// The fuse sums of ONE HighResolutionModule (up to NSM outputs, one per branch) in one launch: they are independent of each other
 // and the low-resolution ones are far too small to fill a launch of their own (4.9 - 11.6 us each at B = 32, mostly launch).
 constexpr int NSM = 4;
+// The jobs of the multi-problem entry points on the host (include/danet_hip.h repeats the two lists): one fuse output each.
+//  forward:  y = [relu](sum of nterms <= 4 terms, term t up-sampled by 2^shifts[t])
+//  backward: d[s] (NULL: none) receives the gradient of the terms that entered the sum with shift s
+struct SumFwdJob { const void* terms[4]; int shifts[4]; int nterms, B, H, W, C, relu; void* y; };
+struct SumBwdJob { const void* gy; const void* y; int B, H, W, C, relu; void* d[4]; };
 struct SumMulti { SumP p[NSM]; elem_t* y[NSM]; int relu[NSM]; int start[NSM + 1]; int n; };
 __global__ __launch_bounds__(256) void sum_relu_multi_kernel(SumMulti m)
 {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.start[i + 1]) ++i;
+    const int i = problem_of(m);
     sum_relu_body(m.p[i], m.y[i], m.relu[i], blockIdx.x - m.start[i], m.start[i + 1] - m.start[i]);
 }
 
@@ -888,8 +908,7 @@ struct SumBwdMultiOne { const elem_t* gy; const elem_t* y; int B, H, W, C, smax,
 struct SumBwdMulti { SumBwdMultiOne a[NSM]; int start[NSM + 1]; int n; };
 __global__ __launch_bounds__(256) void sum_relu_bwd_all_multi_kernel(SumBwdMulti m)
 {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.start[i + 1]) ++i;
+    const int i = problem_of(m);
     const SumBwdMultiOne& a = m.a[i];
     sum_relu_bwd_all_body(a.gy, a.y, a.B, a.H, a.W, a.C, a.smax, a.relu, a.out, blockIdx.x - m.start[i], m.start[i + 1] - m.start[i]);
 }
@@ -937,6 +956,68 @@ inline int wide_slabs(int C) {
     static const bool off = getenv("DANET_BN_WIDE") && atoi(getenv("DANET_BN_WIDE")) == 0;       // A-B timing
     return !off && C > SLAB && C % SLAB == 0 && C / SLAB <= 12 ? C / SLAB : 1;
 }
+inline int slab_width(int C, int c0) { return C - c0 < SLAB ? C - c0 : SLAB; }
+// every slab of a [M, C] tensor maps: what an entry that walks the slabs asks before it enqueues anything
+inline bool slabs_map(int64_t M, int C) {
+    FlatMap fm; int grid;
+    for (int c0 = 0; c0 < C; c0 += SLAB)
+        if (make_map(M, C, c0, slab_width(C, c0), &fm, &grid) != 0) return false;
+    return true;
+}
+
+// What every entry checks of a job (the entries add their own conditions and their own texts) ...
+inline bool bn_fwd_ok(const BnFwdJob& j) { return j.x && j.y && j.M > 0 && j.C > 0; }
+inline bool bn_bwd_ok(const BnBwdJob& j) { return j.dy && j.x && j.dx && j.saved && j.red && j.M > 0 && j.C > 0; }
+// ... and the ReLU gate has its input: mask_mode 0 needs y, 1 the forward's byte mask, 2 (recomputed from x) no residual
+inline bool bn_gate_ok(const BnBwdJob& j) {
+    return !j.relu || (j.mask_mode == 0 && j.y) || (j.mask_mode == 1 && j.mask) || (j.mask_mode == 2 && !j.dres);
+}
+
+// The kernels' view of the slab [c0, c0 + Cs) of a job and its grid; non-zero: make_map refuses the tensor.  The [C] and [2][C]
+// per-channel buffers are addressed as base + c0 with the full width C as their stride.
+inline int bn_fwd_fill(const BnFwdJob& j, int c0, int Cs, BnFwdOne* a, int* grid) {
+    if (make_map(j.M, j.C, c0, Cs, &a->fm, grid) != 0) return -1;
+    a->x = (const elem_t*)j.x; a->res = (const elem_t*)j.res; a->y = (elem_t*)j.y; a->sums = j.sums ? (const bn_acc_t*)j.sums + c0 : nullptr;
+    a->gamma = j.gamma ? j.gamma + c0 : nullptr; a->beta = j.beta ? j.beta + c0 : nullptr;
+    a->running_mean = j.running_mean ? j.running_mean + c0 : nullptr; a->running_var = j.running_var ? j.running_var + c0 : nullptr;
+    a->saved = j.saved ? j.saved + c0 : nullptr; a->mask = (unsigned char*)j.mask; a->C = j.C;
+    a->inv_count = 1.0f / (float)j.M; a->unbias = j.M > 1 ? (float)j.M / (float)(j.M - 1) : 1.f; a->relu = j.relu;
+    return 0;
+}
+inline int bn_bwd_fill(const BnBwdJob& j, int c0, int Cs, BnBwdOne* a, int* grid) {
+    if (make_map(j.M, j.C, c0, Cs, &a->fm, grid) != 0) return -1;
+    a->dy = (const elem_t*)j.dy; a->x = (const elem_t*)j.x; a->y = (const elem_t*)j.y; a->saved = j.saved + c0; a->gamma = j.gamma ? j.gamma + c0 : nullptr;
+    a->red = (bn_acc_t*)j.red + c0; a->dx = (elem_t*)j.dx; a->dres = (elem_t*)j.dres; a->dparam = j.dparam ? j.dparam + c0 : nullptr; a->C = j.C;
+    a->inv_count = 1.0f / (float)j.M; a->relu = j.relu; a->have_red = j.red_state == 2; a->beta = j.beta ? j.beta + c0 : nullptr;
+    a->mask = (const unsigned char*)j.mask; a->mask_mode = j.mask_mode;
+    return 0;
+}
+inline void bn_stats_launch(const BnFwdOne& a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(256), 0, st, a.x, a.fm, const_cast<bn_acc_t*>(a.sums), a.C);
+}
+
+// grid of the flat fuse-sum kernels: one lane per channel vector, at most 4096 workgroups
+inline int flat_grid(long nvec) { const long blocks = (nvec + 255) / 256; return (int)(blocks > 4096 ? 4096 : blocks); }
+// One fuse output's terms into the kernel's view and its grid; returns the first term that is missing, has a negative shift or does
+// not divide H x W (-1: none).
+inline int sum_fill(const void* const* terms, const int* shifts, int nterms, int B, int H, int W, int C, SumP* p, int* grid) {
+    p->nterms = nterms; p->B = B; p->H = H; p->W = W; p->C = C;
+    for (int t = 0; t < 4; ++t) { p->in[t] = t < nterms ? (const elem_t*)terms[t] : nullptr; p->shift[t] = t < nterms ? shifts[t] : 0; }
+    *grid = flat_grid((long)B * H * W * (C / VW));
+    for (int t = 0; t < nterms; ++t)
+        if (!(p->in[t] && p->shift[t] >= 0 && (H % (1 << p->shift[t])) == 0 && (W % (1 << p->shift[t])) == 0)) return t;
+    return -1;
+}
+// One fuse output's gradients: the largest requested shift and the grid over its windows; false: nothing requested, ReLU without y,
+// or H x W is not made of whole windows.
+inline bool sum_bwd_plan(const SumBwdJob& j, int* smax, int* grid) {
+    int s = -1;
+    for (int s_ = 0; s_ < 4; ++s_) if (j.d[s_]) s = s_;
+    if (!(j.gy && (!j.relu || j.y) && j.C % VW == 0 && s >= 0 && j.H % (1 << s) == 0 && j.W % (1 << s) == 0)) return false;
+    *smax = s;
+    *grid = flat_grid((long)j.B * (j.H >> s) * (j.W >> s) * (j.C / VW));
+    return true;
+}
 
 }  // namespace
 
@@ -946,37 +1027,34 @@ extern "C" int NA_NAME(danet_bn_forward)(const void* x, const void* res, void* y
                                 void* relu_mask, void* stream)
 {
     DANET_ENTER();
-    DANET_CHECK_ARG(x && y && M > 0 && C > 0, "bn_forward: bad arguments");
+    // ws_is_zero == 2: the statistics were accumulated by the conv epilogue
+    const BnFwdJob j = {x, res, y, gamma, beta, running_mean, running_var, saved, sums_ws, relu_mask, M, C, ws_is_zero == 2 ? 2 : 1, relu};
+    DANET_CHECK_ARG(bn_fwd_ok(j), "bn_forward: bad arguments");
     DANET_CHECK_ARG(training ? (saved && sums_ws) : (running_mean && running_var), "bn_forward: missing buffers");
     DANET_CHECK_ARG(C % VW == 0, "bn_forward: C=%d must be a multiple of %d", C, VW);
 #ifdef NA_F32
     DANET_CHECK_ARG(!training || ws_is_zero != 2, "bn_forward_f32: the fp32 statistics are shifted sums (bn_stats_kernel): no pre-accumulated sums");
 #endif
+    DANET_CHECK_ARG(slabs_map(M, C), "bn_forward: C=%d (M=%ld) unsupported: channels must be a multiple of 4 and the tensor < 2 GB", C, (long)M);
     hipStream_t st = (hipStream_t)stream;
     if (training && !ws_is_zero) {
         hipError_t e = danet::zero_async(sums_ws, sizeof(bn_acc_t) * 2 * C * NCOPY, st);
         if (e != hipSuccess) return danet::fail(DANET_ERR_HIP, "bn_forward: memset: %s", hipGetErrorString(e));
     }
-    const float inv = 1.0f / (float)M, unbias = M > 1 ? (float)M / (float)(M - 1) : 1.f;
-    if (wide_slabs(C) > 1) {
+    const bool stats = training && j.sums_state == 1;
+    const int mode = training ? 0 : 1;
+    int grid = 0;                                  // (the fills below cannot fail: slabs_map has walked the same slabs)
+    if (const int ns = wide_slabs(C); ns > 1) {
         // a tensor wider than one slab is C / SLAB independent BatchNorms over the same rows: ONE launch over all of them (round 6: the
         // grouped layer4 of the limb branch, [32, 2, 2, 3072], took three 11 us launches per BatchNorm in a stretch of the step where
         // nothing else runs)
-        const int ns = wide_slabs(C);
-        BnFwdMulti m; m.n = ns; m.momentum = momentum; m.eps = eps; m.mode = training ? 0 : 1; m.start[0] = 0;
+        BnFwdMulti m; m.n = ns; m.momentum = momentum; m.eps = eps; m.mode = mode; m.start[0] = 0;
         for (int s = 0; s < ns; ++s) {
-            const int c0 = s * SLAB;
-            BnFwdOne& a = m.a[s];
-            int grid;
-            DANET_CHECK_ARG(make_map(M, C, c0, SLAB, &a.fm, &grid) == 0, "bn_forward: C=%d (M=%ld) unsupported: channels must be a multiple of 4 and the tensor < 2 GB", C, (long)M);
-            if (training && ws_is_zero != 2) {
-                hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(256), 0, st, (const elem_t*)x, a.fm, (bn_acc_t*)sums_ws + c0, C);
+            bn_fwd_fill(j, s * SLAB, SLAB, &m.a[s], &grid);
+            if (stats) {
+                bn_stats_launch(m.a[s], grid, st);
                 DANET_CHECK_LAUNCH("bn_stats_kernel");
             }
-            a.x = (const elem_t*)x; a.res = (const elem_t*)res; a.y = (elem_t*)y; a.sums = sums_ws ? (const bn_acc_t*)sums_ws + c0 : nullptr;
-            a.gamma = gamma ? gamma + c0 : nullptr; a.beta = beta ? beta + c0 : nullptr;
-            a.running_mean = running_mean ? running_mean + c0 : nullptr; a.running_var = running_var ? running_var + c0 : nullptr;
-            a.saved = saved ? saved + c0 : nullptr; a.mask = (unsigned char*)relu_mask; a.C = C; a.inv_count = inv; a.unbias = unbias; a.relu = relu;
             m.start[s + 1] = m.start[s] + grid;
         }
         hipLaunchKernelGGL(bn_apply_multi_kernel, dim3(m.start[ns]), dim3(256), 0, st, m);
@@ -984,18 +1062,14 @@ extern "C" int NA_NAME(danet_bn_forward)(const void* x, const void* res, void* y
         return DANET_OK;
     }
     for (int c0 = 0; c0 < C; c0 += SLAB) {
-        const int Cs = C - c0 < SLAB ? C - c0 : SLAB;
-        FlatMap fm; int grid;
-        DANET_CHECK_ARG(make_map(M, C, c0, Cs, &fm, &grid) == 0, "bn_forward: C=%d (M=%ld) unsupported: channels must be a multiple of 4 and the tensor < 2 GB", C, (long)M);
-        // per-slab views of the per-channel buffers: [2][C] buffers are addressed as base+c0 with stride C
-        if (training && ws_is_zero != 2) {          // ws_is_zero == 2: the statistics were accumulated by the conv epilogue
-            hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(256), 0, st, (const elem_t*)x, fm, (bn_acc_t*)sums_ws + c0, C);
+        BnFwdOne a;
+        bn_fwd_fill(j, c0, slab_width(C, c0), &a, &grid);
+        if (stats) {
+            bn_stats_launch(a, grid, st);
             DANET_CHECK_LAUNCH("bn_stats_kernel");
         }
-        hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, st, (const elem_t*)x, (const elem_t*)res, (elem_t*)y, fm,
-                           sums_ws ? (const bn_acc_t*)sums_ws + c0 : nullptr, gamma ? gamma + c0 : nullptr, beta ? beta + c0 : nullptr,
-                           running_mean ? running_mean + c0 : nullptr, running_var ? running_var + c0 : nullptr,
-                           saved ? saved + c0 : nullptr, C, inv, unbias, momentum, eps, training ? 0 : 1, relu, (unsigned char*)relu_mask);
+        hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, st, a.x, a.res, a.y, a.fm, a.sums, a.gamma, a.beta, a.running_mean,
+                           a.running_var, a.saved, a.C, a.inv_count, a.unbias, momentum, eps, mode, a.relu, a.mask);
         DANET_CHECK_LAUNCH("bn_apply_kernel");
     }
     return DANET_OK;
@@ -1013,30 +1087,25 @@ extern "C" int NA_NAME(danet_bn_backward)(const void* dy, const void* x, const v
                                  int mask_mode, const void* relu_mask, const float* beta, void* stream)
 {
     DANET_ENTER();
-    DANET_CHECK_ARG(dy && x && dx && saved && red_ws && M > 0 && C > 0, "bn_backward: bad arguments");
-    DANET_CHECK_ARG(!relu || (mask_mode == 0 && y) || (mask_mode == 1 && relu_mask) || (mask_mode == 2 && !dres),
-                    "bn_backward: ReLU gate: mask_mode 0 needs y, 1 the forward's byte mask, 2 (recompute from x) no residual");
+    // ws_is_zero == 2: the sums were accumulated by the consumer conv's dgrad epilogue
+    const BnBwdJob j = {dy, x, y, gamma, saved, dx, dres, dparam, red_ws, beta, relu_mask, M, C, ws_is_zero == 2 ? 2 : 1, relu, mask_mode};
+    DANET_CHECK_ARG(bn_bwd_ok(j), "bn_backward: bad arguments");
+    DANET_CHECK_ARG(bn_gate_ok(j), "bn_backward: ReLU gate: mask_mode 0 needs y, 1 the forward's byte mask, 2 (recompute from x) no residual");
     DANET_CHECK_ARG(C % VW == 0, "bn_backward: C=%d must be a multiple of %d", C, VW);
+    DANET_CHECK_ARG(slabs_map(M, C), "bn_backward: C=%d (M=%ld) unsupported: channels must be a multiple of 4 and the tensor < 2 GB", C, (long)M);
     hipStream_t st = (hipStream_t)stream;
     if (!ws_is_zero) {
         hipError_t e = danet::zero_async(red_ws, sizeof(bn_acc_t) * 2 * C * NCOPY, st);
         if (e != hipSuccess) return danet::fail(DANET_ERR_HIP, "bn_backward: memset: %s", hipGetErrorString(e));
     }
-    if (wide_slabs(C) > 1) {                       // as in bn_forward: the slabs of a wide tensor in one launch per phase
-        const int ns = wide_slabs(C);
+    int grid = 0;                                  // (the fills below cannot fail: slabs_map has walked the same slabs)
+    if (const int ns = wide_slabs(C); ns > 1) {    // as in bn_forward: the slabs of a wide tensor in one launch per phase
         BnBwdMulti m; m.n = ns; m.start[0] = 0;
         for (int s = 0; s < ns; ++s) {
-            const int c0 = s * SLAB;
-            BnBwdOne& a = m.a[s];
-            int grid;
-            DANET_CHECK_ARG(make_map(M, C, c0, SLAB, &a.fm, &grid) == 0, "bn_backward: C=%d (M=%ld) unsupported: channels must be a multiple of 4 and the tensor < 2 GB", C, (long)M);
-            a.dy = (const elem_t*)dy; a.x = (const elem_t*)x; a.y = (const elem_t*)y; a.saved = saved + c0; a.gamma = gamma ? gamma + c0 : nullptr;
-            a.red = (bn_acc_t*)red_ws + c0; a.dx = (elem_t*)dx; a.dres = (elem_t*)dres; a.dparam = dparam ? dparam + c0 : nullptr; a.C = C;
-            a.inv_count = 1.0f / (float)M; a.relu = relu; a.have_red = ws_is_zero == 2; a.beta = beta ? beta + c0 : nullptr;
-            a.mask = (const unsigned char*)relu_mask; a.mask_mode = mask_mode;
+            bn_bwd_fill(j, s * SLAB, SLAB, &m.a[s], &grid);
             m.start[s + 1] = m.start[s] + grid;
         }
-        if (ws_is_zero != 2) {
+        if (j.red_state != 2) {
             hipLaunchKernelGGL(bn_bwd_reduce_multi_kernel, dim3(m.start[ns]), dim3(256), 0, st, m);
             DANET_CHECK_LAUNCH("bn_bwd_reduce_multi_kernel");
         }
@@ -1045,18 +1114,15 @@ extern "C" int NA_NAME(danet_bn_backward)(const void* dy, const void* x, const v
         return DANET_OK;
     }
     for (int c0 = 0; c0 < C; c0 += SLAB) {
-        const int Cs = C - c0 < SLAB ? C - c0 : SLAB;
-        FlatMap fm; int grid;
-        DANET_CHECK_ARG(make_map(M, C, c0, Cs, &fm, &grid) == 0, "bn_backward: C=%d (M=%ld) unsupported: channels must be a multiple of 4 and the tensor < 2 GB", C, (long)M);
-        if (ws_is_zero != 2) {                     // ws_is_zero == 2: the sums were accumulated by the consumer conv's dgrad epilogue
-            hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(grid), dim3(256), 0, st, (const elem_t*)dy, (const elem_t*)x, (const elem_t*)y,
-                               fm, saved + c0, C, relu, (bn_acc_t*)red_ws + c0, mask_mode, (const unsigned char*)relu_mask,
-                               gamma ? gamma + c0 : nullptr, beta ? beta + c0 : nullptr);
+        BnBwdOne a;
+        bn_bwd_fill(j, c0, slab_width(C, c0), &a, &grid);
+        if (j.red_state != 2) {
+            hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(grid), dim3(256), 0, st, a.dy, a.x, a.y, a.fm, a.saved, a.C, a.relu, a.red,
+                               a.mask_mode, a.mask, a.gamma, a.beta);
             DANET_CHECK_LAUNCH("bn_bwd_reduce_kernel");
         }
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid), dim3(256), 0, st, (const elem_t*)dy, (const elem_t*)x, (const elem_t*)y,
-                           fm, saved + c0, gamma ? gamma + c0 : nullptr, (const bn_acc_t*)red_ws + c0, C, 1.0f / (float)M, relu, (elem_t*)dx, (elem_t*)dres,
-                           dparam ? dparam + c0 : nullptr, mask_mode, (const unsigned char*)relu_mask, beta ? beta + c0 : nullptr);
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid), dim3(256), 0, st, a.dy, a.x, a.y, a.fm, a.saved, a.gamma, a.red, a.C, a.inv_count,
+                           a.relu, a.dx, a.dres, a.dparam, a.mask_mode, a.mask, a.beta);
         DANET_CHECK_LAUNCH("bn_bwd_apply_kernel");
     }
     return DANET_OK;
@@ -1071,15 +1137,15 @@ extern "C" int NA_NAME(danet_channel_sum)(const void* x, int64_t M, int C, doubl
 {
     DANET_ENTER();
     DANET_CHECK_ARG(x && out && M > 0 && C > 0 && C % VW == 0 && ncopy >= 1 && ncopy <= 64, "channel_sum: bad arguments (C=%d must be a multiple of %d)", C, VW);
+    DANET_CHECK_ARG(slabs_map(M, C), "channel_sum: C=%d (M=%ld) unsupported", C, (long)M);
     hipStream_t st = (hipStream_t)stream;
     if (!out_is_zero) {
         hipError_t err = danet::zero_async(out, sizeof(double) * (size_t)C * ncopy, st);
         if (err != hipSuccess) return danet::fail(DANET_ERR_HIP, "channel_sum: memset: %s", hipGetErrorString(err));
     }
     for (int c0 = 0; c0 < C; c0 += SLAB) {
-        const int Cs = C - c0 < SLAB ? C - c0 : SLAB;
         FlatMap fm; int grid;
-        DANET_CHECK_ARG(make_map(M, C, c0, Cs, &fm, &grid) == 0, "channel_sum: C=%d (M=%ld) unsupported", C, (long)M);
+        make_map(M, C, c0, slab_width(C, c0), &fm, &grid);          // (cannot fail: slabs_map has walked the same slabs)
         // every workgroup ends with one atomic per channel on the SAME C addresses (no replicas here): 1024 workgroups serialised
         // there; one workgroup per compute unit reads as fast and queues a quarter of the atomics (A-B in the step: within noise)
         const int cap = ncopy >= 4 ? 1024 : 256;
@@ -1096,13 +1162,10 @@ extern "C" int NA_NAME(danet_sum_relu_forward)(const void* const* terms /* host 
     DANET_ENTER();
     DANET_CHECK_ARG(terms && shifts && y && nterms >= 1 && nterms <= 4 && C % VW == 0, "sum_relu_forward: bad arguments");
     SumP p;
-    p.nterms = nterms; p.B = B; p.H = H; p.W = W; p.C = C;
-    for (int i = 0; i < 4; ++i) { p.in[i] = i < nterms ? (const elem_t*)terms[i] : nullptr; p.shift[i] = i < nterms ? shifts[i] : 0; }
-    for (int i = 0; i < nterms; ++i)
-        DANET_CHECK_ARG(p.in[i] && p.shift[i] >= 0 && (H % (1 << p.shift[i])) == 0 && (W % (1 << p.shift[i])) == 0, "sum_relu_forward: term %d", i);
-    const long nvec = (long)B * H * W * (C / VW);
-    long blocks = (nvec + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(sum_relu_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, (elem_t*)y, relu);
+    int grid;
+    const int bad = sum_fill(terms, shifts, nterms, B, H, W, C, &p, &grid);
+    DANET_CHECK_ARG(bad < 0, "sum_relu_forward: term %d", bad);
+    hipLaunchKernelGGL(sum_relu_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, (elem_t*)y, relu);
     DANET_CHECK_LAUNCH("sum_relu_kernel");
     return DANET_OK;
 }
@@ -1113,27 +1176,18 @@ extern "C" int NA_NAME(danet_sum_relu_backward_all)(const void* gy, const void* 
                                            void* d0, void* d1, void* d2, void* d3, void* stream)
 {
     DANET_ENTER();
-    void* d[4] = {d0, d1, d2, d3};
-    int smax = -1;
-    for (int s_ = 0; s_ < 4; ++s_) if (d[s_]) smax = s_;
-    DANET_CHECK_ARG(gy && (!relu || y) && C % VW == 0 && smax >= 0 && H % (1 << smax) == 0 && W % (1 << smax) == 0,
-                    "sum_relu_backward_all: bad arguments");
+    const SumBwdJob j = {gy, y, B, H, W, C, relu, {d0, d1, d2, d3}};
+    int smax, grid;
+    DANET_CHECK_ARG(sum_bwd_plan(j, &smax, &grid), "sum_relu_backward_all: bad arguments");
     SumBwdAll out;
-    for (int s_ = 0; s_ < 4; ++s_) out.d[s_] = (elem_t*)d[s_];
-    const long nvec = (long)B * (H >> smax) * (W >> smax) * (C / VW);
-    long blocks = (nvec + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(sum_relu_bwd_all_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const elem_t*)gy,
+    for (int s_ = 0; s_ < 4; ++s_) out.d[s_] = (elem_t*)j.d[s_];
+    hipLaunchKernelGGL(sum_relu_bwd_all_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (const elem_t*)gy,
                        (const elem_t*)y, B, H, W, C, smax, relu, out);
     DANET_CHECK_LAUNCH("sum_relu_bwd_all_kernel");
     return DANET_OK;
 }
 
-// Multi-problem forms (host job arrays, n <= 4): the fuse sums of one HighResolutionModule / their gradients in ONE launch each.
-//  forward job  { const void* terms[4]; int shifts[4]; int nterms, B, H, W, C, relu; void* y; }
-//  backward job { const void* gy; const void* y; int B, H, W, C, relu; void* d[4]; }      d[s] = gradient of the terms with shift s (NULL: none)
-struct SumFwdJob { const void* terms[4]; int shifts[4]; int nterms, B, H, W, C, relu; void* y; };
-struct SumBwdJob { const void* gy; const void* y; int B, H, W, C, relu; void* d[4]; };
-
+// Multi-problem forms (host job arrays, n <= NSM): the fuse sums of one HighResolutionModule / their gradients in ONE launch each.
 extern "C" int NA_NAME(danet_sum_relu_forward_multi)(const void* jobs_, int n, void* stream)
 {
     DANET_ENTER();
@@ -1143,15 +1197,11 @@ extern "C" int NA_NAME(danet_sum_relu_forward_multi)(const void* jobs_, int n, v
     for (int i = 0; i < n; ++i) {
         const SumFwdJob& j = jobs[i];
         DANET_CHECK_ARG(j.y && j.nterms >= 1 && j.nterms <= 4 && j.C % VW == 0 && j.B > 0, "sum_relu_forward_multi: job %d: bad arguments", i);
-        SumP& p = m.p[i];
-        p.nterms = j.nterms; p.B = j.B; p.H = j.H; p.W = j.W; p.C = j.C;
-        for (int t = 0; t < 4; ++t) { p.in[t] = t < j.nterms ? (const elem_t*)j.terms[t] : nullptr; p.shift[t] = t < j.nterms ? j.shifts[t] : 0; }
-        for (int t = 0; t < j.nterms; ++t)
-            DANET_CHECK_ARG(p.in[t] && p.shift[t] >= 0 && (j.H % (1 << p.shift[t])) == 0 && (j.W % (1 << p.shift[t])) == 0, "sum_relu_forward_multi: job %d term %d", i, t);
+        int grid;
+        const int bad = sum_fill(j.terms, j.shifts, j.nterms, j.B, j.H, j.W, j.C, &m.p[i], &grid);
+        DANET_CHECK_ARG(bad < 0, "sum_relu_forward_multi: job %d term %d", i, bad);
         m.y[i] = (elem_t*)j.y; m.relu[i] = j.relu;
-        const long nvec = (long)j.B * j.H * j.W * (j.C / VW);
-        long blocks = (nvec + 255) / 256; if (blocks > 4096) blocks = 4096;
-        m.start[i + 1] = m.start[i] + (int)blocks;
+        m.start[i + 1] = m.start[i] + grid;
     }
     hipLaunchKernelGGL(sum_relu_multi_kernel, dim3((unsigned)m.start[n]), dim3(256), 0, (hipStream_t)stream, m);
     DANET_CHECK_LAUNCH("sum_relu_multi_kernel");
@@ -1166,16 +1216,12 @@ extern "C" int NA_NAME(danet_sum_relu_backward_all_multi)(const void* jobs_, int
     SumBwdMulti m; m.n = n; m.start[0] = 0;
     for (int i = 0; i < n; ++i) {
         const SumBwdJob& j = jobs[i];
-        int smax = -1;
-        for (int s_ = 0; s_ < 4; ++s_) if (j.d[s_]) smax = s_;
-        DANET_CHECK_ARG(j.gy && (!j.relu || j.y) && j.C % VW == 0 && smax >= 0 && j.H % (1 << smax) == 0 && j.W % (1 << smax) == 0,
-                        "sum_relu_backward_all_multi: job %d: bad arguments", i);
+        int smax, grid;
+        DANET_CHECK_ARG(sum_bwd_plan(j, &smax, &grid), "sum_relu_backward_all_multi: job %d: bad arguments", i);
         SumBwdMultiOne& a = m.a[i];
         a.gy = (const elem_t*)j.gy; a.y = (const elem_t*)j.y; a.B = j.B; a.H = j.H; a.W = j.W; a.C = j.C; a.smax = smax; a.relu = j.relu;
         for (int s_ = 0; s_ < 4; ++s_) a.out.d[s_] = (elem_t*)j.d[s_];
-        const long nvec = (long)j.B * (j.H >> smax) * (j.W >> smax) * (j.C / VW);
-        long blocks = (nvec + 255) / 256; if (blocks > 4096) blocks = 4096;
-        m.start[i + 1] = m.start[i] + (int)blocks;
+        m.start[i + 1] = m.start[i] + grid;
     }
     hipLaunchKernelGGL(sum_relu_bwd_all_multi_kernel, dim3((unsigned)m.start[n]), dim3(256), 0, (hipStream_t)stream, m);
     DANET_CHECK_LAUNCH("sum_relu_bwd_all_multi_kernel");
@@ -1187,9 +1233,8 @@ extern "C" int NA_NAME(danet_sum_relu_backward)(const void* gy, const void* y, i
 {
     DANET_ENTER();
     DANET_CHECK_ARG(gy && d_term && (!relu || y) && C % VW == 0 && shift >= 0, "sum_relu_backward: bad arguments");
-    const long nvec = (long)B * (H >> shift) * (W >> shift) * (C / VW);
-    long blocks = (nvec + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(sum_relu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const elem_t*)gy,
+    const int grid = flat_grid((long)B * (H >> shift) * (W >> shift) * (C / VW));
+    hipLaunchKernelGGL(sum_relu_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (const elem_t*)gy,
                        (const elem_t*)y, B, H, W, C, shift, relu, (elem_t*)d_term);
     DANET_CHECK_LAUNCH("sum_relu_bwd_kernel");
     return DANET_OK;
@@ -1197,17 +1242,7 @@ extern "C" int NA_NAME(danet_sum_relu_backward)(const void* gy, const void* y, i
 
 
 // ---------------------------------------------------------------------------------------------
-// Multi-tensor BatchNorm (training mode): jobs on the host, up to 4 per call, C <= 1024 each.
-//  forward job:  { x, res, y, gamma, beta, running_mean, running_var, saved, sums; int64 M; int C, sums_state, relu }
-//      sums_state: 1 = sums is zeroed scratch (statistics pass needed), 2 = statistics already accumulated by the conv epilogue
-//      mask: NULL or M*C/4 bytes that receive the ReLU gate of y (bit j of byte i = channel 4i+j positive)
-//  backward job: { dy, x, y, gamma, saved, dx, dres, dparam, red, beta, mask; int64 M; int C, red_state, relu, mask_mode }
-//      (red_state as above; mask_mode: see ldmask above)
-struct BnFwdJob { const void* x; const void* res; void* y; const float* gamma; const float* beta; float* running_mean; float* running_var;
-                  float* saved; float* sums; void* mask; int64_t M; int C, sums_state, relu; };
-struct BnBwdJob { const void* dy; const void* x; const void* y; const float* gamma; const float* saved; void* dx; void* dres; float* dparam;
-                  float* red; const float* beta; const void* mask; int64_t M; int C, red_state, relu, mask_mode; };
-
+// Multi-tensor BatchNorm (training mode): BnFwdJob / BnBwdJob arrays on the host, up to NBM per call, C <= 1024 each.
 extern "C" int NA_NAME(danet_bn_forward_multi)(const void* jobs_, int n, float momentum, float eps, void* stream)
 {
     DANET_ENTER();
@@ -1217,23 +1252,20 @@ extern "C" int NA_NAME(danet_bn_forward_multi)(const void* jobs_, int n, float m
     BnFwdMulti m; m.n = n; m.momentum = momentum; m.eps = eps; m.mode = 0; m.start[0] = 0;
     for (int i = 0; i < n; ++i) {
         const BnFwdJob& j = jobs[i];
-        DANET_CHECK_ARG(j.x && j.y && j.saved && j.sums && j.M > 0 && j.C > 0 && j.C <= SLAB && (j.sums_state == 1 || j.sums_state == 2),
+        DANET_CHECK_ARG(bn_fwd_ok(j) && j.saved && j.sums && j.C <= SLAB && (j.sums_state == 1 || j.sums_state == 2),
                         "bn_forward_multi: job %d: bad arguments (C <= %d, zeroed or pre-accumulated sums required)", i, SLAB);
 #ifdef NA_F32
         DANET_CHECK_ARG(j.sums_state == 1, "bn_forward_multi_f32: job %d: the fp32 statistics are shifted sums (bn_stats_kernel): no pre-accumulated sums", i);
 #endif
-        BnFwdOne& a = m.a[i];
         int grid;
-        DANET_CHECK_ARG(make_map(j.M, j.C, 0, j.C, &a.fm, &grid) == 0, "bn_forward_multi: job %d: C=%d unsupported", i, j.C);
-        if (j.sums_state == 1) {
-            hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(256), 0, st, (const elem_t*)j.x, a.fm, (bn_acc_t*)j.sums, j.C);
-            DANET_CHECK_LAUNCH("bn_stats_kernel");
-        }
-        a.x = (const elem_t*)j.x; a.res = (const elem_t*)j.res; a.y = (elem_t*)j.y; a.sums = (const bn_acc_t*)j.sums; a.gamma = j.gamma; a.beta = j.beta;
-        a.running_mean = j.running_mean; a.running_var = j.running_var; a.saved = j.saved; a.C = j.C; a.mask = (unsigned char*)j.mask;
-        a.inv_count = 1.0f / (float)j.M; a.unbias = j.M > 1 ? (float)j.M / (float)(j.M - 1) : 1.f; a.relu = j.relu;
+        DANET_CHECK_ARG(bn_fwd_fill(j, 0, j.C, &m.a[i], &grid) == 0, "bn_forward_multi: job %d: C=%d unsupported", i, j.C);
         m.start[i + 1] = m.start[i] + grid;
     }
+    for (int i = 0; i < n; ++i)                     // every job has passed: only now is anything enqueued
+        if (jobs[i].sums_state == 1) {
+            bn_stats_launch(m.a[i], m.start[i + 1] - m.start[i], st);
+            DANET_CHECK_LAUNCH("bn_stats_kernel");
+        }
     hipLaunchKernelGGL(bn_apply_multi_kernel, dim3(m.start[n]), dim3(256), 0, st, m);
     DANET_CHECK_LAUNCH("bn_apply_multi_kernel");
     return DANET_OK;
@@ -1249,17 +1281,11 @@ extern "C" int NA_NAME(danet_bn_backward_multi)(const void* jobs_, int n, void* 
     bool need_reduce = false;
     for (int i = 0; i < n; ++i) {
         const BnBwdJob& j = jobs[i];
-        DANET_CHECK_ARG(j.dy && j.x && j.dx && j.saved && j.red && j.M > 0 && j.C > 0 && j.C <= SLAB &&
-                        (j.red_state == 1 || j.red_state == 2), "bn_backward_multi: job %d: bad arguments", i);
-        DANET_CHECK_ARG(!j.relu || (j.mask_mode == 0 && j.y) || (j.mask_mode == 1 && j.mask) || (j.mask_mode == 2 && !j.dres),
-                        "bn_backward_multi: job %d: ReLU gate (mask_mode %d) lacks its input", i, j.mask_mode);
-        BnBwdOne& a = m.a[i];
+        DANET_CHECK_ARG(bn_bwd_ok(j) && j.C <= SLAB && (j.red_state == 1 || j.red_state == 2), "bn_backward_multi: job %d: bad arguments", i);
+        DANET_CHECK_ARG(bn_gate_ok(j), "bn_backward_multi: job %d: ReLU gate (mask_mode %d) lacks its input", i, j.mask_mode);
         int grid;
-        DANET_CHECK_ARG(make_map(j.M, j.C, 0, j.C, &a.fm, &grid) == 0, "bn_backward_multi: job %d: C=%d unsupported", i, j.C);
-        a.dy = (const elem_t*)j.dy; a.x = (const elem_t*)j.x; a.y = (const elem_t*)j.y; a.saved = j.saved; a.gamma = j.gamma; a.red = (bn_acc_t*)j.red;
-        a.dx = (elem_t*)j.dx; a.dres = (elem_t*)j.dres; a.dparam = j.dparam; a.C = j.C; a.inv_count = 1.0f / (float)j.M; a.relu = j.relu;
-        a.have_red = j.red_state == 2; a.beta = j.beta; a.mask = (const unsigned char*)j.mask; a.mask_mode = j.mask_mode;
-        need_reduce = need_reduce || !a.have_red;
+        DANET_CHECK_ARG(bn_bwd_fill(j, 0, j.C, &m.a[i], &grid) == 0, "bn_backward_multi: job %d: C=%d unsupported", i, j.C);
+        need_reduce = need_reduce || !m.a[i].have_red;
         m.start[i + 1] = m.start[i] + grid;
     }
     if (need_reduce) {
@@ -1323,24 +1349,20 @@ static int onepass_plan_rows(const BnBwdJob* jobs, int n, BnOnePass* ms /* [NBM]
     BnOnePass* m = nullptr;
     for (int i = 0; i < n; ++i) {
         const BnBwdJob& j = jobs[i];
-        if (!(j.dy && j.x && j.dx && j.saved && j.red && j.M > 0 && j.C > 0 && (j.C <= SLAB || wide_slabs(j.C) > 1) && j.red_state == 1)) return 0;
-        if (j.relu && !((j.mask_mode == 1 && j.mask) || (j.mask_mode == 2 && !j.dres))) return 0;
+        if (!(bn_bwd_ok(j) && (j.C <= SLAB || wide_slabs(j.C) > 1) && j.red_state == 1)) return 0;
+        if (!bn_gate_ok(j) || (j.relu && j.mask_mode == 0)) return 0;        // (the saved output is not among what a lane keeps)
       // a wide tensor: one entry per channel slab (same rows, per-channel buffers offset, the full width as their stride)
       for (int s = 0, ns = wide_slabs(j.C); s < ns; ++s) {
-        const int c0 = s * SLAB, Cs = j.C < SLAB ? j.C : SLAB;
         BnBwdOne a;
         int grid;
-        if (make_map(j.M, j.C, c0, Cs, &a.fm, &grid) != 0) return 0;
+        if (bn_bwd_fill(j, s * SLAB, j.C < SLAB ? j.C : SLAB, &a, &grid) != 0) return 0;
         // rows per lane <= rows_per_lane: blocks >= rows / (rows per block step * rows_per_lane)
         const long rows_per_block = a.fm.span / a.fm.CV;
         long blocks = (j.M + rows_per_block * rows_per_lane - 1) / (rows_per_block * rows_per_lane);
         if (blocks < 1) blocks = 1;
         if (blocks > max_blocks) return 0;
         a.fm.rstep = (int)(rows_per_block * blocks);
-        a.dy = (const elem_t*)j.dy; a.x = (const elem_t*)j.x; a.y = (const elem_t*)j.y; a.saved = j.saved + c0; a.gamma = j.gamma ? j.gamma + c0 : nullptr;
-        a.red = (bn_acc_t*)j.red + c0;
-        a.dx = (elem_t*)j.dx; a.dres = (elem_t*)j.dres; a.dparam = j.dparam ? j.dparam + c0 : nullptr; a.C = j.C; a.inv_count = 1.0f / (float)j.M; a.relu = j.relu;
-        a.have_red = 0; a.beta = j.beta ? j.beta + c0 : nullptr; a.mask = (const unsigned char*)j.mask; a.mask_mode = j.mask_mode;
+        a.have_red = 0;
         if (!m || m->n == NBM || m->start[m->n] + blocks > max_blocks) {
             if (nl == NBM) return 0;
             m = &ms[nl++]; m->n = 0; m->start[0] = 0;

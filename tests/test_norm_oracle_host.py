@@ -1,6 +1,8 @@
 """CPU checks of tests/norm_oracle.py: the float64 restatements against torch in float64, the byte-mask layout against a
 hand-written example, and the case tables -- every "exists for" claim recomputed from make_map's formulas as norm_oracle restates
 them, the exactness conditions of the integer cases, and the share of ReLU gates the mask comparison has to leave out."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -220,3 +222,153 @@ def test_bounds_catch_the_faults_the_old_tolerance_let_pass():
     assert (np.abs(b.view(np.float32).astype(np.float64) - o.y) > bound).mean() > 0.2
     # one wrong gate bit moves dres by a whole integer gradient value and dbeta by it: the exact tests see both
     assert np.abs(i.dy).min() == 0 and (np.abs(i.dy) >= 1).mean() > 0.9
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='its evidence is that every launch fails where there is no device, and its fake '
+                                                      'pointers must never reach a GPU')
+def test_refused_calls_answer_err_arg_with_their_text_and_enqueue_nothing():
+    """Refused argument sets of every entry of csrc/norm_act.hip, in both instantiations: DANET_ERR_ARG and the exact text.  Without
+    a device every launch attempt answers DANET_ERR_HIP (the premise, asserted first), so DANET_ERR_ARG also says that the call had
+    enqueued nothing -- the zeroing kernel and bn_stats_kernel included -- when it refused."""
+    from danet_densepose2smpl_amd import _lib
+    L = _lib.lib()
+    ERR_ARG, ERR_HIP, NBM, NSM = -1, -2, 12, 4
+    P = ctypes.c_void_p(64)
+    BIG = dict(M=1 << 22, C=512)                                   # 2^32 bytes in bf16: past the 32-bit byte offsets ("< 2 GB")
+    GB2 = 'C=512 (M=4194304) unsupported'
+    GATE = "bn_backward: ReLU gate: mask_mode 0 needs y, 1 the forward's byte mask, 2 (recompute from x) no residual"
+    SHIFTED = 'the fp32 statistics are shifted sums (bn_stats_kernel): no pre-accumulated sums'
+
+    def call(name, order, defaults, kw):
+        a = dict(defaults, **kw)
+        rc = getattr(L, name)(*[a[k] for k in order.split()])
+        return rc, L.danet_last_error().decode()
+
+    def arr(ctype, values):
+        return (ctype * len(values))(*values)
+
+    def fwd_jobs(*kws):
+        jobs = (_lib.BnFwdJob * (NBM + 1))()
+        for j, kw in zip(jobs, kws):
+            for k in ('x', 'y', 'saved', 'sums'):
+                setattr(j, k, 64)
+            j.M, j.C, j.sums_state = 8, 8, 1
+            for k, v in kw.items():
+                setattr(j, k, v)
+        return ctypes.addressof(jobs), jobs
+
+    def bwd_jobs(*kws):
+        jobs = (_lib.BnBwdJob * (NBM + 1))()
+        for j, kw in zip(jobs, kws):
+            for k in ('dy', 'x', 'dx', 'saved', 'red'):
+                setattr(j, k, 64)
+            j.M, j.C, j.red_state = 8, 8, 1
+            for k, v in kw.items():
+                setattr(j, k, v)
+        return ctypes.addressof(jobs), jobs
+
+    def sum_fwd_jobs(*kws):
+        jobs = (_lib.SumFwdJob * (NSM + 1))()
+        for j, kw in zip(jobs, kws):
+            j.terms[0], j.terms[1], j.shifts[1], j.nterms, j.B, j.H, j.W, j.C, j.y = 64, 64, 1, 2, 1, 8, 8, 8, 64
+            for k, v in kw.items():
+                setattr(j, k, v)
+        return ctypes.addressof(jobs), jobs
+
+    def sum_bwd_jobs(*kws):
+        jobs = (_lib.SumBwdJob * (NSM + 1))()
+        for j, kw in zip(jobs, kws):
+            j.gy, j.B, j.H, j.W, j.C = 64, 1, 8, 8, 8
+            j.d[1] = 64
+            for k, v in kw.items():
+                setattr(j, k, v)
+        return ctypes.addressof(jobs), jobs
+
+    FWD = ('x res y M C gamma beta rm rv saved sums ws_is_zero momentum eps training relu mask stream',
+           dict(x=P, res=None, y=P, M=8, C=8, gamma=None, beta=None, rm=P, rv=P, saved=P, sums=P, ws_is_zero=1, momentum=0.1, eps=1e-5,
+                training=1, relu=0, mask=None, stream=None))
+    BWD = ('dy x y M C gamma saved relu dx dres dparam red ws_is_zero mask_mode mask beta stream',
+           dict(dy=P, x=P, y=None, M=8, C=8, gamma=None, saved=P, relu=0, dx=P, dres=None, dparam=None, red=P, ws_is_zero=1, mask_mode=0,
+                mask=None, beta=None, stream=None))
+    CSUM = ('x M C out out_is_zero ncopy stream', dict(x=P, M=8, C=8, out=P, out_is_zero=1, ncopy=1, stream=None))
+    SFWD = ('terms shifts nterms B H W C relu y stream',
+            dict(terms=arr(ctypes.c_void_p, [64, 64, 64, 64]), shifts=arr(ctypes.c_int, [0, 1, 0, 0]), nterms=2, B=1, H=8, W=8, C=8, relu=1, y=P,
+                 stream=None))
+    SALL = ('gy y B H W C relu d0 d1 d2 d3 stream', dict(gy=P, y=P, B=1, H=8, W=8, C=8, relu=1, d0=P, d1=None, d2=None, d3=None, stream=None))
+    SBWD = ('gy y B H W C shift relu d_term stream', dict(gy=P, y=P, B=1, H=8, W=8, C=8, shift=1, relu=1, d_term=P, stream=None))
+
+    for suffix in ('', '_f32'):
+        f32 = suffix == '_f32'
+        # the premise: an accepted call reaches its launch, and without a device the launch fails
+        rc, msg = call('danet_bn_forward' + suffix, *FWD, dict(training=0))
+        assert rc == ERR_HIP and msg.startswith('bn_apply'), (suffix, rc, msg)
+
+        single = [
+            ('danet_bn_forward', FWD, [
+                (dict(x=None), 'bn_forward: bad arguments'), (dict(M=0), 'bn_forward: bad arguments'),
+                (dict(saved=None), 'bn_forward: missing buffers'), (dict(training=0, rm=None), 'bn_forward: missing buffers'),
+                (dict(C=6), 'bn_forward: C=6 must be a multiple of 4'),
+                (dict(BIG, training=0), 'bn_forward: %s: channels must be a multiple of 4 and the tensor < 2 GB' % GB2),
+                (dict(BIG, ws_is_zero=0), 'bn_forward: %s: channels must be a multiple of 4 and the tensor < 2 GB' % GB2)]
+             + ([(dict(ws_is_zero=2), 'bn_forward_f32: ' + SHIFTED)] if f32 else [])),
+            ('danet_bn_backward', BWD, [
+                (dict(dx=None), 'bn_backward: bad arguments'),
+                (dict(relu=1, mask_mode=0), GATE), (dict(relu=1, mask_mode=1, y=P), GATE), (dict(relu=1, mask_mode=2, dres=P), GATE),
+                (dict(C=6), 'bn_backward: C=6 must be a multiple of 4'),
+                (dict(BIG, ws_is_zero=0), 'bn_backward: %s: channels must be a multiple of 4 and the tensor < 2 GB' % GB2)]),
+            ('danet_channel_sum', CSUM, [
+                (dict(ncopy=0), 'channel_sum: bad arguments (C=8 must be a multiple of 4)'),
+                (dict(ncopy=65), 'channel_sum: bad arguments (C=8 must be a multiple of 4)'),
+                (dict(C=6), 'channel_sum: bad arguments (C=6 must be a multiple of 4)'),
+                (dict(BIG, out_is_zero=0), 'channel_sum: ' + GB2)]),
+            ('danet_sum_relu_forward', SFWD, [
+                (dict(nterms=0), 'sum_relu_forward: bad arguments'), (dict(nterms=5), 'sum_relu_forward: bad arguments'),
+                (dict(C=6), 'sum_relu_forward: bad arguments'),
+                (dict(terms=arr(ctypes.c_void_p, [64, None, 64, 64])), 'sum_relu_forward: term 1'),
+                (dict(H=6, shifts=arr(ctypes.c_int, [0, 2, 0, 0])), 'sum_relu_forward: term 1'),
+                (dict(shifts=arr(ctypes.c_int, [-1, 1, 0, 0])), 'sum_relu_forward: term 0')]),
+            ('danet_sum_relu_backward_all', SALL, [
+                (dict(d0=None), 'sum_relu_backward_all: bad arguments'), (dict(y=None), 'sum_relu_backward_all: bad arguments'),
+                (dict(H=6, d2=P), 'sum_relu_backward_all: bad arguments')]),
+            ('danet_sum_relu_backward', SBWD, [
+                (dict(shift=-1), 'sum_relu_backward: bad arguments'), (dict(d_term=None), 'sum_relu_backward: bad arguments')]),
+        ]
+        for name, (order, defaults), cases in single:
+            for kw, text in cases:
+                assert call(name + suffix, order, defaults, kw) == (ERR_ARG, text), (name + suffix, kw)
+
+        good = {}
+        multi = [
+            ('danet_bn_forward_multi', fwd_jobs, NBM, lambda p, n: (p, n, 0.1, 1e-5, None), 'bn_forward_multi: 1..12 jobs', [
+                # job 0 is accepted and asks for a statistics pass (sums_state 1): refusing job 1 must come before that launch
+                ((good, dict(y=None)), 'bn_forward_multi: job 1: bad arguments (C <= 1024, zeroed or pre-accumulated sums required)'),
+                ((good, dict(BIG)), 'bn_forward_multi: job 1: C=512 unsupported'),
+                ((dict(C=2048),), 'bn_forward_multi: job 0: bad arguments (C <= 1024, zeroed or pre-accumulated sums required)')]
+             + ([((dict(sums_state=2),), 'bn_forward_multi_f32: job 0: ' + SHIFTED), ((good, dict(sums_state=2)), 'bn_forward_multi_f32: job 1: ' + SHIFTED)]
+                if f32 else [])),
+            ('danet_bn_backward_multi', bwd_jobs, NBM, lambda p, n: (p, n, None), 'bn_backward_multi: 1..12 jobs', [
+                ((good, dict(dx=None)), 'bn_backward_multi: job 1: bad arguments'),
+                ((dict(C=2048),), 'bn_backward_multi: job 0: bad arguments'),
+                ((good, dict(red_state=0)), 'bn_backward_multi: job 1: bad arguments'),
+                ((good, dict(relu=1, mask_mode=0)), 'bn_backward_multi: job 1: ReLU gate (mask_mode 0) lacks its input'),
+                ((good, dict(relu=1, mask_mode=1, y=64)), 'bn_backward_multi: job 1: ReLU gate (mask_mode 1) lacks its input'),
+                ((good, dict(relu=1, mask_mode=2, dres=64)), 'bn_backward_multi: job 1: ReLU gate (mask_mode 2) lacks its input'),
+                ((good, dict(BIG)), 'bn_backward_multi: job 1: C=512 unsupported')]),
+            ('danet_sum_relu_forward_multi', sum_fwd_jobs, NSM, lambda p, n: (p, n, None), 'sum_relu_forward_multi: 1..4 jobs', [
+                ((good, dict(y=None)), 'sum_relu_forward_multi: job 1: bad arguments'),
+                ((good, dict(nterms=5)), 'sum_relu_forward_multi: job 1: bad arguments'),
+                ((good, dict(H=7)), 'sum_relu_forward_multi: job 1 term 1')]),
+            ('danet_sum_relu_backward_all_multi', sum_bwd_jobs, NSM, lambda p, n: (p, n, None), 'sum_relu_backward_all_multi: 1..4 jobs', [
+                ((good, dict(gy=None)), 'sum_relu_backward_all_multi: job 1: bad arguments'),
+                ((good, dict(relu=1)), 'sum_relu_backward_all_multi: job 1: bad arguments'),
+                ((good, dict(H=7)), 'sum_relu_backward_all_multi: job 1: bad arguments')]),
+        ]
+        for name, make, nmax, args, count_text, cases in multi:
+            fn = getattr(L, name + suffix)
+            p, keep = make(*([good] * (nmax + 1)))
+            for n in (0, nmax + 1):
+                assert (fn(*args(p, n)), L.danet_last_error().decode()) == (ERR_ARG, count_text), (name + suffix, n)
+            assert (fn(*args(None, 1)), L.danet_last_error().decode()) == (ERR_ARG, count_text), name + suffix
+            for kws, text in cases:
+                p, keep = make(*kws)
+                assert (fn(*args(p, len(kws))), L.danet_last_error().decode()) == (ERR_ARG, text), (name + suffix, kws)
